@@ -7,19 +7,24 @@ uniform over the zoom levels that have decodable fixtures, then uniform over tha
 test/fixtures).  A "step" is one decode launch over the whole batch: every Id/Geometry stream of every
 tile, inputs (tile bytes + descriptor table) already resident in HBM, outputs written to HBM.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it samples and plans the batch, uploads it, warms up, times
+the K steps and prints one JSON line (`value`, `ms_per_step` = wall clock of the K steps / K, the roofline of
+the decode launch, the build ids).  `--dump-outputs DIR` then writes what the last timed launch left in HBM
+(dump_outputs below).  Everything else the benchmark measures rides behind `--full`: BASELINE configs 1-4
+(`configs`), the PCIe-inclusive and C-ABI host timings, the device plan (+ decode:
+`device_plan.plan_plus_decode`), assembly and property legs, the strong-scaling shard projection, the weak
+figure at N > 1 and the CPU baseline; the `--no-*` / `--*-reps 0` switches drop single legs of a full run.
 
 N>1: one process per GPU -- either started by torch.distributed.run (WORLD_SIZE/RANK/LOCAL_RANK in the
 environment) or, without a launcher, spawned here (one child per GPU, started before anything touches
 the GPU; fails if fewer than N GPUs are visible).  Scaling is strong by default, as BASELINE config 5
 states it ("10k-tile batch ... sharded across 8xMI355X"): one 10k-tile batch split over the ranks by the
-greedy longest-processing-time byte balance of SURVEY §8(e).  At N > 1 the line also carries `weak`: every
-rank then decodes a whole 10k-tile batch of its own (seed 20250117 + rank), the per-GPU-work-fixed figure;
-`--scaling weak` makes that the headline instead.  Tiles are independent, so there is no collective on
-the data path and no RCCL: a gloo group carries the timing barriers and gathers the per-rank numbers.
-Besides `value` (config 5) the line carries BASELINE configs 2-4 (`configs`), the PCIe-inclusive and
-C-ABI host timings, the device plan (+ decode: `device_plan.plan_plus_decode`), assembly and property legs,
-and the CPU baseline.
+greedy longest-processing-time byte balance of SURVEY §8(e).  At N > 1 a `--full` line also carries `weak`:
+every rank then decodes a whole 10k-tile batch of its own (seed 20250117 + rank), the per-GPU-work-fixed
+figure; `--scaling weak` makes that the headline instead.  Tiles are independent, so there is no collective
+on the data path and no RCCL: a gloo group carries the timing barriers and gathers the per-rank numbers.
 """
 from __future__ import annotations
 
@@ -675,6 +680,62 @@ def timed_steps(batch, stream, steps, torch, dev, barrier):
     return wall, float(np.mean([s.elapsed_time(e) for s, e in ev]))
 
 
+def stream_results(batch):
+    """(status, consumed) of every stream in plan order: DeviceBatch.results() without the output bytes."""
+    plan = batch.plan
+    res = batch.d_res.cpu().numpy().reshape(-1, 2)[:plan.num_descs]
+    return res[plan.streams["desc_index"]] if plan.num_streams else res
+
+
+DUMP_MAX_VALUES = 4 << 20  # decoded values sampled per rank: 32 MiB of float64
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(dirname, batch, rank, world):
+    """--dump-outputs: what a caller of the timed path (DeviceBatch.decode) receives, read back after the
+    last timed launch and written as float64 .npy files (every int32 / uint8 value exactly, int64 ids
+    exactly up to 2^53), under 64 MB in all:
+      status.npy, consumed.npy    every stream's result record, plan order
+      values.npy                  the decoded arrays of a sample of the streams, one after the other: a
+                                  numpy.random.default_rng(SEED) permutation of the streams, taken while
+                                  the running total stays within DUMP_MAX_VALUES values, in plan order
+      value_streams.npy           the plan-order index of each sampled stream
+      value_offsets.npy           where each sampled stream's array starts in values.npy (one more entry
+                                  than streams: the total)
+    The batch, the plan and the sample depend only on the arguments, so two builds run with the same
+    arguments write arrays that compare entry for entry.  At N > 1 every rank writes its own shard's files
+    with a `_rank<r>` suffix."""
+    import torch
+
+    plan = batch.plan
+    st = plan.streams
+    n = plan.num_streams
+    res = stream_results(batch)
+    order = np.random.default_rng(SEED).permutation(n)
+    elems = st["out_elems"][order].astype(np.int64)
+    k = int(np.searchsorted(np.cumsum(elems), DUMP_MAX_VALUES, side="right"))
+    pick = np.sort(order[:k])
+    if 8 * (2 * n + 2 * k + 1 + int(elems[:k].sum())) + 5 * 128 > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write more than %d bytes (%d streams)" % (DUMP_MAX_BYTES, n))
+    off = st["out_off"][pick].astype(np.int64)
+    nb = (st["out_elems"][pick] * st["elem_bytes"][pick]).astype(np.int64)
+    # the sampled streams' bytes gathered on the device: one copy to the host, not the whole output buffer
+    parts = [batch.d_out[int(o):int(o + b)] for o, b in zip(off, nb)]
+    host = torch.cat(parts).cpu().numpy() if parts else np.zeros(0, dtype=np.uint8)
+    ends = np.cumsum(nb)
+    vals = []
+    for i, e, b in zip(pick, ends, nb):
+        dt = {1: np.uint8, 4: np.int32, 8: np.int64}[int(st["elem_bytes"][i])]
+        vals.append(host[e - b:e].view(dt).astype(np.float64))
+    voff = np.concatenate([[0], np.cumsum(st["out_elems"][pick].astype(np.int64))])
+    arrays = {"status": res[:, 0], "consumed": res[:, 1],
+              "values": np.concatenate(vals) if vals else np.zeros(0), "value_streams": pick, "value_offsets": voff}
+    os.makedirs(dirname, exist_ok=True)
+    sfx = "_rank%d" % rank if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + sfx + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def launch_ranks(args):
     """`bench.py --gpus N` without a launcher: one child process per GPU (RANK/LOCAL_RANK/WORLD_SIZE set
     before the child touches the GPU), rank 0 prints the line.  This parent never initialises HIP."""
@@ -713,6 +774,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the CPU baseline, BASELINE configs 1-4, the end-to-end, C-ABI host, "
+                         "device-plan, assembly, property and strong-shard legs, and at N > 1 the weak figure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's results and a seeded sample of its decoded "
+                         "arrays as DIR/<name>.npy (float64, under 64 MB)")
     ap.add_argument("--tiles", type=int, default=10000)
     ap.add_argument("--scaling", choices=("weak", "strong"), default="strong",
                     help="strong (default): one --tiles batch sharded over the ranks (BASELINE config 5); "
@@ -737,6 +804,8 @@ def main():
                     help="no GPU: sample + plan per rank, time an empty step, print the aggregated line "
                          "(tests the rank launch and aggregation on CPU)")
     args = ap.parse_args()
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the GPU run: a dry run decodes nothing")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         launch_ranks(args)  # exits
@@ -799,15 +868,17 @@ def main():
         for _ in range(args.warmup):
             batch.decode(stream)
         torch.cuda.synchronize(dev)
-        _, res = batch.results()
+        res = stream_results(batch)
         if (res[:, 0] != 0).any():
             raise RuntimeError("decode reported errors on %d streams" % int((res[:, 0] != 0).sum()))
 
         wall, kern_ms = timed_steps(batch, stream, args.steps, torch, dev, barrier)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, batch, rank, world)
 
     legs = {}
     weak = None
-    if world > 1 and args.scaling == "strong" and not args.no_weak:
+    if args.full and world > 1 and args.scaling == "strong" and not args.no_weak:
         # the per-GPU-work-fixed figure beside the strong headline: a whole batch per rank
         wpicks = sample_batch(lib, args.tiles, SEED + rank)
         wplan = covt.Plan.from_tiles([t for _, t in wpicks], covt.FORMAT_GENC, args.id_mode)
@@ -826,7 +897,7 @@ def main():
         weak = {"tiles": len(wpicks), "stream_bytes": int(wplan.in_bytes), "wall_s": wwall, "kernel_ms": wms,
                 "seed": SEED + rank}
         del wplan
-    if not args.dry_run:
+    if args.full and not args.dry_run:
         if args.e2e_reps > 0:
             legs["end_to_end"] = end_to_end(plan, batch, stream, torch, dev, args.e2e_reps)
         if args.abi_host_reps > 0 and rank == 0:
@@ -895,6 +966,7 @@ def main():
             "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True,
             "scaling": args.scaling,
+            "full": args.full,
             "vs_baseline": None,
             "dtype": "int32",
             "data": "fixture-sampled: seeded sample of the reference's committed OMT+Bing COVT tiles",
@@ -950,7 +1022,7 @@ def main():
         line.update(legs)
         line["host_plan_ms"] = round(t_plan * 1e3, 1)  # covt_plan_create: metadata walk, descriptors, host
         line["host_pack_ms"] = round(t_pack * 1e3, 1)  # pack_tiles: copying the tiles into one buffer
-        if not args.no_cpu:  # rank 0, over its own batch, at every N
+        if args.full and not args.no_cpu:  # rank 0, over its own batch, at every N
             cb = cpu_baseline(plan, args, config1_tile(lib))
             c1 = cb.pop("config1")
             line["cpu_baseline"] = cb

@@ -6,6 +6,8 @@ What it writes (all DATA -- inputs and expected outputs, no reference source):
   tiles/{omt,bing,amazon}/*.covt   the reference's committed COVT fixtures (test/fixtures/*/covt),
                                    byte-identical copies; Gen B variants (omt/3_4_5, amazon_here/*)
                                    are not copied.
+  mvt/*.mvt                        the smallest of the reference's OMT MVT originals at each of z10-z13
+                                   (byte-identical copies, 276 KB): inputs of tests/test_mvt_decode.py.
   mvt_digests.json                 per OMT tile and layer: SHA-256 of the per-feature geometry and of
                                    the feature ids decoded from the reference's MVT originals
                                    (test/fixtures/omt/mvt/*.mvt) -- independent of any COVT decoder.
@@ -53,6 +55,21 @@ def copy_tiles():
             if key in EXCLUDED_GEN_B:
                 continue
             shutil.copyfile(f, os.path.join(dst, os.path.basename(f)))
+
+
+def copy_mvt():
+    """The smallest OMT MVT original of each zoom z10-z13 -> mvt/ (the whole set is 32 MB: the lower zooms' tiles
+    are 0.3-1.5 MB each, two of them over 1 MiB)."""
+    best = {}
+    for f in sorted(glob.glob(os.path.join(REF, "omt", "mvt", "*.mvt"))):
+        z = int(os.path.basename(f).split("_")[0])
+        if not 10 <= z <= 13:
+            continue
+        if z not in best or os.path.getsize(f) < os.path.getsize(best[z]):
+            best[z] = f
+    os.makedirs(os.path.join(HERE, "mvt"), exist_ok=True)
+    for f in best.values():
+        shutil.copyfile(f, os.path.join(HERE, "mvt", os.path.basename(f)))
 
 
 def layer_names(t: bytes):
@@ -255,6 +272,7 @@ def main():
             json.dump(mvt_prop_digests(), f, separators=(",", ":"), sort_keys=True)
         return
     copy_tiles()
+    copy_mvt()
     with open(os.path.join(HERE, "kats.json"), "w") as f:
         json.dump(kats(), f, indent=1)
     with open(os.path.join(HERE, "mvt_digests.json"), "w") as f:

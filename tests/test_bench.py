@@ -21,7 +21,7 @@ def _run(args, timeout=240):
 
 def test_gpus2_dry_run_spawns_two_ranks():
     p, lines = _run(["--gpus", "2", "--dry-run", "--tiles", "40", "--steps", "2", "--warmup", "1", "--cpu-iters", "2",
-                     "--scaling", "weak"])
+                     "--scaling", "weak", "--full"])
     assert p.returncode == 0, p.stderr[-2000:]
     assert len(lines) == 1, p.stdout  # rank 0 only
     line = json.loads(lines[0])
@@ -60,7 +60,8 @@ def test_gpus2_default_is_strong_scaling():
     the default shards ONE batch over the ranks by LPT byte balance; the weak figure rides beside it."""
     import bench
 
-    p, lines = _run(["--gpus", "2", "--dry-run", "--tiles", "41", "--steps", "1", "--warmup", "0", "--no-cpu"])
+    p, lines = _run(["--gpus", "2", "--dry-run", "--tiles", "41", "--steps", "1", "--warmup", "0", "--no-cpu",
+                     "--full"])
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads(lines[0])
     assert line["scaling"] == "strong" and "sharded over 2 GPUs" in line["config"]["workload"]
@@ -84,6 +85,25 @@ def test_gpus1_default_is_the_whole_batch():
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads(lines[0])
     assert line["n_gpus"] == 1 and line["per_rank"][0]["tiles"] == 25 and "weak" not in line
+
+
+def test_plain_run_prints_the_headline_only():
+    """Without --full the line carries the headline fields and nothing that takes a run of its own: no CPU
+    baseline, no legs, no weak figure beside a strong N > 1 headline.  --steps is the number of timed steps."""
+    p, lines = _run(["--gpus", "2", "--dry-run", "--tiles", "25", "--steps", "3", "--warmup", "0"])
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert len(lines) == 1, p.stdout
+    line = json.loads(lines[0])
+    assert line["full"] is False and line["cpu_baseline"] is None and "weak" not in line
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "GB/s" and line["higher_is_better"] is True and line["dtype"] == "int32"
+    assert line["metric"] == __import__("bench").METRIC
+    for leg in ("end_to_end", "c_abi_host", "device_plan", "assembly", "properties", "configs", "strong_shards"):
+        assert leg not in line
+    # a dry run decodes nothing, so it has nothing to dump
+    p, lines = _run(["--dry-run", "--tiles", "5", "--dump-outputs", os.path.join(ROOT, "no-such-dir")])
+    assert p.returncode != 0 and not lines and "--dump-outputs" in p.stderr
+    assert not os.path.exists(os.path.join(ROOT, "no-such-dir"))
 
 
 @pytest.mark.skipif(__import__("torch").cuda.device_count() >= 2, reason="host has >= 2 GPUs")
@@ -124,7 +144,7 @@ def test_config_selections_match_survey():
 def test_cpu_baseline_leg_uses_host_cpus():
     import bench
 
-    p, lines = _run(["--dry-run", "--tiles", "30", "--steps", "1", "--warmup", "0", "--cpu-iters", "3"])
+    p, lines = _run(["--dry-run", "--tiles", "30", "--steps", "1", "--warmup", "0", "--cpu-iters", "3", "--full"])
     assert p.returncode == 0, p.stderr[-2000:]
     cb = json.loads(lines[0])["cpu_baseline"]
     n, info = bench.host_cpus()

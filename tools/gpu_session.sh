@@ -36,8 +36,8 @@ for s in "$@"; do
     asm_debug) step asm_debug 300 python tools/asm_debug.py 1 ;;
     tests_all) step pytest_gpu 900 python -m pytest tests -m gpu -q -p no:cacheprovider ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 600 python bench.py ;;
-    bench_short) step bench 600 python bench.py --steps 10 --warmup 3 --cpu-iters 3 ;;
+    bench) step bench 600 python bench.py --full ;;
+    bench_short) step bench 600 python bench.py --full --steps 10 --warmup 3 --cpu-iters 3 ;;
     ops) step op_breakdown 600 python tools/op_breakdown.py ;;
     timeline) step timeline 300 python tools/stream_timeline.py ;;
     timeline_props) step timeline_props 300 python tools/stream_timeline.py --props ;;
