@@ -142,6 +142,15 @@ GEOM_CLOSED_IN_STREAM = 0x1
 GEOM_TOO_LARGE = 0x80000000
 GEOM_MAX_CAP = 1 << 25
 assert C.sizeof(GeomDesc) == 160 and GEOM_INFO_DTYPE.itemsize == 112
+# geometry as WKB (include/covt.h "Geometry as WKB")
+WKB_DESC_DTYPE = np.dtype([("offsets_off", np.int64), ("bytes_off", np.int64), ("byte_cap", np.int64),
+                           ("n_features", np.int32), ("flags", np.int32)])
+WKB_RESULT_DTYPE = np.dtype([("status", np.int32), ("reserved", np.int32), ("n_bytes", np.int64)])
+WKB_INFO_DTYPE = np.dtype([("tile", np.int32), ("layer", np.int32), ("n_features", np.int32),
+                           ("desc_index", np.int32), ("offsets_off", np.int64), ("bytes_off", np.int64),
+                           ("byte_cap", np.int64), ("flags", np.int32), ("reserved", np.int32)])
+WKB_TOO_LARGE = 0x1
+assert WKB_DESC_DTYPE.itemsize == 32 and WKB_RESULT_DTYPE.itemsize == 16 and WKB_INFO_DTYPE.itemsize == 48
 
 class PlanOptions(C.Structure):
     """covt_plan_options (include/covt.h): the plan-layout options.  ``PlanOptions()`` holds the
@@ -196,6 +205,9 @@ EXPORTED_SYMBOLS = (
     "covt_device_plan_assemble", "covt_device_plan_num_property_columns", "covt_device_plan_property_bytes",
     "covt_device_plan_property_descs_device", "covt_device_plan_property_copy", "covt_device_plan_materialize",
     "covt_release_scratch", "covt_scratch_blocks", "covt_device_plan_pool_trim",
+    "covt_plan_wkb_bytes", "covt_plan_wkb_columns", "covt_plan_wkb_descs", "covt_geometry_wkb_device",
+    "covt_plan_wkb_host", "covt_device_plan_wkb_bytes", "covt_device_plan_wkb_descs_device",
+    "covt_device_plan_wkb_copy", "covt_device_plan_wkb",
 )
 
 
@@ -335,6 +347,18 @@ def lib() -> C.CDLL:
     L.covt_device_plan_property_descs_device.restype = vp
     L.covt_device_plan_property_copy.argtypes = [vp, vp, vp]
     L.covt_device_plan_materialize.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.covt_plan_wkb_bytes.argtypes = [vp]
+    L.covt_plan_wkb_bytes.restype = C.c_int64
+    L.covt_plan_wkb_columns.argtypes = [vp, vp]
+    L.covt_plan_wkb_descs.argtypes = [vp, vp]
+    L.covt_geometry_wkb_device.argtypes = [vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp]
+    L.covt_plan_wkb_host.argtypes = [vp, u8p, C.c_uint64, vp, vp]
+    L.covt_device_plan_wkb_bytes.argtypes = [vp]
+    L.covt_device_plan_wkb_bytes.restype = C.c_int64
+    L.covt_device_plan_wkb_descs_device.argtypes = [vp]
+    L.covt_device_plan_wkb_descs_device.restype = vp
+    L.covt_device_plan_wkb_copy.argtypes = [vp, vp, vp]
+    L.covt_device_plan_wkb.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.covt_version.restype = C.c_char_p
     L.covt_device_count.argtypes = [i32p]
     _lib = L
@@ -578,6 +602,13 @@ class Plan:
         if self.num_geometry_columns:
             L.covt_plan_geometry_columns(h, self.geom.ctypes.data)
             L.covt_plan_geometry_descs(h, self.gdescs.ctypes.data)
+        # geometry as WKB (include/covt.h "Geometry as WKB"): one column per geometry column
+        self.wkb_bytes = int(L.covt_plan_wkb_bytes(h))
+        self.wkb = np.zeros(self.num_geometry_columns, dtype=WKB_INFO_DTYPE)
+        self.wdescs = np.zeros(self.num_geometry_columns, dtype=WKB_DESC_DTYPE)
+        if self.num_geometry_columns:
+            L.covt_plan_wkb_columns(h, self.wkb.ctypes.data)
+            L.covt_plan_wkb_descs(h, self.wdescs.ctypes.data)
         # property columns (include/covt.h "Property columns"; plans made with PLAN_PROPERTIES)
         self.num_property_columns = int(L.covt_plan_num_property_columns(h))
         self.property_bytes = int(L.covt_plan_property_bytes(h))
@@ -642,6 +673,22 @@ class Plan:
         _raise(lib().covt_plan_assemble_host(self._h, _ptr(self.blob, C.c_uint8), self.blob.size, asm.ctypes.data,
                                              gres.ctypes.data), "covt_plan_assemble_host")
         return asm[:self.assembly_bytes], gres[:self.num_geometry_columns]
+
+    def wkb_host(self):
+        """H2D + decode + geometry assembly + WKB serialization + D2H (covt_plan_wkb_host).
+        Returns (uint8 WKB buffer, results[num_geometry_columns] in tile order); see wkb_column."""
+        buf = np.zeros(max(self.wkb_bytes, 1), dtype=np.uint8)
+        wres = np.zeros(max(self.num_geometry_columns, 1), dtype=WKB_RESULT_DTYPE)
+        _raise(lib().covt_plan_wkb_host(self._h, _ptr(self.blob, C.c_uint8), self.blob.size, buf.ctypes.data,
+                                        wres.ctypes.data), "covt_plan_wkb_host")
+        return buf[:self.wkb_bytes], wres[:self.num_geometry_columns]
+
+    def wkb_column(self, buf: np.ndarray, wres: np.ndarray, c: int) -> "WkbColumn":
+        """Column c (tile order) of a WKB buffer -> WkbColumn (raises on its status)."""
+        w, r = self.wkb[c], wres[c]
+        _raise(int(r["status"]), "WKB column %d (tile %d, layer %d)" % (c, w["tile"], w["layer"]))
+        o, b = int(w["offsets_off"]), int(w["bytes_off"])
+        return WkbColumn(buf[o:o + 4 * (int(w["n_features"]) + 1)].view(np.int32), buf[b:b + int(r["n_bytes"])])
 
     def properties_host(self):
         """H2D + decode + property materialization + D2H (covt_plan_properties_host).
@@ -792,6 +839,30 @@ class DeviceBatch:
                                                    self.d_gdesc.data_ptr(), self.plan.num_geometry_columns,
                                                    self.d_asm.data_ptr(), self.d_gres.data_ptr(), s.cuda_stream),
                "covt_assemble_geometry_device")
+
+    def wkb(self, stream=None):
+        """Enqueue the WKB serialization of every assembled geometry column (after assemble() on the
+        same stream)."""
+        import torch
+
+        self._asm_buffers()
+        if getattr(self, "d_wkb", None) is None:
+            p = self.plan
+            self.d_wdesc = torch.from_numpy(p.wdescs.view(np.uint8).reshape(-1)).to(self.device) \
+                if p.num_geometry_columns else torch.zeros(32, dtype=torch.uint8, device=self.device)
+            self.d_wkb = torch.empty(max(p.wkb_bytes, 16), dtype=torch.uint8, device=self.device)
+            self.d_wres = torch.zeros(max(p.num_geometry_columns, 1) * 2, dtype=torch.int64, device=self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _raise(lib().covt_geometry_wkb_device(self.d_out.data_ptr(), self.d_gdesc.data_ptr(), self.d_asm.data_ptr(),
+                                              self.d_gres.data_ptr(), self.d_wdesc.data_ptr(),
+                                              self.plan.num_geometry_columns, self.d_wkb.data_ptr(),
+                                              self.d_wres.data_ptr(), s.cuda_stream), "covt_geometry_wkb_device")
+
+    def wkb_results(self):
+        """(WKB bytes, WKB results in tile order) copied to the host (after wkb())."""
+        buf = self.d_wkb.cpu().numpy()[:self.plan.wkb_bytes]
+        r = self.d_wres.cpu().numpy().view(WKB_RESULT_DTYPE)[:self.plan.num_geometry_columns]
+        return buf, r[self.plan.wkb["desc_index"]] if self.plan.num_geometry_columns else r
 
     def _prop_buffers(self):
         import torch
@@ -950,6 +1021,7 @@ class DevicePlan:
             _raise(lib().covt_device_plan_geometry(self._h, s.cuda_stream), "covt_device_plan_geometry")
         self.num_geometry_columns = lib().covt_device_plan_num_geometry_columns(self._h)
         self.assembly_bytes = lib().covt_device_plan_assembly_bytes(self._h)
+        self.wkb_bytes = lib().covt_device_plan_wkb_bytes(self._h)
         return self.num_geometry_columns
 
     def geometry_copy(self):
@@ -977,6 +1049,33 @@ class DevicePlan:
         s = stream if stream is not None else torch.cuda.current_stream(self.device)
         _raise(lib().covt_device_plan_assemble(self._h, d_out.data_ptr(), d_res.data_ptr(), d_asm.data_ptr(),
                                                d_gres.data_ptr(), s.cuda_stream), "covt_device_plan_assemble")
+
+
+    def wkb_copy(self):
+        """(WKB records in tile order, WKB descriptors in launch order) as host arrays (Plan.wkb / Plan.wdescs)."""
+        self.geometry()
+        w = np.zeros(self.num_geometry_columns, dtype=WKB_INFO_DTYPE)
+        d = np.zeros(self.num_geometry_columns, dtype=WKB_DESC_DTYPE)
+        _raise(lib().covt_device_plan_wkb_copy(self._h, w.ctypes.data, d.ctypes.data), "covt_device_plan_wkb_copy")
+        return w, d
+
+    def alloc_wkb(self):
+        """(WKB buffer, WKB results) on the device, sized for this plan's geometry columns."""
+        import torch
+
+        self.geometry()
+        return (torch.empty(max(self.wkb_bytes, 16), dtype=torch.uint8, device=self.device),
+                torch.zeros(max(self.num_geometry_columns, 1) * 2, dtype=torch.int64, device=self.device))
+
+    def wkb(self, d_out, d_res, d_asm, d_gres, d_wkb, d_wres, stream=None):
+        """Enqueue the WKB serialization over this plan's descriptors (after assemble() on the same stream)."""
+        import torch
+
+        self.geometry(stream)
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _raise(lib().covt_device_plan_wkb(self._h, d_out.data_ptr(), d_res.data_ptr(), d_asm.data_ptr(),
+                                          d_gres.data_ptr(), d_wkb.data_ptr(), d_wres.data_ptr(), s.cuda_stream),
+               "covt_device_plan_wkb")
 
 
 class DeviceSubset:
@@ -1062,6 +1161,22 @@ class GeoArrowGeometry:
 
 
 @dataclass
+class WkbColumn:
+    """One geometry column as an Arrow binary column of little-endian ISO WKB values (include/covt.h
+    "Geometry as WKB"): int32 offsets [n + 1] into data; feature i is data[offsets[i]:offsets[i + 1]]."""
+    offsets: np.ndarray
+    data: np.ndarray
+
+    def __len__(self) -> int:
+        return int(self.offsets.size) - 1
+
+    def feature(self, i: int) -> bytes:
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        return bytes(self.data[int(self.offsets[i]):int(self.offsets[i + 1])])
+
+
+@dataclass
 class PropertyColumn:
     """One materialized property (sub)column (include/covt.h "Property columns"): Arrow-style validity
     bitmap (LSB first) + values at feature positions (BOOLEAN: bitmap; INT64: int64; FLOAT: float32;
@@ -1104,6 +1219,7 @@ class LayerColumns:
     num_bits: int = 0
     column_type: int = 0
     properties: Optional[dict] = None
+    wkb: Optional[WkbColumn] = None  # the layer's geometries, one WKB value per feature
 
 
 _GEOM_FIELD = {GEOMETRY_TYPES: "geometryTypes", GEOMETRY_OFFSETS: "geometryOffsets", PART_OFFSETS: "partOffsets",
@@ -1138,6 +1254,13 @@ class CovtParser:
         _raise(int(plan.tile_status[0]), "decodeLayerMetadata")
         out, res = plan.decode_host()
         layers = split_layers(plan, out, res, 0)
+        if plan.num_geometry_columns:
+            wbuf, wres = plan.wkb_host()
+            by_layer = {lc.layer: lc for lc in layers}
+            for c in range(plan.num_geometry_columns):
+                lc = by_layer.get(int(plan.wkb["layer"][c]))
+                if lc is not None and int(wres["status"][c]) == OK:  # (a failed column keeps wkb = None)
+                    lc.wkb = plan.wkb_column(wbuf, wres, c)
         if properties and plan.num_property_columns:
             buf, pres = plan.properties_host()
             by_layer = {lc.layer: lc for lc in layers}
@@ -1158,8 +1281,9 @@ def version() -> str:
 
 # the files whose sha256 (in this order) the Makefile compiles into covt_version() as "src:<16 hex>"
 _BUILD_SOURCES = ("csrc/covt_decode.hip", "csrc/covt_assemble.hip", "csrc/covt_props.hip", "csrc/covt_plan_device.hip",
-                  "csrc/covt_host.cpp", "../include/covt.h", "csrc/covt_internal.h", "csrc/covt_wave.h",
-                  "csrc/covt_walk.h", "csrc/covt_props_plan.h", "csrc/covt_scratch.h")
+                  "csrc/covt_wkb.hip", "csrc/covt_host.cpp", "../include/covt.h", "csrc/covt_internal.h", "csrc/covt_wave.h",
+                  "csrc/covt_walk.h", "csrc/covt_props_plan.h", "csrc/covt_scratch.h", "csrc/covt_coop.h",
+                  "csrc/covt_wkb_plan.h")
 
 
 def source_build_id() -> str:

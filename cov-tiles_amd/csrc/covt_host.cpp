@@ -23,6 +23,7 @@
 #include "covt_internal.h"
 #include "covt_walk.h"
 #include "covt_props_plan.h"
+#include "covt_wkb_plan.h"
 
 namespace {
 
@@ -785,6 +786,9 @@ struct covt_plan {
     std::vector<covt_geom_info> ginfo;   // geometry columns, tile order
     std::vector<covt_geom_desc> gdescs;  // launch order: largest first
     int64_t asm_bytes = 0;
+    std::vector<covt_wkb_info> winfo;    // WKB columns, tile order (one per geometry column)
+    std::vector<covt_wkb_desc> wdescs;   // launch order (that of gdescs)
+    int64_t wkb_bytes = 0;
     std::vector<covt_prop_info> pinfo;   // property (sub)columns, tile order
     std::vector<uint16_t> pflags;        // their COVT_PROP_* flags
     std::vector<covt_prop_desc> pdescs;  // launch order: largest first
@@ -913,6 +917,32 @@ void plan_geometry(covt_plan* p, int32_t nthr) {
             p->gdescs[k] = d;
         }
     });
+}
+
+// WKB columns (include/covt.h "Geometry as WKB"): one per geometry column, slices laid out in tile order
+// next to the assembly layout (covt_wkb_plan.h), descriptors in the geometry descriptors' order.
+void plan_wkb(covt_plan* p) {
+    const size_t nc = p->ginfo.size();
+    p->winfo.resize(nc);
+    p->wdescs.resize(nc);
+    int64_t off = 0;
+    for (size_t c = 0; c < nc; ++c) {
+        const covt_geom_info& g = p->ginfo[c];
+        covt_wkb_desc d{};
+        off = wkb_column_layout(g.n_features, g.part_cap, g.ring_cap, g.coord_cap, (uint32_t)g.flags, off, d);
+        covt_wkb_info w{};
+        w.tile = g.tile;
+        w.layer = g.layer;
+        w.n_features = d.n_features;
+        w.desc_index = g.desc_index;
+        w.offsets_off = d.offsets_off;
+        w.bytes_off = d.bytes_off;
+        w.byte_cap = d.byte_cap;
+        w.flags = d.flags;
+        p->winfo[c] = w;
+        p->wdescs[(size_t)g.desc_index] = d;
+    }
+    p->wkb_bytes = off;
 }
 
 // Property (sub)columns (include/covt.h "Property columns"; CovtParser.decodePropertyColumn
@@ -1627,6 +1657,7 @@ int covt_plan_create_opts(const uint8_t* bytes, const uint64_t* tile_offsets, co
         }
     });
     plan_geometry(p, n_thr);
+    plan_wkb(p);
     plan_property_layout(p);
     *out = p;
     return COVT_OK;
@@ -1922,6 +1953,78 @@ int covt_plan_assemble_host(const covt_plan* p, const uint8_t* bytes, uint64_t n
     if (st == COVT_OK)
         for (size_t k = 0; k < nc; ++k) host_gres[k] = gres[(size_t)p->ginfo[k].desc_index];
     for (void* q : {(void*)d_in, (void*)d_out, (void*)d_asm, (void*)d_desc, (void*)d_res, (void*)d_gdesc, (void*)d_gres})
+        if (q) (void)hipFree(q);
+    (void)hipStreamDestroy(s);
+    return st;
+}
+
+int64_t covt_plan_wkb_bytes(const covt_plan* p) { return p ? p->wkb_bytes : 0; }
+int covt_plan_wkb_columns(const covt_plan* p, covt_wkb_info* out) {
+    if (!p || (!out && !p->winfo.empty())) return COVT_ERR_INVALID_ARG;
+    if (!p->winfo.empty()) std::memcpy(out, p->winfo.data(), p->winfo.size() * sizeof(covt_wkb_info));
+    return COVT_OK;
+}
+int covt_plan_wkb_descs(const covt_plan* p, covt_wkb_desc* out) {
+    if (!p || (!out && !p->wdescs.empty())) return COVT_ERR_INVALID_ARG;
+    if (!p->wdescs.empty()) std::memcpy(out, p->wdescs.data(), p->wdescs.size() * sizeof(covt_wkb_desc));
+    return COVT_OK;
+}
+
+// Whole plan on the current device: tile bytes H2D as they lie, decode, assembly, WKB serialization, the
+// WKB buffer and results back on one stream.
+int covt_plan_wkb_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, uint8_t* host_wkb,
+                       covt_wkb_result* host_wres) {
+    if (!p || (!bytes && n_bytes) || (!host_wkb && p->wkb_bytes) || (!host_wres && !p->winfo.empty()))
+        return COVT_ERR_INVALID_ARG;
+    for (int32_t t = 0; t < p->n_tiles; ++t)
+        if (p->tile_off[(size_t)t] + p->tile_size[(size_t)t] > n_bytes) return COVT_ERR_INVALID_ARG;
+    hipStream_t s;
+    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return COVT_ERR_DEVICE;
+    const size_t nd = p->descs.size(), nc = p->gdescs.size();
+    uint8_t *d_in = nullptr, *d_out = nullptr, *d_asm = nullptr, *d_wkb = nullptr;
+    covt_stream_desc* d_desc = nullptr;
+    covt_stream_result* d_res = nullptr;
+    covt_geom_desc* d_gdesc = nullptr;
+    covt_geom_result* d_gres = nullptr;
+    covt_wkb_desc* d_wdesc = nullptr;
+    covt_wkb_result* d_wres = nullptr;
+    int st = COVT_OK;
+    auto chk = [&](hipError_t e) { if (e != hipSuccess && st == COVT_OK) st = COVT_ERR_DEVICE; };
+    chk(hipMalloc(&d_in, (size_t)n_bytes + COVT_INPUT_PADDING));
+    chk(hipMalloc(&d_out, (size_t)std::max<int64_t>(p->out_bytes, 16)));
+    chk(hipMalloc(&d_asm, (size_t)std::max<int64_t>(p->asm_bytes, 16)));
+    chk(hipMalloc(&d_wkb, (size_t)std::max<int64_t>(p->wkb_bytes, 16)));
+    chk(hipMalloc(&d_desc, std::max<size_t>(nd, 1) * sizeof(covt_stream_desc)));
+    chk(hipMalloc(&d_res, std::max<size_t>(nd, 1) * sizeof(covt_stream_result)));
+    chk(hipMalloc(&d_gdesc, std::max<size_t>(nc, 1) * sizeof(covt_geom_desc)));
+    chk(hipMalloc(&d_gres, std::max<size_t>(nc, 1) * sizeof(covt_geom_result)));
+    chk(hipMalloc(&d_wdesc, std::max<size_t>(nc, 1) * sizeof(covt_wkb_desc)));
+    chk(hipMalloc(&d_wres, std::max<size_t>(nc, 1) * sizeof(covt_wkb_result)));
+    std::vector<covt_wkb_result> wres(nc);
+    if (st == COVT_OK) {
+        if (n_bytes) chk(hipMemcpyAsync(d_in, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, s));
+        chk(hipMemsetAsync(d_in + n_bytes, 0, COVT_INPUT_PADDING, s));
+        if (nd) chk(hipMemcpyAsync(d_desc, p->descs.data(), nd * sizeof(covt_stream_desc), hipMemcpyHostToDevice, s));
+        if (nc) {
+            chk(hipMemcpyAsync(d_gdesc, p->gdescs.data(), nc * sizeof(covt_geom_desc), hipMemcpyHostToDevice, s));
+            chk(hipMemcpyAsync(d_wdesc, p->wdescs.data(), nc * sizeof(covt_wkb_desc), hipMemcpyHostToDevice, s));
+        }
+        if (st == COVT_OK && ((uintptr_t)d_in & 15)) st = COVT_ERR_DEVICE;
+        if (st == COVT_OK) st = launch_grouped(d_in, d_desc, p->fam_counts, d_out, d_res, s);
+        if (st == COVT_OK)
+            st = covt_assemble_geometry_device(d_out, d_res, d_gdesc, (int64_t)nc, d_asm, d_gres, s);
+        if (st == COVT_OK)
+            st = covt_geometry_wkb_device(d_out, d_gdesc, d_asm, d_gres, d_wdesc, (int64_t)nc, d_wkb, d_wres, s);
+        if (st == COVT_OK && p->wkb_bytes)
+            chk(hipMemcpyAsync(host_wkb, d_wkb, (size_t)p->wkb_bytes, hipMemcpyDeviceToHost, s));
+        if (st == COVT_OK && nc)
+            chk(hipMemcpyAsync(wres.data(), d_wres, nc * sizeof(covt_wkb_result), hipMemcpyDeviceToHost, s));
+        chk(hipStreamSynchronize(s));
+    }
+    if (st == COVT_OK)
+        for (size_t k = 0; k < nc; ++k) host_wres[k] = wres[(size_t)p->winfo[k].desc_index];
+    for (void* q : {(void*)d_in, (void*)d_out, (void*)d_asm, (void*)d_wkb, (void*)d_desc, (void*)d_res, (void*)d_gdesc,
+                    (void*)d_gres, (void*)d_wdesc, (void*)d_wres})
         if (q) (void)hipFree(q);
     (void)hipStreamDestroy(s);
     return st;

@@ -32,6 +32,7 @@
 #include "covt_internal.h"
 #include "covt_walk.h"
 #include "covt_props_plan.h"
+#include "covt_wkb_plan.h"
 
 struct covt_device_plan {
     int dev = 0;
@@ -47,6 +48,9 @@ struct covt_device_plan {
     int64_t n_geo = 0, asm_bytes = 0;
     covt_geom_info* d_ginfo = nullptr;
     covt_geom_desc* d_gdesc = nullptr;
+    int64_t wkb_bytes = 0;         // WKB columns (built with the geometry records, in the geometry arena)
+    covt_wkb_info* d_winfo = nullptr;
+    covt_wkb_desc* d_wdesc = nullptr;
     void* prop_arena = nullptr;    // property columns (COVT_PLAN_PROPERTIES): records, infos, descriptors
     void* scratch = nullptr;       // creation-time scratch (the property walk's record slots), freed on the way
     int64_t n_props = 0, prop_bytes = 0;
@@ -2733,6 +2737,35 @@ __global__ void geom_descs(const covt_stream_info* __restrict__ info, covt_geom_
     gdesc[k] = d;
 }
 
+// WKB columns (covt_host.cpp plan_wkb): slices in tile order from the shared layout rule
+// (covt_wkb_plan.h), a record per column and its descriptor at the geometry descriptor's row.
+__global__ void wkb_col_bytes(const covt_geom_info* __restrict__ ginfo, int64_t nc, int64_t* __restrict__ wbytes) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= nc) return;
+    const covt_geom_info& g = ginfo[c];
+    covt_wkb_desc d{};
+    wbytes[c] = wkb_column_layout(g.n_features, g.part_cap, g.ring_cap, g.coord_cap, (uint32_t)g.flags, 0, d);
+}
+__global__ void wkb_records(const covt_geom_info* __restrict__ ginfo, int64_t nc, const int64_t* __restrict__ woff,
+                            covt_wkb_info* __restrict__ winfo, covt_wkb_desc* __restrict__ wdesc) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= nc) return;
+    const covt_geom_info& g = ginfo[c];
+    covt_wkb_desc d{};
+    (void)wkb_column_layout(g.n_features, g.part_cap, g.ring_cap, g.coord_cap, (uint32_t)g.flags, woff[c], d);
+    covt_wkb_info w{};
+    w.tile = g.tile;
+    w.layer = g.layer;
+    w.n_features = d.n_features;
+    w.desc_index = g.desc_index;
+    w.offsets_off = d.offsets_off;
+    w.bytes_off = d.bytes_off;
+    w.byte_cap = d.byte_cap;
+    w.flags = d.flags;
+    winfo[c] = w;
+    wdesc[g.desc_index] = d;
+}
+
 size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 
@@ -3264,7 +3297,9 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     const size_t o_gd = up256(m * sizeof(covt_geom_info)), o_cb = o_gd + up256(m * sizeof(covt_geom_desc)),
                  o_co = o_cb + up256((m + 1) * 8), o_k0 = o_co + up256((m + 1) * 8), o_k1 = o_k0 + up256(m * 8),
                  o_v0 = o_k1 + up256(m * 8), o_v1 = o_v0 + up256(m * 4), o_st = o_v1 + up256(m * 4),
-                 o_cs = o_st + up256(sort_tmp), total = o_cs + up256(cscan_tmp);
+                 o_cs = o_st + up256(sort_tmp), o_wi = o_cs + up256(cscan_tmp),
+                 o_wd = o_wi + up256(m * sizeof(covt_wkb_info)), o_wb = o_wd + up256(m * sizeof(covt_wkb_desc)),
+                 o_wo = o_wb + up256((m + 1) * 8), total = o_wo + up256((m + 1) * 8);
     // the arena is the plan's only on success: a failed build frees it (a retry allocates afresh)
     void* arena = nullptr;
     if (plan_malloc(&arena, total, p->dev, s) != hipSuccess) return COVT_ERR_DEVICE;
@@ -3276,7 +3311,11 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     uint64_t *k0 = (uint64_t*)(g + o_k0), *k1 = (uint64_t*)(g + o_k1);
     uint32_t *v0 = (uint32_t*)(g + o_v0), *v1 = (uint32_t*)(g + o_v1);
     if (hipMemsetAsync(colbytes, 0, (m + 1) * 8, s) != hipSuccess) return COVT_ERR_DEVICE;
-    int64_t asm_bytes = 0;
+    covt_wkb_info* winfo = (covt_wkb_info*)(g + o_wi);
+    covt_wkb_desc* wdesc = (covt_wkb_desc*)(g + o_wd);
+    int64_t *wbytes = (int64_t*)(g + o_wb), *woff = (int64_t*)(g + o_wo);
+    if (hipMemsetAsync(wbytes, 0, (m + 1) * 8, s) != hipSuccess) return COVT_ERR_DEVICE;
+    int64_t asm_bytes = 0, wkb_bytes = 0;
     if (nc > 0) {
         geom_columns<<<(int)((ns + 255) / 256), 256, 0, s>>>(p->d_info, ns, p->format, gst, gpos, p->d_ginfo, colbytes);
         if (hipGetLastError() != hipSuccess) return COVT_ERR_DEVICE;
@@ -3289,6 +3328,14 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
             return COVT_ERR_DEVICE;
         geom_descs<<<cb, 256, 0, s>>>(p->d_info, p->d_ginfo, v1, nc, p->d_gdesc);
         if (hipGetLastError() != hipSuccess) return COVT_ERR_DEVICE;
+        // the WKB layout over the finished records (tile order), descriptors at the geometry descriptors' rows
+        wkb_col_bytes<<<cb, 256, 0, s>>>(p->d_ginfo, nc, wbytes);
+        if (hipGetLastError() != hipSuccess) return COVT_ERR_DEVICE;
+        if (hipcub::DeviceScan::ExclusiveSum(g + o_cs, cscan_tmp, wbytes, woff, (int)(nc + 1), s) != hipSuccess)
+            return COVT_ERR_DEVICE;
+        wkb_records<<<cb, 256, 0, s>>>(p->d_ginfo, nc, woff, winfo, wdesc);
+        if (hipGetLastError() != hipSuccess) return COVT_ERR_DEVICE;
+        if (hipMemcpyAsync(&wkb_bytes, woff + nc, 8, hipMemcpyDeviceToHost, s) != hipSuccess) return COVT_ERR_DEVICE;
         if (hipMemcpyAsync(&asm_bytes, coloff + nc, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
             hipStreamSynchronize(s) != hipSuccess)
             return COVT_ERR_DEVICE;
@@ -3298,6 +3345,9 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     free_arena.q = nullptr;
     p->n_geo = nc;
     p->asm_bytes = asm_bytes;
+    p->wkb_bytes = wkb_bytes;
+    p->d_winfo = winfo;
+    p->d_wdesc = wdesc;
     p->geo_built = true;
     return COVT_OK;
 }
@@ -3335,6 +3385,30 @@ int covt_device_plan_geometry_copy(const covt_device_plan* p, covt_geom_info* in
     if (descs && nc && hipMemcpy(descs, p->d_gdesc, nc * sizeof(covt_geom_desc), hipMemcpyDeviceToHost) != hipSuccess)
         return COVT_ERR_DEVICE;
     return COVT_OK;
+}
+
+int64_t covt_device_plan_wkb_bytes(const covt_device_plan* p) { return p && p->geo_built ? p->wkb_bytes : 0; }
+const covt_wkb_desc* covt_device_plan_wkb_descs_device(const covt_device_plan* p) {
+    return p && p->geo_built ? p->d_wdesc : nullptr;
+}
+int covt_device_plan_wkb_copy(const covt_device_plan* p, covt_wkb_info* infos, covt_wkb_desc* descs) {
+    if (!p || !p->geo_built) return COVT_ERR_INVALID_ARG;
+    const size_t nc = (size_t)p->n_geo;
+    if (infos && nc && hipMemcpy(infos, p->d_winfo, nc * sizeof(covt_wkb_info), hipMemcpyDeviceToHost) != hipSuccess)
+        return COVT_ERR_DEVICE;
+    if (descs && nc && hipMemcpy(descs, p->d_wdesc, nc * sizeof(covt_wkb_desc), hipMemcpyDeviceToHost) != hipSuccess)
+        return COVT_ERR_DEVICE;
+    return COVT_OK;
+}
+int covt_device_plan_wkb(covt_device_plan* p, const uint8_t* d_decoded, const covt_stream_result* d_res,
+                         const uint8_t* d_asm, const covt_geom_result* d_gres, uint8_t* d_wkb,
+                         covt_wkb_result* d_wres, void* hip_stream) {
+    (void)d_res;
+    if (!p) return COVT_ERR_INVALID_ARG;
+    const int st = covt_device_plan_geometry(p, hip_stream);
+    if (st) return st;
+    return covt_geometry_wkb_device(d_decoded, p->d_gdesc, d_asm, d_gres, p->d_wdesc, p->n_geo, d_wkb, d_wres,
+                                    hip_stream);
 }
 
 int covt_device_plan_assemble(covt_device_plan* p, const uint8_t* d_decoded, const covt_stream_result* d_res,

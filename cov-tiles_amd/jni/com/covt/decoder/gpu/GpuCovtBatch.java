@@ -29,6 +29,9 @@ public final class GpuCovtBatch implements AutoCloseable {
      * column_type, n_features, n_data, n_dict, lang, name_len, lang_len, dict_bytes, stream[3],
      * desc_index, name_off, lang_off, out_off[4]); name_off / lang_off index the batch input. */
     public static final int PROPERTY_FIELDS = 22;
+    /** Fields per row of {@link #wkbColumns()}: covt_wkb_info in order (tile, layer, n_features,
+     * desc_index, offsets_off, bytes_off, byte_cap); the offsets index the buffer of {@link #geometryWkb}. */
+    public static final int WKB_FIELDS = 7;
 
     private final ByteBuffer tiles;
     private final int numTiles;
@@ -84,6 +87,21 @@ public final class GpuCovtBatch implements AutoCloseable {
         return properties(live(), tiles, out);
     }
 
+    /** Bytes {@link #geometryWkb} writes. */
+    public long wkbBytes() { return wkbBytes(live()); }
+
+    /** One row of WKB_FIELDS values per geometry column, tile order. */
+    public long[] wkbColumns() { return wkbColumns(live()); }
+
+    /** Decode + geometry assembly + WKB serialization into {@code out} (direct, wkbBytes() long): per
+     * column an int32 offsets array (n_features + 1, little-endian) at offsets_off and the features' ISO
+     * WKB values back to back at bytes_off -- feature i is bytes [offsets[i], offsets[i + 1]), ready for
+     * {@code new WKBReader().read(bytes)}.  Returns (status, n_bytes) per column, tile order. */
+    public long[] geometryWkb(ByteBuffer out) {
+        if (!out.isDirect() || out.capacity() < wkbBytes()) throw new IllegalArgumentException("output buffer");
+        return geometryWkb(live(), tiles, out);
+    }
+
     @Override
     public void close() {
         if (handle != 0) destroy(handle);
@@ -106,4 +124,7 @@ public final class GpuCovtBatch implements AutoCloseable {
     private static native long propertyBytes(long plan);
     private static native long[] propertyColumns(long plan);
     private static native int[] properties(long plan, ByteBuffer tiles, ByteBuffer out);
+    private static native long wkbBytes(long plan);
+    private static native long[] wkbColumns(long plan);
+    private static native long[] geometryWkb(long plan, ByteBuffer tiles, ByteBuffer out);
 }

@@ -258,4 +258,43 @@ JNIEXPORT jintArray JNICALL BFN(properties)(JNIEnv* env, jclass, jlong h, jobjec
     return a;
 }
 
+// Geometry as WKB (include/covt.h "Geometry as WKB"): the third member of CovtParser's Feature, one WKB
+// value per feature for new WKBReader().read(bytes)
+JNIEXPORT jlong JNICALL BFN(wkbBytes)(JNIEnv*, jclass, jlong h) { return covt_plan_wkb_bytes(plan_of(h)); }
+JNIEXPORT jlongArray JNICALL BFN(wkbColumns)(JNIEnv* env, jclass, jlong h) {
+    const int64_t n = covt_plan_num_geometry_columns(plan_of(h));
+    std::vector<covt_wkb_info> info((size_t)n);
+    if (!check(env, covt_plan_wkb_columns(plan_of(h), info.data()))) return nullptr;
+    std::vector<jlong> rows((size_t)n * 7);
+    for (int64_t i = 0; i < n; ++i) {
+        const covt_wkb_info& w = info[(size_t)i];
+        const jlong r[7] = {w.tile, w.layer, w.n_features, w.desc_index, w.offsets_off, w.bytes_off, w.byte_cap};
+        std::copy(r, r + 7, rows.begin() + 7 * i);
+    }
+    jlongArray a = env->NewLongArray((jsize)rows.size());
+    env->SetLongArrayRegion(a, 0, (jsize)rows.size(), rows.data());
+    return a;
+}
+JNIEXPORT jlongArray JNICALL BFN(geometryWkb)(JNIEnv* env, jclass, jlong h, jobject tiles, jobject out) {
+    const int64_t n = covt_plan_num_geometry_columns(plan_of(h));
+    // a heap buffer has no address, a short one would be overrun: IllegalArgumentException either way
+    uint8_t* dst = static_cast<uint8_t*>(env->GetDirectBufferAddress(out));
+    if (!dst || env->GetDirectBufferCapacity(out) < covt_plan_wkb_bytes(plan_of(h))) {
+        check(env, COVT_ERR_INVALID_ARG);
+        return nullptr;
+    }
+    std::vector<covt_wkb_result> res((size_t)n);
+    if (!check(env, covt_plan_wkb_host(plan_of(h), direct(env, tiles), (uint64_t)env->GetDirectBufferCapacity(tiles),
+                                       dst, res.data())))
+        return nullptr;
+    std::vector<jlong> rows((size_t)n * 2);
+    for (int64_t i = 0; i < n; ++i) {
+        rows[(size_t)(2 * i)] = res[(size_t)i].status;
+        rows[(size_t)(2 * i + 1)] = res[(size_t)i].n_bytes;
+    }
+    jlongArray a = env->NewLongArray((jsize)rows.size());
+    env->SetLongArrayRegion(a, 0, (jsize)rows.size(), rows.data());
+    return a;
+}
+
 }  // extern "C"

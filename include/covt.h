@@ -381,6 +381,72 @@ int covt_plan_assemble_host(const covt_plan* plan, const uint8_t* bytes, uint64_
                             covt_geom_result* host_gres);
 
 /* ---------------------------------------------------------------------------
+ * Geometry as WKB: the last step of CovtParser.convertGeometryColumn (CovtParser.java:135-274), whose
+ * result is one JTS Geometry per feature.  Every assembled geometry column of a plan becomes one Arrow
+ * `binary` column holding one little-endian ISO WKB value per feature, which JTS (WKBReader), GeoParquet,
+ * PostGIS, GDAL and shapely read as it is:
+ *
+ *   wkb_offsets[n_features + 1]  int32 byte offsets into the column's own byte slice (first 0, last =
+ *                                the column's byte count, covt_wkb_result.n_bytes)
+ *   wkb_bytes                    the features' WKB values back to back, in feature order
+ *
+ * Byte order 1 (NDR), geometry code = GeometryTypes ordinal + 1 (POINT 1 ... MULTIPOLYGON 6), 2-D, no
+ * SRID; counts uint32, coordinates float64 of the assembled int32 x, y (exact).  The structure is the
+ * assembled column's, format truth as above: polygon rings closed as assembly left them, empty parts and
+ * rings written with count 0, a degenerate ring JTS would reject written as the stream has it.
+ * With G parts, R rings and C coordinates in a feature its value takes
+ *   POINT 21, LINESTRING 9 + 16 C, POLYGON 9 + 4 R + 16 C, MULTIPOINT 9 + 21 G,
+ *   MULTILINESTRING 9 + 9 G + 16 C, MULTIPOLYGON 9 + 9 G + 4 R + 16 C  bytes,
+ * so a column's slice of 9 (n_features + part_cap) + 4 ring_cap + 16 coord_cap bytes always suffices.
+ * The pass runs after covt_assemble_geometry_device on the same stream: a scan of the per-feature sizes,
+ * then every coordinate, ring count, part header and feature header stored at its closed-form address.
+ * Statuses: a column whose assembly result is not COVT_OK gets that status (n_bytes 0, slices untouched);
+ * COVT_GEOM_TOO_LARGE, COVT_WKB_TOO_LARGE or a byte_cap over INT32_MAX -> COVT_ERR_INVALID_ARG; a byte
+ * total over byte_cap -> COVT_ERR_COUNT_MISMATCH (no byte of the byte slice written).
+ * ------------------------------------------------------------------------- */
+#define COVT_WKB_TOO_LARGE 0x1 /* covt_wkb_desc.flags: the column's capacity does not fit int32 offsets */
+
+/* One device-resident WKB column entry (32 bytes), parallel to covt_geom_desc (launch order). */
+typedef struct covt_wkb_desc {
+    int64_t offsets_off; /* byte offset of wkb_offsets in the WKB output buffer (16-byte aligned) */
+    int64_t bytes_off;   /* byte offset of wkb_bytes (16-byte aligned) */
+    int64_t byte_cap;    /* bytes the wkb_bytes slice holds */
+    int32_t n_features, flags;
+} covt_wkb_desc;
+
+/* Per-column WKB result written by the kernel. */
+typedef struct covt_wkb_result {
+    int32_t status, reserved;
+    int64_t n_bytes; /* bytes of WKB written (0 unless status is COVT_OK) */
+} covt_wkb_result;
+
+/* Host-visible WKB column record of a plan, in tile order (48 bytes); column c belongs to geometry
+ * column c (covt_geom_info). */
+typedef struct covt_wkb_info {
+    int32_t tile, layer, n_features, desc_index; /* desc_index: row in the launch-ordered descriptors */
+    int64_t offsets_off, bytes_off, byte_cap;
+    int32_t flags, reserved;
+} covt_wkb_info;
+
+int64_t covt_plan_wkb_bytes(const covt_plan* plan); /* size of the WKB output buffer */
+int covt_plan_wkb_columns(const covt_plan* plan, covt_wkb_info* out); /* tile order, num_geometry_columns */
+int covt_plan_wkb_descs(const covt_plan* plan, covt_wkb_desc* out);   /* launch order (= covt_plan_geometry_descs) */
+
+/* Serialize every assembled geometry column on `hip_stream`, after covt_assemble_geometry_device on the
+ * same stream: d_decoded the decode output (GeometryTypes are read from it at covt_geom_desc.in_off[0]),
+ * d_gdesc / d_asm / d_gres the assembly's descriptors, output and results, d_wdesc the WKB descriptors
+ * (same order), d_wkb an output buffer of covt_plan_wkb_bytes bytes, d_wres n_columns results (same
+ * order).  Asynchronous; needs no scratch, so it can be captured in a HIP graph as it is. */
+int covt_geometry_wkb_device(const uint8_t* d_decoded, const covt_geom_desc* d_gdesc, const uint8_t* d_asm,
+                             const covt_geom_result* d_gres, const covt_wkb_desc* d_wdesc, int64_t n_columns,
+                             uint8_t* d_wkb, covt_wkb_result* d_wres, void* hip_stream);
+
+/* Convenience: H2D + decode + assembly + WKB + D2H of the whole plan on the current device.
+ * host_wkb: covt_plan_wkb_bytes bytes; host_wres: one result per column in tile order. */
+int covt_plan_wkb_host(const covt_plan* plan, const uint8_t* bytes, uint64_t n_bytes, uint8_t* host_wkb,
+                       covt_wkb_result* host_wres);
+
+/* ---------------------------------------------------------------------------
  * Property columns: the GPU replacement for
  * CovtParser.decodePropertyColumn (CovtParser.java:276-354) and getStringDictionary (:367-377).
  * A plan created with COVT_PLAN_PROPERTIES also plans every property column: its present / data /
@@ -555,6 +621,18 @@ int covt_device_plan_geometry_copy(const covt_device_plan* plan, covt_geom_info*
  * result per column in launch order (column c's at its covt_geom_info.desc_index). */
 int covt_device_plan_assemble(covt_device_plan* plan, const uint8_t* d_decoded, const covt_stream_result* d_res,
                               uint8_t* d_asm, covt_geom_result* d_gres, void* hip_stream);
+/* WKB columns from a device plan: the records and descriptors of covt_plan_wkb_columns /
+ * covt_plan_wkb_descs, built on the device together with the geometry records (covt_device_plan_geometry;
+ * the host plan's exactly); 0 / NULL before that call. */
+int64_t covt_device_plan_wkb_bytes(const covt_device_plan* plan);
+const covt_wkb_desc* covt_device_plan_wkb_descs_device(const covt_device_plan* plan);
+int covt_device_plan_wkb_copy(const covt_device_plan* plan, covt_wkb_info* infos, covt_wkb_desc* descs);
+/* covt_geometry_wkb_device over the plan's descriptors, after covt_device_plan_assemble on the same stream:
+ * d_wkb covt_device_plan_wkb_bytes bytes, d_wres one result per column in launch order (column c's at its
+ * covt_wkb_info.desc_index).  d_res is unused (the assembly results carry the source streams' statuses). */
+int covt_device_plan_wkb(covt_device_plan* plan, const uint8_t* d_decoded, const covt_stream_result* d_res,
+                         const uint8_t* d_asm, const covt_geom_result* d_gres, uint8_t* d_wkb,
+                         covt_wkb_result* d_wres, void* hip_stream);
 /* Property columns from a device plan made with COVT_PLAN_PROPERTIES in opts->flags: the records,
  * output layout and largest-first descriptors of covt_plan_property_columns / covt_plan_property_descs,
  * built on the device with the plan (the host plan's exactly); a plan without the flag has none. */
