@@ -2637,7 +2637,7 @@ __device__ __forceinline__ void run_varint_chunk(Ctx& c, int32_t s, int32_t e, i
     if (l == 0 && (has_last || short_end || err)) {
         covt_stream_result r;
         r.status = err ? err : (has_last ? COVT_OK : COVT_ERR_TRUNCATED);
-        r.consumed = pos;
+        r.consumed = r.status ? 0 : pos;  // a failed stream consumed nothing (include/covt.h)
         *r0 = r;
     }
 }
@@ -2709,7 +2709,7 @@ __device__ __forceinline__ void run_fastpfor_chunk(Ctx& c, int32_t v0, int32_t v
     if (lane_id() == 0 && (v1 >= c.n || err)) {  // the last chunk (or an error) sets the stream's result
         covt_stream_result r;
         r.status = err;
-        r.consumed = c.byte_length;
+        r.consumed = err ? 0 : c.byte_length;
         res[kSplitSlots * (t - chunk)] = r;
     }
 }
@@ -2730,9 +2730,20 @@ __device__ __forceinline__ void run_rle_chunk(Ctx& c, const covt_stream_desc* __
     if (c.op == COVT_OP_BYTE_RLE_U8 || c.op == COVT_OP_BYTE_RLE_RAW) run_rle_byte(c, v0, true);
     else run_rle_int(c, v0);
     if (lane_id() == 0) {
-        covt_stream_result* r0 = res + kSplitSlots * (t - chunk);
-        if (c.err) atomicMin(&r0->status, c.err);
-        if (chunk == 0) r0->consumed = (int32_t)cd[3].in_off;
+        // (status, consumed) as one 64-bit word (status in the low half): consumed stays 0 once any chunk
+        // failed, whichever of that chunk and chunk 0 comes first
+        static_assert(sizeof(covt_stream_result) == 8 && offsetof(covt_stream_result, status) == 0, "result word");
+        unsigned long long* w = (unsigned long long*)(res + kSplitSlots * (t - chunk));
+        if (c.err) {
+            unsigned long long old = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), seen;
+            do {
+                seen = old;
+                const int32_t st = (int32_t)(uint32_t)seen;
+                old = atomicCAS(w, seen, (unsigned long long)(uint32_t)(st < c.err ? st : c.err));
+            } while (old != seen);
+        } else if (chunk == 0) {
+            atomicCAS(w, 0ull, (unsigned long long)(uint32_t)cd[3].in_off << 32);
+        }
     }
 }
 
@@ -2910,7 +2921,7 @@ __device__ __forceinline__ void decode_family_wave(uint8_t* smem, const uint8_t*
     if (lane_id() == 0) {
         covt_stream_result r;
         r.status = c.err;
-        r.consumed = c.consumed;
+        r.consumed = c.err ? 0 : c.consumed;  // a failed stream consumed nothing (include/covt.h)
 #ifdef COVT_TIMING
         const uint64_t t_end = __builtin_amdgcn_s_memrealtime();
         r.status = c.err ? -1 : (int32_t)(t_end - t_start);

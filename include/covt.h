@@ -213,10 +213,12 @@ typedef struct covt_stream_desc {
     int32_t byte_length; /* wire byteLength (FastPFOR reads byteLength/4 big-endian words) */
 } covt_stream_desc;
 
-/* Per-stream result written by the kernel. */
+/* Per-stream result written by the kernel.  consumed is 0 whenever status != COVT_OK, on every decode path
+ * (wave-per-stream, lane-per-stream, split chunks): a failed stream's row does not depend on which kernel the
+ * plan gave it to, so a batch and its shards report the same rows. */
 typedef struct covt_stream_result {
     int32_t status;   /* COVT_OK or a negative COVT_ERR_* */
-    int32_t consumed; /* payload bytes consumed (FastPFOR / byte RLE: byteLength) */
+    int32_t consumed; /* payload bytes consumed (FastPFOR / byte RLE: byteLength); 0 unless status is COVT_OK */
 } covt_stream_result;
 
 /* Host-visible stream record of a plan, in tile order. */

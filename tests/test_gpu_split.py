@@ -56,6 +56,7 @@ def test_fixtures_forced_split(covt, gpu_available, golden_streams, chunk, value
             n_split += int(st["desc_index"][i] >= fam0)
             assert (int(res[i][0]) == 0) == (row[ist] == 0), (key, int(i))
             if row[ist] != 0:
+                assert int(res[i][1]) == 0, (key, int(i))  # a failed stream consumed nothing (include/covt.h)
                 continue
             assert int(res[i][1]) == row[ico], (key, int(i))
             assert hashlib.sha256(plan.stream_array(out, int(i)).tobytes()).hexdigest() == row[ish], (key, int(i))
@@ -176,6 +177,7 @@ def test_adversarial_streams_split(covt, oracle, gpu_available, chunk, launch):
                 o_st, o_arr, o_pos = _oracle(oracle, covt, op, buf, nvals, nb)
                 out, r = _split_launch(covt, buf, op, nvals, nb, chunk, ebytes, launch=launch)
                 assert (int(r[0]) == 0) == (o_st == 0), (name, op, n, int(r[0]), o_st)
+                assert o_st == 0 or int(r[1]) == 0, (name, op, n)
                 if o_st == 0:
                     assert int(r[1]) == o_pos, (name, op, n)
                     got = out.view(np.int64 if ebytes == 8 * (2 * nvals if nb else nvals) else np.int32)
@@ -214,8 +216,8 @@ def test_fastpfor_streams_split(covt, oracle, gpu_available, values, launch):
                 ne = 2 * nv if nb else nv
                 out, r = _split_launch(covt, body[:bl], op, nv, nb, values, 4 * ne, fpf=True, launch=launch)
                 assert (int(r[0]) == 0) == (o[0] == 0), (n, op, nv, int(r[0]), o[0])
+                assert int(r[1]) == (bl if o[0] == 0 else 0), (n, op, nv)
                 if o[0] == 0:
-                    assert int(r[1]) == bl
                     assert np.array_equal(out.view(np.int32), np.asarray(o[1], dtype=np.int32)), (n, op, nv)
                 n_checked += 1
     # corrupted payloads: a status (never a fault), equal arrays whenever the oracle decodes
@@ -315,6 +317,7 @@ def test_u64_streams_split(covt, oracle, gpu_available, chunk):
                     assert int(r[1]) == o_pos, (name, op, n)
                     assert np.array_equal(out.view(np.int64), o_arr.view(np.int64)), (name, op, n)
                 else:
+                    assert int(r[1]) == 0, (name, op, n)
                     n_err += 1
                 n_checked += 1
     assert n_checked > 100 and n_err > 10
@@ -455,6 +458,7 @@ def test_rle_streams_split(covt, oracle, gpu_available, unit, launch):
             else:
                 o_st, o_arr, _, o_cons = oracle.decode_rle(buf, n, 0, op == covt.OP_RLE_S64)
             assert (int(r[0]) == 0) == (o_st == 0), (op, n, unit, int(r[0]), o_st)
+            assert o_st == 0 or int(r[1]) == 0, (op, n, unit)  # whichever of the failing chunk and chunk 0 came first
             n_bad += o_st != 0
             if o_st == 0:
                 assert int(r[1]) == o_cons, (op, n, unit)
