@@ -151,6 +151,14 @@ WKB_INFO_DTYPE = np.dtype([("tile", np.int32), ("layer", np.int32), ("n_features
                            ("byte_cap", np.int64), ("flags", np.int32), ("reserved", np.int32)])
 WKB_TOO_LARGE = 0x1
 assert WKB_DESC_DTYPE.itemsize == 32 and WKB_RESULT_DTYPE.itemsize == 16 and WKB_INFO_DTYPE.itemsize == 48
+# geometry bounding boxes (include/covt.h "Geometry bounding boxes")
+BBOX_DESC_DTYPE = np.dtype([("off", np.int64), ("n_features", np.int32), ("flags", np.int32)])
+BBOX_RESULT_DTYPE = np.dtype([("status", np.int32), ("n_empty", np.int32), ("extent", np.float64, (4,))])
+BBOX_INFO_DTYPE = np.dtype([("tile", np.int32), ("layer", np.int32), ("n_features", np.int32),
+                            ("desc_index", np.int32), ("off", np.int64), ("flags", np.int32),
+                            ("reserved", np.int32)])
+BBOX_TOO_LARGE = 0x1
+assert BBOX_DESC_DTYPE.itemsize == 16 and BBOX_RESULT_DTYPE.itemsize == 40 and BBOX_INFO_DTYPE.itemsize == 32
 
 class PlanOptions(C.Structure):
     """covt_plan_options (include/covt.h): the plan-layout options.  ``PlanOptions()`` holds the
@@ -208,6 +216,9 @@ EXPORTED_SYMBOLS = (
     "covt_plan_wkb_bytes", "covt_plan_wkb_columns", "covt_plan_wkb_descs", "covt_geometry_wkb_device",
     "covt_plan_wkb_host", "covt_device_plan_wkb_bytes", "covt_device_plan_wkb_descs_device",
     "covt_device_plan_wkb_copy", "covt_device_plan_wkb",
+    "covt_plan_bbox_bytes", "covt_plan_bbox_columns", "covt_plan_bbox_descs", "covt_geometry_bbox_device",
+    "covt_plan_bbox_host", "covt_device_plan_bbox_bytes", "covt_device_plan_bbox_descs_device",
+    "covt_device_plan_bbox_copy", "covt_device_plan_bbox",
 )
 
 
@@ -359,6 +370,18 @@ def lib() -> C.CDLL:
     L.covt_device_plan_wkb_descs_device.restype = vp
     L.covt_device_plan_wkb_copy.argtypes = [vp, vp, vp]
     L.covt_device_plan_wkb.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.covt_plan_bbox_bytes.argtypes = [vp]
+    L.covt_plan_bbox_bytes.restype = C.c_int64
+    L.covt_plan_bbox_columns.argtypes = [vp, vp]
+    L.covt_plan_bbox_descs.argtypes = [vp, vp]
+    L.covt_geometry_bbox_device.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, vp]
+    L.covt_plan_bbox_host.argtypes = [vp, u8p, C.c_uint64, vp, vp]
+    L.covt_device_plan_bbox_bytes.argtypes = [vp]
+    L.covt_device_plan_bbox_bytes.restype = C.c_int64
+    L.covt_device_plan_bbox_descs_device.argtypes = [vp]
+    L.covt_device_plan_bbox_descs_device.restype = vp
+    L.covt_device_plan_bbox_copy.argtypes = [vp, vp, vp]
+    L.covt_device_plan_bbox.argtypes = [vp, vp, vp, vp, vp, vp]
     L.covt_version.restype = C.c_char_p
     L.covt_device_count.argtypes = [i32p]
     _lib = L
@@ -609,6 +632,13 @@ class Plan:
         if self.num_geometry_columns:
             L.covt_plan_wkb_columns(h, self.wkb.ctypes.data)
             L.covt_plan_wkb_descs(h, self.wdescs.ctypes.data)
+        # geometry bounding boxes (include/covt.h "Geometry bounding boxes"): one column per geometry column
+        self.bbox_bytes = int(L.covt_plan_bbox_bytes(h))
+        self.bbox = np.zeros(self.num_geometry_columns, dtype=BBOX_INFO_DTYPE)
+        self.bdescs = np.zeros(self.num_geometry_columns, dtype=BBOX_DESC_DTYPE)
+        if self.num_geometry_columns:
+            L.covt_plan_bbox_columns(h, self.bbox.ctypes.data)
+            L.covt_plan_bbox_descs(h, self.bdescs.ctypes.data)
         # property columns (include/covt.h "Property columns"; plans made with PLAN_PROPERTIES)
         self.num_property_columns = int(L.covt_plan_num_property_columns(h))
         self.property_bytes = int(L.covt_plan_property_bytes(h))
@@ -689,6 +719,24 @@ class Plan:
         _raise(int(r["status"]), "WKB column %d (tile %d, layer %d)" % (c, w["tile"], w["layer"]))
         o, b = int(w["offsets_off"]), int(w["bytes_off"])
         return WkbColumn(buf[o:o + 4 * (int(w["n_features"]) + 1)].view(np.int32), buf[b:b + int(r["n_bytes"])])
+
+    def bbox_host(self):
+        """H2D + decode + geometry assembly + bounding boxes + D2H (covt_plan_bbox_host).
+        Returns (uint8 bounding-box buffer, results[num_geometry_columns] in tile order); see bbox_column."""
+        buf = np.zeros(max(self.bbox_bytes, 1), dtype=np.uint8)
+        bres = np.zeros(max(self.num_geometry_columns, 1), dtype=BBOX_RESULT_DTYPE)
+        _raise(lib().covt_plan_bbox_host(self._h, _ptr(self.blob, C.c_uint8), self.blob.size, buf.ctypes.data,
+                                         bres.ctypes.data), "covt_plan_bbox_host")
+        return buf[:self.bbox_bytes], bres[:self.num_geometry_columns]
+
+    def bbox_column(self, buf: np.ndarray, bres: np.ndarray, c: int) -> "BboxColumn":
+        """Column c (tile order) of a bounding-box buffer -> BboxColumn (raises on its status)."""
+        b, r = self.bbox[c], bres[c]
+        _raise(int(r["status"]), "bounding-box column %d (tile %d, layer %d)" % (c, b["tile"], b["layer"]))
+        o, n = int(b["off"]), int(b["n_features"])
+        a = buf[o:o + 32 * n].view(np.float64)
+        return BboxColumn(a[:n], a[n:2 * n], a[2 * n:3 * n], a[3 * n:], np.array(r["extent"], dtype=np.float64),
+                          int(r["n_empty"]))
 
     def properties_host(self):
         """H2D + decode + property materialization + D2H (covt_plan_properties_host).
@@ -864,6 +912,30 @@ class DeviceBatch:
         r = self.d_wres.cpu().numpy().view(WKB_RESULT_DTYPE)[:self.plan.num_geometry_columns]
         return buf, r[self.plan.wkb["desc_index"]] if self.plan.num_geometry_columns else r
 
+    def bbox(self, stream=None):
+        """Enqueue the bounding boxes of every assembled geometry column (after assemble() on the same
+        stream)."""
+        import torch
+
+        self._asm_buffers()
+        if getattr(self, "d_bbox", None) is None:
+            p = self.plan
+            self.d_bdesc = torch.from_numpy(p.bdescs.view(np.uint8).reshape(-1)).to(self.device) \
+                if p.num_geometry_columns else torch.zeros(16, dtype=torch.uint8, device=self.device)
+            self.d_bbox = torch.empty(max(p.bbox_bytes, 16), dtype=torch.uint8, device=self.device)
+            self.d_bres = torch.zeros(max(p.num_geometry_columns, 1) * 5, dtype=torch.int64, device=self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _raise(lib().covt_geometry_bbox_device(self.d_gdesc.data_ptr(), self.d_asm.data_ptr(), self.d_gres.data_ptr(),
+                                               self.d_bdesc.data_ptr(), self.plan.num_geometry_columns,
+                                               self.d_bbox.data_ptr(), self.d_bres.data_ptr(), s.cuda_stream),
+               "covt_geometry_bbox_device")
+
+    def bbox_results(self):
+        """(bounding-box bytes, results in tile order) copied to the host (after bbox())."""
+        buf = self.d_bbox.cpu().numpy()[:self.plan.bbox_bytes]
+        r = self.d_bres.cpu().numpy().view(BBOX_RESULT_DTYPE)[:self.plan.num_geometry_columns]
+        return buf, r[self.plan.bbox["desc_index"]] if self.plan.num_geometry_columns else r
+
     def _prop_buffers(self):
         import torch
 
@@ -1022,6 +1094,7 @@ class DevicePlan:
         self.num_geometry_columns = lib().covt_device_plan_num_geometry_columns(self._h)
         self.assembly_bytes = lib().covt_device_plan_assembly_bytes(self._h)
         self.wkb_bytes = lib().covt_device_plan_wkb_bytes(self._h)
+        self.bbox_bytes = lib().covt_device_plan_bbox_bytes(self._h)
         return self.num_geometry_columns
 
     def geometry_copy(self):
@@ -1076,6 +1149,33 @@ class DevicePlan:
         _raise(lib().covt_device_plan_wkb(self._h, d_out.data_ptr(), d_res.data_ptr(), d_asm.data_ptr(),
                                           d_gres.data_ptr(), d_wkb.data_ptr(), d_wres.data_ptr(), s.cuda_stream),
                "covt_device_plan_wkb")
+
+
+    def bbox_copy(self):
+        """(bounding-box records in tile order, descriptors in launch order) as host arrays (Plan.bbox /
+        Plan.bdescs)."""
+        self.geometry()
+        b = np.zeros(self.num_geometry_columns, dtype=BBOX_INFO_DTYPE)
+        d = np.zeros(self.num_geometry_columns, dtype=BBOX_DESC_DTYPE)
+        _raise(lib().covt_device_plan_bbox_copy(self._h, b.ctypes.data, d.ctypes.data), "covt_device_plan_bbox_copy")
+        return b, d
+
+    def alloc_bbox(self):
+        """(bounding-box buffer, results) on the device, sized for this plan's geometry columns."""
+        import torch
+
+        self.geometry()
+        return (torch.empty(max(self.bbox_bytes, 16), dtype=torch.uint8, device=self.device),
+                torch.zeros(max(self.num_geometry_columns, 1) * 5, dtype=torch.int64, device=self.device))
+
+    def bbox(self, d_asm, d_gres, d_bbox, d_bres, stream=None):
+        """Enqueue the bounding boxes over this plan's descriptors (after assemble() on the same stream)."""
+        import torch
+
+        self.geometry(stream)
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        _raise(lib().covt_device_plan_bbox(self._h, d_asm.data_ptr(), d_gres.data_ptr(), d_bbox.data_ptr(),
+                                           d_bres.data_ptr(), s.cuda_stream), "covt_device_plan_bbox")
 
 
 class DeviceSubset:
@@ -1177,6 +1277,26 @@ class WkbColumn:
 
 
 @dataclass
+class BboxColumn:
+    """One geometry column's bounding boxes (include/covt.h "Geometry bounding boxes"), the four arrays of
+    a GeoParquet bbox covering column: float64 views of n values each, NaN in all four for a feature
+    without a coordinate; extent = (xmin, ymin, xmax, ymax) of the column, n_empty its NaN rows."""
+    xmin: np.ndarray
+    ymin: np.ndarray
+    xmax: np.ndarray
+    ymax: np.ndarray
+    extent: np.ndarray
+    n_empty: int = 0
+
+    def __len__(self) -> int:
+        return int(self.xmin.size)
+
+    def as_struct(self) -> np.ndarray:
+        """(n, 4) float64: one (xmin, ymin, xmax, ymax) row per feature."""
+        return np.stack([self.xmin, self.ymin, self.xmax, self.ymax], axis=1)
+
+
+@dataclass
 class PropertyColumn:
     """One materialized property (sub)column (include/covt.h "Property columns"): Arrow-style validity
     bitmap (LSB first) + values at feature positions (BOOLEAN: bitmap; INT64: int64; FLOAT: float32;
@@ -1220,6 +1340,7 @@ class LayerColumns:
     column_type: int = 0
     properties: Optional[dict] = None
     wkb: Optional[WkbColumn] = None  # the layer's geometries, one WKB value per feature
+    bbox: Optional[BboxColumn] = None  # their bounding boxes, the bbox covering column beside wkb
 
 
 _GEOM_FIELD = {GEOMETRY_TYPES: "geometryTypes", GEOMETRY_OFFSETS: "geometryOffsets", PART_OFFSETS: "partOffsets",
@@ -1261,6 +1382,11 @@ class CovtParser:
                 lc = by_layer.get(int(plan.wkb["layer"][c]))
                 if lc is not None and int(wres["status"][c]) == OK:  # (a failed column keeps wkb = None)
                     lc.wkb = plan.wkb_column(wbuf, wres, c)
+            bbuf, bres = plan.bbox_host()
+            for c in range(plan.num_geometry_columns):
+                lc = by_layer.get(int(plan.bbox["layer"][c]))
+                if lc is not None and int(bres["status"][c]) == OK:  # (a failed column keeps bbox = None)
+                    lc.bbox = plan.bbox_column(bbuf, bres, c)
         if properties and plan.num_property_columns:
             buf, pres = plan.properties_host()
             by_layer = {lc.layer: lc for lc in layers}
@@ -1281,9 +1407,9 @@ def version() -> str:
 
 # the files whose sha256 (in this order) the Makefile compiles into covt_version() as "src:<16 hex>"
 _BUILD_SOURCES = ("csrc/covt_decode.hip", "csrc/covt_assemble.hip", "csrc/covt_props.hip", "csrc/covt_plan_device.hip",
-                  "csrc/covt_wkb.hip", "csrc/covt_host.cpp", "../include/covt.h", "csrc/covt_internal.h", "csrc/covt_wave.h",
+                  "csrc/covt_wkb.hip", "csrc/covt_bbox.hip", "csrc/covt_host.cpp", "../include/covt.h", "csrc/covt_internal.h", "csrc/covt_wave.h",
                   "csrc/covt_walk.h", "csrc/covt_props_plan.h", "csrc/covt_scratch.h", "csrc/covt_coop.h",
-                  "csrc/covt_wkb_plan.h")
+                  "csrc/covt_wkb_plan.h", "csrc/covt_bbox_plan.h")
 
 
 def source_build_id() -> str:

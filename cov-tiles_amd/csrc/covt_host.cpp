@@ -24,6 +24,7 @@
 #include "covt_walk.h"
 #include "covt_props_plan.h"
 #include "covt_wkb_plan.h"
+#include "covt_bbox_plan.h"
 
 namespace {
 
@@ -789,6 +790,9 @@ struct covt_plan {
     std::vector<covt_wkb_info> winfo;    // WKB columns, tile order (one per geometry column)
     std::vector<covt_wkb_desc> wdescs;   // launch order (that of gdescs)
     int64_t wkb_bytes = 0;
+    std::vector<covt_bbox_info> binfo;   // bounding-box columns, tile order (one per geometry column)
+    std::vector<covt_bbox_desc> bdescs;  // launch order (that of gdescs)
+    int64_t bbox_bytes = 0;
     std::vector<covt_prop_info> pinfo;   // property (sub)columns, tile order
     std::vector<uint16_t> pflags;        // their COVT_PROP_* flags
     std::vector<covt_prop_desc> pdescs;  // launch order: largest first
@@ -943,6 +947,30 @@ void plan_wkb(covt_plan* p) {
         p->wdescs[(size_t)g.desc_index] = d;
     }
     p->wkb_bytes = off;
+}
+
+// Bounding-box columns (include/covt.h "Geometry bounding boxes"): one per geometry column, slices laid
+// out in tile order in a buffer of their own (covt_bbox_plan.h), descriptors in the geometry descriptors' order.
+void plan_bbox(covt_plan* p) {
+    const size_t nc = p->ginfo.size();
+    p->binfo.resize(nc);
+    p->bdescs.resize(nc);
+    int64_t off = 0;
+    for (size_t c = 0; c < nc; ++c) {
+        const covt_geom_info& g = p->ginfo[c];
+        covt_bbox_desc d{};
+        off = bbox_column_layout(g.n_features, (uint32_t)g.flags, off, d);
+        covt_bbox_info b{};
+        b.tile = g.tile;
+        b.layer = g.layer;
+        b.n_features = d.n_features;
+        b.desc_index = g.desc_index;
+        b.off = d.off;
+        b.flags = d.flags;
+        p->binfo[c] = b;
+        p->bdescs[(size_t)g.desc_index] = d;
+    }
+    p->bbox_bytes = off;
 }
 
 // Property (sub)columns (include/covt.h "Property columns"; CovtParser.decodePropertyColumn
@@ -1658,6 +1686,7 @@ int covt_plan_create_opts(const uint8_t* bytes, const uint64_t* tile_offsets, co
     });
     plan_geometry(p, n_thr);
     plan_wkb(p);
+    plan_bbox(p);
     plan_property_layout(p);
     *out = p;
     return COVT_OK;
@@ -2025,6 +2054,78 @@ int covt_plan_wkb_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_byte
         for (size_t k = 0; k < nc; ++k) host_wres[k] = wres[(size_t)p->winfo[k].desc_index];
     for (void* q : {(void*)d_in, (void*)d_out, (void*)d_asm, (void*)d_wkb, (void*)d_desc, (void*)d_res, (void*)d_gdesc,
                     (void*)d_gres, (void*)d_wdesc, (void*)d_wres})
+        if (q) (void)hipFree(q);
+    (void)hipStreamDestroy(s);
+    return st;
+}
+
+int64_t covt_plan_bbox_bytes(const covt_plan* p) { return p ? p->bbox_bytes : 0; }
+int covt_plan_bbox_columns(const covt_plan* p, covt_bbox_info* out) {
+    if (!p || (!out && !p->binfo.empty())) return COVT_ERR_INVALID_ARG;
+    if (!p->binfo.empty()) std::memcpy(out, p->binfo.data(), p->binfo.size() * sizeof(covt_bbox_info));
+    return COVT_OK;
+}
+int covt_plan_bbox_descs(const covt_plan* p, covt_bbox_desc* out) {
+    if (!p || (!out && !p->bdescs.empty())) return COVT_ERR_INVALID_ARG;
+    if (!p->bdescs.empty()) std::memcpy(out, p->bdescs.data(), p->bdescs.size() * sizeof(covt_bbox_desc));
+    return COVT_OK;
+}
+
+// Whole plan on the current device: tile bytes H2D as they lie, decode, assembly, bounding boxes, the
+// bounding-box buffer and results back on one stream.
+int covt_plan_bbox_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, uint8_t* host_bbox,
+                        covt_bbox_result* host_bres) {
+    if (!p || (!bytes && n_bytes) || (!host_bbox && p->bbox_bytes) || (!host_bres && !p->binfo.empty()))
+        return COVT_ERR_INVALID_ARG;
+    for (int32_t t = 0; t < p->n_tiles; ++t)
+        if (p->tile_off[(size_t)t] + p->tile_size[(size_t)t] > n_bytes) return COVT_ERR_INVALID_ARG;
+    hipStream_t s;
+    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return COVT_ERR_DEVICE;
+    const size_t nd = p->descs.size(), nc = p->gdescs.size();
+    uint8_t *d_in = nullptr, *d_out = nullptr, *d_asm = nullptr, *d_bbox = nullptr;
+    covt_stream_desc* d_desc = nullptr;
+    covt_stream_result* d_res = nullptr;
+    covt_geom_desc* d_gdesc = nullptr;
+    covt_geom_result* d_gres = nullptr;
+    covt_bbox_desc* d_bdesc = nullptr;
+    covt_bbox_result* d_bres = nullptr;
+    int st = COVT_OK;
+    auto chk = [&](hipError_t e) { if (e != hipSuccess && st == COVT_OK) st = COVT_ERR_DEVICE; };
+    chk(hipMalloc(&d_in, (size_t)n_bytes + COVT_INPUT_PADDING));
+    chk(hipMalloc(&d_out, (size_t)std::max<int64_t>(p->out_bytes, 16)));
+    chk(hipMalloc(&d_asm, (size_t)std::max<int64_t>(p->asm_bytes, 16)));
+    chk(hipMalloc(&d_bbox, (size_t)std::max<int64_t>(p->bbox_bytes, 16)));
+    chk(hipMalloc(&d_desc, std::max<size_t>(nd, 1) * sizeof(covt_stream_desc)));
+    chk(hipMalloc(&d_res, std::max<size_t>(nd, 1) * sizeof(covt_stream_result)));
+    chk(hipMalloc(&d_gdesc, std::max<size_t>(nc, 1) * sizeof(covt_geom_desc)));
+    chk(hipMalloc(&d_gres, std::max<size_t>(nc, 1) * sizeof(covt_geom_result)));
+    chk(hipMalloc(&d_bdesc, std::max<size_t>(nc, 1) * sizeof(covt_bbox_desc)));
+    chk(hipMalloc(&d_bres, std::max<size_t>(nc, 1) * sizeof(covt_bbox_result)));
+    std::vector<covt_bbox_result> bres(nc);
+    if (st == COVT_OK) {
+        if (n_bytes) chk(hipMemcpyAsync(d_in, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, s));
+        chk(hipMemsetAsync(d_in + n_bytes, 0, COVT_INPUT_PADDING, s));
+        if (nd) chk(hipMemcpyAsync(d_desc, p->descs.data(), nd * sizeof(covt_stream_desc), hipMemcpyHostToDevice, s));
+        if (nc) {
+            chk(hipMemcpyAsync(d_gdesc, p->gdescs.data(), nc * sizeof(covt_geom_desc), hipMemcpyHostToDevice, s));
+            chk(hipMemcpyAsync(d_bdesc, p->bdescs.data(), nc * sizeof(covt_bbox_desc), hipMemcpyHostToDevice, s));
+        }
+        if (st == COVT_OK && ((uintptr_t)d_in & 15)) st = COVT_ERR_DEVICE;
+        if (st == COVT_OK) st = launch_grouped(d_in, d_desc, p->fam_counts, d_out, d_res, s);
+        if (st == COVT_OK)
+            st = covt_assemble_geometry_device(d_out, d_res, d_gdesc, (int64_t)nc, d_asm, d_gres, s);
+        if (st == COVT_OK)
+            st = covt_geometry_bbox_device(d_gdesc, d_asm, d_gres, d_bdesc, (int64_t)nc, d_bbox, d_bres, s);
+        if (st == COVT_OK && p->bbox_bytes)
+            chk(hipMemcpyAsync(host_bbox, d_bbox, (size_t)p->bbox_bytes, hipMemcpyDeviceToHost, s));
+        if (st == COVT_OK && nc)
+            chk(hipMemcpyAsync(bres.data(), d_bres, nc * sizeof(covt_bbox_result), hipMemcpyDeviceToHost, s));
+        chk(hipStreamSynchronize(s));
+    }
+    if (st == COVT_OK)
+        for (size_t k = 0; k < nc; ++k) host_bres[k] = bres[(size_t)p->binfo[k].desc_index];
+    for (void* q : {(void*)d_in, (void*)d_out, (void*)d_asm, (void*)d_bbox, (void*)d_desc, (void*)d_res, (void*)d_gdesc,
+                    (void*)d_gres, (void*)d_bdesc, (void*)d_bres})
         if (q) (void)hipFree(q);
     (void)hipStreamDestroy(s);
     return st;

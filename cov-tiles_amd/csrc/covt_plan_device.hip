@@ -33,6 +33,7 @@
 #include "covt_walk.h"
 #include "covt_props_plan.h"
 #include "covt_wkb_plan.h"
+#include "covt_bbox_plan.h"
 
 struct covt_device_plan {
     int dev = 0;
@@ -51,6 +52,9 @@ struct covt_device_plan {
     int64_t wkb_bytes = 0;         // WKB columns (built with the geometry records, in the geometry arena)
     covt_wkb_info* d_winfo = nullptr;
     covt_wkb_desc* d_wdesc = nullptr;
+    int64_t bbox_bytes = 0;        // bounding-box columns (likewise)
+    covt_bbox_info* d_binfo = nullptr;
+    covt_bbox_desc* d_bdesc = nullptr;
     void* prop_arena = nullptr;    // property columns (COVT_PLAN_PROPERTIES): records, infos, descriptors
     void* scratch = nullptr;       // creation-time scratch (the property walk's record slots), freed on the way
     int64_t n_props = 0, prop_bytes = 0;
@@ -2766,6 +2770,33 @@ __global__ void wkb_records(const covt_geom_info* __restrict__ ginfo, int64_t nc
     wdesc[g.desc_index] = d;
 }
 
+// Bounding-box columns (covt_host.cpp plan_bbox): slices in tile order from the shared layout rule
+// (covt_bbox_plan.h), a record per column and its descriptor at the geometry descriptor's row.
+__global__ void bbox_col_bytes(const covt_geom_info* __restrict__ ginfo, int64_t nc, int64_t* __restrict__ bbytes) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= nc) return;
+    const covt_geom_info& g = ginfo[c];
+    covt_bbox_desc d{};
+    bbytes[c] = bbox_column_layout(g.n_features, (uint32_t)g.flags, 0, d);
+}
+__global__ void bbox_records(const covt_geom_info* __restrict__ ginfo, int64_t nc, const int64_t* __restrict__ boff,
+                             covt_bbox_info* __restrict__ binfo, covt_bbox_desc* __restrict__ bdesc) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= nc) return;
+    const covt_geom_info& g = ginfo[c];
+    covt_bbox_desc d{};
+    (void)bbox_column_layout(g.n_features, (uint32_t)g.flags, boff[c], d);
+    covt_bbox_info b{};
+    b.tile = g.tile;
+    b.layer = g.layer;
+    b.n_features = d.n_features;
+    b.desc_index = g.desc_index;
+    b.off = d.off;
+    b.flags = d.flags;
+    binfo[c] = b;
+    bdesc[g.desc_index] = d;
+}
+
 size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 
@@ -3299,7 +3330,9 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
                  o_v0 = o_k1 + up256(m * 8), o_v1 = o_v0 + up256(m * 4), o_st = o_v1 + up256(m * 4),
                  o_cs = o_st + up256(sort_tmp), o_wi = o_cs + up256(cscan_tmp),
                  o_wd = o_wi + up256(m * sizeof(covt_wkb_info)), o_wb = o_wd + up256(m * sizeof(covt_wkb_desc)),
-                 o_wo = o_wb + up256((m + 1) * 8), total = o_wo + up256((m + 1) * 8);
+                 o_wo = o_wb + up256((m + 1) * 8), o_bi = o_wo + up256((m + 1) * 8),
+                 o_bd = o_bi + up256(m * sizeof(covt_bbox_info)), o_bb = o_bd + up256(m * sizeof(covt_bbox_desc)),
+                 o_bo = o_bb + up256((m + 1) * 8), total = o_bo + up256((m + 1) * 8);
     // the arena is the plan's only on success: a failed build frees it (a retry allocates afresh)
     void* arena = nullptr;
     if (plan_malloc(&arena, total, p->dev, s) != hipSuccess) return COVT_ERR_DEVICE;
@@ -3315,7 +3348,11 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     covt_wkb_desc* wdesc = (covt_wkb_desc*)(g + o_wd);
     int64_t *wbytes = (int64_t*)(g + o_wb), *woff = (int64_t*)(g + o_wo);
     if (hipMemsetAsync(wbytes, 0, (m + 1) * 8, s) != hipSuccess) return COVT_ERR_DEVICE;
-    int64_t asm_bytes = 0, wkb_bytes = 0;
+    covt_bbox_info* binfo = (covt_bbox_info*)(g + o_bi);
+    covt_bbox_desc* bdesc = (covt_bbox_desc*)(g + o_bd);
+    int64_t *bbytes = (int64_t*)(g + o_bb), *boff = (int64_t*)(g + o_bo);
+    if (hipMemsetAsync(bbytes, 0, (m + 1) * 8, s) != hipSuccess) return COVT_ERR_DEVICE;
+    int64_t asm_bytes = 0, wkb_bytes = 0, bbox_bytes = 0;
     if (nc > 0) {
         geom_columns<<<(int)((ns + 255) / 256), 256, 0, s>>>(p->d_info, ns, p->format, gst, gpos, p->d_ginfo, colbytes);
         if (hipGetLastError() != hipSuccess) return COVT_ERR_DEVICE;
@@ -3336,6 +3373,14 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
         wkb_records<<<cb, 256, 0, s>>>(p->d_ginfo, nc, woff, winfo, wdesc);
         if (hipGetLastError() != hipSuccess) return COVT_ERR_DEVICE;
         if (hipMemcpyAsync(&wkb_bytes, woff + nc, 8, hipMemcpyDeviceToHost, s) != hipSuccess) return COVT_ERR_DEVICE;
+        // the bounding-box layout, the same way
+        bbox_col_bytes<<<cb, 256, 0, s>>>(p->d_ginfo, nc, bbytes);
+        if (hipGetLastError() != hipSuccess) return COVT_ERR_DEVICE;
+        if (hipcub::DeviceScan::ExclusiveSum(g + o_cs, cscan_tmp, bbytes, boff, (int)(nc + 1), s) != hipSuccess)
+            return COVT_ERR_DEVICE;
+        bbox_records<<<cb, 256, 0, s>>>(p->d_ginfo, nc, boff, binfo, bdesc);
+        if (hipGetLastError() != hipSuccess) return COVT_ERR_DEVICE;
+        if (hipMemcpyAsync(&bbox_bytes, boff + nc, 8, hipMemcpyDeviceToHost, s) != hipSuccess) return COVT_ERR_DEVICE;
         if (hipMemcpyAsync(&asm_bytes, coloff + nc, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
             hipStreamSynchronize(s) != hipSuccess)
             return COVT_ERR_DEVICE;
@@ -3348,6 +3393,9 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     p->wkb_bytes = wkb_bytes;
     p->d_winfo = winfo;
     p->d_wdesc = wdesc;
+    p->bbox_bytes = bbox_bytes;
+    p->d_binfo = binfo;
+    p->d_bdesc = bdesc;
     p->geo_built = true;
     return COVT_OK;
 }
@@ -3409,6 +3457,27 @@ int covt_device_plan_wkb(covt_device_plan* p, const uint8_t* d_decoded, const co
     if (st) return st;
     return covt_geometry_wkb_device(d_decoded, p->d_gdesc, d_asm, d_gres, p->d_wdesc, p->n_geo, d_wkb, d_wres,
                                     hip_stream);
+}
+
+int64_t covt_device_plan_bbox_bytes(const covt_device_plan* p) { return p && p->geo_built ? p->bbox_bytes : 0; }
+const covt_bbox_desc* covt_device_plan_bbox_descs_device(const covt_device_plan* p) {
+    return p && p->geo_built ? p->d_bdesc : nullptr;
+}
+int covt_device_plan_bbox_copy(const covt_device_plan* p, covt_bbox_info* infos, covt_bbox_desc* descs) {
+    if (!p || !p->geo_built) return COVT_ERR_INVALID_ARG;
+    const size_t nc = (size_t)p->n_geo;
+    if (infos && nc && hipMemcpy(infos, p->d_binfo, nc * sizeof(covt_bbox_info), hipMemcpyDeviceToHost) != hipSuccess)
+        return COVT_ERR_DEVICE;
+    if (descs && nc && hipMemcpy(descs, p->d_bdesc, nc * sizeof(covt_bbox_desc), hipMemcpyDeviceToHost) != hipSuccess)
+        return COVT_ERR_DEVICE;
+    return COVT_OK;
+}
+int covt_device_plan_bbox(covt_device_plan* p, const uint8_t* d_asm, const covt_geom_result* d_gres, uint8_t* d_bbox,
+                          covt_bbox_result* d_bres, void* hip_stream) {
+    if (!p) return COVT_ERR_INVALID_ARG;
+    const int st = covt_device_plan_geometry(p, hip_stream);
+    if (st) return st;
+    return covt_geometry_bbox_device(p->d_gdesc, d_asm, d_gres, p->d_bdesc, p->n_geo, d_bbox, d_bres, hip_stream);
 }
 
 int covt_device_plan_assemble(covt_device_plan* p, const uint8_t* d_decoded, const covt_stream_result* d_res,

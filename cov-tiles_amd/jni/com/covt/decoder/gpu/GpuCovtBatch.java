@@ -32,6 +32,12 @@ public final class GpuCovtBatch implements AutoCloseable {
     /** Fields per row of {@link #wkbColumns()}: covt_wkb_info in order (tile, layer, n_features,
      * desc_index, offsets_off, bytes_off, byte_cap); the offsets index the buffer of {@link #geometryWkb}. */
     public static final int WKB_FIELDS = 7;
+    /** Fields per row of {@link #bboxColumns()}: covt_bbox_info in order (tile, layer, n_features,
+     * desc_index, off); off indexes the buffer of {@link #geometryBbox}. */
+    public static final int BBOX_FIELDS = 5;
+    /** Fields per row of {@link #geometryBbox}: status, n_empty, then the column's extent xmin, ymin,
+     * xmax, ymax as the bits of their doubles (Double.longBitsToDouble; NaN without a coordinate). */
+    public static final int BBOX_RESULT_FIELDS = 6;
 
     private final ByteBuffer tiles;
     private final int numTiles;
@@ -102,6 +108,21 @@ public final class GpuCovtBatch implements AutoCloseable {
         return geometryWkb(live(), tiles, out);
     }
 
+    /** Bytes {@link #geometryBbox} writes. */
+    public long bboxBytes() { return bboxBytes(live()); }
+
+    /** One row of BBOX_FIELDS values per geometry column, tile order. */
+    public long[] bboxColumns() { return bboxColumns(live()); }
+
+    /** Decode + geometry assembly + bounding boxes into {@code out} (direct, bboxBytes() long): per column,
+     * at off, four little-endian float64 arrays of n_features values back to back -- xmin, ymin, xmax, ymax,
+     * the GeoParquet bbox covering column of the WKB column of {@link #geometryWkb}; a feature without a
+     * coordinate holds NaN in all four.  Returns BBOX_RESULT_FIELDS values per column, tile order. */
+    public long[] geometryBbox(ByteBuffer out) {
+        if (!out.isDirect() || out.capacity() < bboxBytes()) throw new IllegalArgumentException("output buffer");
+        return geometryBbox(live(), tiles, out);
+    }
+
     @Override
     public void close() {
         if (handle != 0) destroy(handle);
@@ -127,4 +148,7 @@ public final class GpuCovtBatch implements AutoCloseable {
     private static native long wkbBytes(long plan);
     private static native long[] wkbColumns(long plan);
     private static native long[] geometryWkb(long plan, ByteBuffer tiles, ByteBuffer out);
+    private static native long bboxBytes(long plan);
+    private static native long[] bboxColumns(long plan);
+    private static native long[] geometryBbox(long plan, ByteBuffer tiles, ByteBuffer out);
 }

@@ -8,6 +8,7 @@
 #include <jni.h>
 
 #include <algorithm>
+#include <cstring>
 #include <vector>
 
 #include "covt.h"
@@ -291,6 +292,47 @@ JNIEXPORT jlongArray JNICALL BFN(geometryWkb)(JNIEnv* env, jclass, jlong h, jobj
     for (int64_t i = 0; i < n; ++i) {
         rows[(size_t)(2 * i)] = res[(size_t)i].status;
         rows[(size_t)(2 * i + 1)] = res[(size_t)i].n_bytes;
+    }
+    jlongArray a = env->NewLongArray((jsize)rows.size());
+    env->SetLongArrayRegion(a, 0, (jsize)rows.size(), rows.data());
+    return a;
+}
+
+// Geometry bounding boxes (include/covt.h "Geometry bounding boxes"): the bbox covering column beside the
+// WKB column, four float64 arrays per geometry column
+JNIEXPORT jlong JNICALL BFN(bboxBytes)(JNIEnv*, jclass, jlong h) { return covt_plan_bbox_bytes(plan_of(h)); }
+JNIEXPORT jlongArray JNICALL BFN(bboxColumns)(JNIEnv* env, jclass, jlong h) {
+    const int64_t n = covt_plan_num_geometry_columns(plan_of(h));
+    std::vector<covt_bbox_info> info((size_t)n);
+    if (!check(env, covt_plan_bbox_columns(plan_of(h), info.data()))) return nullptr;
+    std::vector<jlong> rows((size_t)n * 5);
+    for (int64_t i = 0; i < n; ++i) {
+        const covt_bbox_info& b = info[(size_t)i];
+        const jlong r[5] = {b.tile, b.layer, b.n_features, b.desc_index, b.off};
+        std::copy(r, r + 5, rows.begin() + 5 * i);
+    }
+    jlongArray a = env->NewLongArray((jsize)rows.size());
+    env->SetLongArrayRegion(a, 0, (jsize)rows.size(), rows.data());
+    return a;
+}
+JNIEXPORT jlongArray JNICALL BFN(geometryBbox)(JNIEnv* env, jclass, jlong h, jobject tiles, jobject out) {
+    const int64_t n = covt_plan_num_geometry_columns(plan_of(h));
+    // a heap buffer has no address, a short one would be overrun: IllegalArgumentException either way
+    uint8_t* dst = static_cast<uint8_t*>(env->GetDirectBufferAddress(out));
+    if (!dst || env->GetDirectBufferCapacity(out) < covt_plan_bbox_bytes(plan_of(h))) {
+        check(env, COVT_ERR_INVALID_ARG);
+        return nullptr;
+    }
+    std::vector<covt_bbox_result> res((size_t)n);
+    if (!check(env, covt_plan_bbox_host(plan_of(h), direct(env, tiles), (uint64_t)env->GetDirectBufferCapacity(tiles),
+                                        dst, res.data())))
+        return nullptr;
+    std::vector<jlong> rows((size_t)n * 6);
+    for (int64_t i = 0; i < n; ++i) {
+        rows[(size_t)(6 * i)] = res[(size_t)i].status;
+        rows[(size_t)(6 * i + 1)] = res[(size_t)i].n_empty;
+        // the extent's doubles as their bits (Double.longBitsToDouble on the Java side)
+        std::memcpy(&rows[(size_t)(6 * i + 2)], res[(size_t)i].extent, 32);
     }
     jlongArray a = env->NewLongArray((jsize)rows.size());
     env->SetLongArrayRegion(a, 0, (jsize)rows.size(), rows.data());

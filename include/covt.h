@@ -449,6 +449,65 @@ int covt_plan_wkb_host(const covt_plan* plan, const uint8_t* bytes, uint64_t n_b
                        covt_wkb_result* host_wres);
 
 /* ---------------------------------------------------------------------------
+ * Geometry bounding boxes: the GeoParquet 1.1 bbox covering column of every assembled geometry column,
+ * the companion of its WKB column.  Per column one slice of 32 * n_features bytes (16-byte aligned start):
+ *
+ *   xmin[n_features] | ymin[n_features] | xmax[n_features] | ymax[n_features]     float64, back to back
+ *
+ * the struct-of-arrays layout of an Arrow struct<xmin, ymin, xmax, ymax: double>.  A value is the min / max
+ * of the feature's assembled int32 x or y as float64 (exact), over every coordinate the assembled column
+ * attributes to the feature: coords[ring_offsets[part_offsets[geometry_offsets[f]]] ..
+ * ring_offsets[part_offsets[geometry_offsets[f + 1]]]), the ring-closing vertex included, whatever the
+ * geometry type.  A feature with no coordinate (a MULTI* of 0 parts, a line of 0 vertices, a polygon whose
+ * rings are all empty) gets the quiet NaN 0x7FF8000000000000 in all four arrays, as shapely.bounds reports
+ * an empty geometry.  Coordinates are tile-local, the space of coords and of the WKB values.
+ * Per column a covt_bbox_result: extent = xmin, ymin, xmax, ymax over all the column's coordinates (the
+ * layer's bbox in GeoParquet file metadata, row-group statistics; all NaN without a coordinate), n_empty
+ * the number of NaN rows.
+ * Statuses: a column whose assembly result is not COVT_OK gets that status (n_empty 0, extent NaN, slice
+ * untouched); COVT_GEOM_TOO_LARGE or COVT_BBOX_TOO_LARGE -> COVT_ERR_INVALID_ARG, likewise.
+ * ------------------------------------------------------------------------- */
+#define COVT_BBOX_TOO_LARGE 0x1 /* covt_bbox_desc.flags: assembly refuses the column (COVT_GEOM_TOO_LARGE) */
+
+/* One device-resident bounding-box column entry (16 bytes), parallel to covt_geom_desc (launch order). */
+typedef struct covt_bbox_desc {
+    int64_t off; /* byte offset of the column's slice in the bounding-box output buffer (16-byte aligned) */
+    int32_t n_features, flags;
+} covt_bbox_desc;
+
+/* Per-column bounding-box result written by the kernels (40 bytes). */
+typedef struct covt_bbox_result {
+    int32_t status, n_empty;
+    double extent[4]; /* xmin, ymin, xmax, ymax of the column (NaN: no coordinate, or status not COVT_OK) */
+} covt_bbox_result;
+
+/* Host-visible bounding-box column record of a plan, in tile order (32 bytes); column c belongs to
+ * geometry column c (covt_geom_info). */
+typedef struct covt_bbox_info {
+    int32_t tile, layer, n_features, desc_index; /* desc_index: row in the launch-ordered descriptors */
+    int64_t off;
+    int32_t flags, reserved;
+} covt_bbox_info;
+
+int64_t covt_plan_bbox_bytes(const covt_plan* plan); /* size of the bounding-box output buffer */
+int covt_plan_bbox_columns(const covt_plan* plan, covt_bbox_info* out); /* tile order, num_geometry_columns */
+int covt_plan_bbox_descs(const covt_plan* plan, covt_bbox_desc* out);   /* launch order (= covt_plan_geometry_descs) */
+
+/* Bounding boxes of every assembled geometry column on `hip_stream`, after covt_assemble_geometry_device
+ * on the same stream: d_gdesc / d_asm / d_gres the assembly's descriptors, output and results, d_bdesc the
+ * bounding-box descriptors (same order), d_bbox an output buffer of covt_plan_bbox_bytes bytes, d_bres
+ * n_columns results (same order).  Asynchronous; needs no scratch and writes every output double exactly
+ * once, so it can be captured in a HIP graph as it is and its result does not depend on scheduling. */
+int covt_geometry_bbox_device(const covt_geom_desc* d_gdesc, const uint8_t* d_asm, const covt_geom_result* d_gres,
+                              const covt_bbox_desc* d_bdesc, int64_t n_columns, uint8_t* d_bbox,
+                              covt_bbox_result* d_bres, void* hip_stream);
+
+/* Convenience: H2D + decode + assembly + bounding boxes + D2H of the whole plan on the current device.
+ * host_bbox: covt_plan_bbox_bytes bytes; host_bres: one result per column in tile order. */
+int covt_plan_bbox_host(const covt_plan* plan, const uint8_t* bytes, uint64_t n_bytes, uint8_t* host_bbox,
+                        covt_bbox_result* host_bres);
+
+/* ---------------------------------------------------------------------------
  * Property columns: the GPU replacement for
  * CovtParser.decodePropertyColumn (CovtParser.java:276-354) and getStringDictionary (:367-377).
  * A plan created with COVT_PLAN_PROPERTIES also plans every property column: its present / data /
@@ -635,6 +694,17 @@ int covt_device_plan_wkb_copy(const covt_device_plan* plan, covt_wkb_info* infos
 int covt_device_plan_wkb(covt_device_plan* plan, const uint8_t* d_decoded, const covt_stream_result* d_res,
                          const uint8_t* d_asm, const covt_geom_result* d_gres, uint8_t* d_wkb,
                          covt_wkb_result* d_wres, void* hip_stream);
+/* Bounding-box columns from a device plan: the records and descriptors of covt_plan_bbox_columns /
+ * covt_plan_bbox_descs, built on the device next to the WKB records (covt_device_plan_geometry; the host
+ * plan's exactly); 0 / NULL before that call. */
+int64_t covt_device_plan_bbox_bytes(const covt_device_plan* plan);
+const covt_bbox_desc* covt_device_plan_bbox_descs_device(const covt_device_plan* plan);
+int covt_device_plan_bbox_copy(const covt_device_plan* plan, covt_bbox_info* infos, covt_bbox_desc* descs);
+/* covt_geometry_bbox_device over the plan's descriptors, after covt_device_plan_assemble on the same stream:
+ * d_bbox covt_device_plan_bbox_bytes bytes, d_bres one result per column in launch order (column c's at its
+ * covt_bbox_info.desc_index). */
+int covt_device_plan_bbox(covt_device_plan* plan, const uint8_t* d_asm, const covt_geom_result* d_gres,
+                          uint8_t* d_bbox, covt_bbox_result* d_bres, void* hip_stream);
 /* Property columns from a device plan made with COVT_PLAN_PROPERTIES in opts->flags: the records,
  * output layout and largest-first descriptors of covt_plan_property_columns / covt_plan_property_descs,
  * built on the device with the plan (the host plan's exactly); a plan without the flag has none. */
