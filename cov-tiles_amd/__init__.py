@@ -20,7 +20,7 @@ import ctypes as C
 import os
 import subprocess
 from dataclasses import dataclass
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import numpy as np
 
@@ -187,39 +187,82 @@ STREAM_INFO_DTYPE = np.dtype([(n, np.int32 if t is C.c_int32 else np.int64) for 
 assert STREAM_INFO_DTYPE.itemsize == C.sizeof(StreamInfo)
 assert C.sizeof(StreamDesc) == 32
 
-EXPORTED_SYMBOLS = (
-    "covt_decode_varint", "covt_decode_zigzag_varint", "covt_decode_zigzag_delta_varint",
-    "covt_decode_zigzag_delta_varint_coordinates", "covt_decode_rle", "covt_decode_byte_rle",
-    "covt_decode_fastpfor_zigzag_delta", "covt_decode_fastpfor_delta_coordinates",
-    "covt_decode_delta_varint_morton_codes", "covt_decode_fastpfor_delta_morton_codes",
-    "covt_plan_create", "covt_plan_destroy", "covt_plan_num_streams", "covt_plan_output_bytes",
-    "covt_plan_totals", "covt_plan_streams", "covt_plan_descs", "covt_plan_tile_status",
-    "covt_decode_streams_device", "covt_plan_decode_host", "covt_plan_decode_host_multi", "covt_version",
-    "covt_device_count", "covt_plan_family_counts", "covt_decode_streams_device_grouped",
-    "covt_decode_streams_device_grouped_mode",
-    "covt_plan_num_geometry_columns", "covt_plan_assembly_bytes", "covt_plan_geometry_columns",
-    "covt_plan_geometry_descs", "covt_assemble_geometry_device", "covt_plan_assemble_host",
-    "covt_plan_create_ex", "covt_plan_num_property_columns", "covt_plan_property_bytes",
-    "covt_plan_property_columns", "covt_plan_property_descs", "covt_materialize_properties_device",
-    "covt_plan_properties_host", "covt_decode_byte_rle_reencode", "covt_decode_floats_le", "covt_decode_string",
-    "covt_plan_decode_host_shards", "covt_plan_release_device", "covt_plan_num_descs", "covt_plan_desc_streams",
-    "covt_device_plan_create", "covt_device_plan_destroy", "covt_device_plan_num_streams",
-    "covt_device_plan_output_bytes", "covt_device_plan_totals", "covt_device_plan_family_counts",
-    "covt_device_plan_descs_device", "covt_device_plan_streams_device", "covt_device_plan_tile_status_device",
-    "covt_device_plan_order_device", "covt_device_plan_copy", "covt_device_plan_decode",
-    "covt_plan_options_init", "covt_plan_create_opts", "covt_device_plan_create_opts",
-    "covt_device_plan_num_descs", "covt_device_plan_geometry", "covt_device_plan_num_geometry_columns",
-    "covt_device_plan_assembly_bytes", "covt_device_plan_geometry_descs_device", "covt_device_plan_geometry_copy",
-    "covt_device_plan_assemble", "covt_device_plan_num_property_columns", "covt_device_plan_property_bytes",
-    "covt_device_plan_property_descs_device", "covt_device_plan_property_copy", "covt_device_plan_materialize",
-    "covt_release_scratch", "covt_scratch_blocks", "covt_device_plan_pool_trim",
-    "covt_plan_wkb_bytes", "covt_plan_wkb_columns", "covt_plan_wkb_descs", "covt_geometry_wkb_device",
-    "covt_plan_wkb_host", "covt_device_plan_wkb_bytes", "covt_device_plan_wkb_descs_device",
-    "covt_device_plan_wkb_copy", "covt_device_plan_wkb",
-    "covt_plan_bbox_bytes", "covt_plan_bbox_columns", "covt_plan_bbox_descs", "covt_geometry_bbox_device",
-    "covt_plan_bbox_host", "covt_device_plan_bbox_bytes", "covt_device_plan_bbox_descs_device",
-    "covt_device_plan_bbox_copy", "covt_device_plan_bbox",
-)
+_u8p, _i32p, _i64p, _u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint64)
+_vp, _vpp, _sz = C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t
+_i32, _i64, _u64, _int = C.c_int32, C.c_int64, C.c_uint64, C.c_int
+
+
+def _sig(restype, argtypes, *names):
+    return {n: (restype, argtypes) for n in names}
+
+
+# The binding table: every entry point include/covt.h declares -> (restype, argtypes).  lib() applies it;
+# a new entry point is one row here.  (argtypes None: left unset, ctypes checks nothing.)
+_SIGNATURES = {
+    # DecodingUtils mirror
+    **_sig(_int, [_u8p, _sz, _i32p, _i32, _i32p], "covt_decode_varint", "covt_decode_zigzag_varint",
+           "covt_decode_zigzag_delta_varint", "covt_decode_zigzag_delta_varint_coordinates"),
+    "covt_decode_rle": (_int, [_u8p, _sz, _i32, _i32p, _i32, _i64p]),
+    "covt_decode_byte_rle": (_int, [_u8p, _sz, _i32, _i32p, _i32, _u8p]),
+    **_sig(_int, [_u8p, _sz, _i32, _i32, _i32p, _i32p], "covt_decode_fastpfor_zigzag_delta",
+           "covt_decode_fastpfor_delta_coordinates"),
+    "covt_decode_delta_varint_morton_codes": (_int, [_u8p, _sz, _i32p, _i32, _i32, _i32p]),
+    "covt_decode_fastpfor_delta_morton_codes": (_int, [_u8p, _sz, _i32, _i32, _i32p, _i32, _i32p]),
+    "covt_decode_byte_rle_reencode": (_int, [_u8p, _sz, _i32, _i32p, _u8p]),
+    "covt_decode_floats_le": (_int, [_u8p, _sz, _i32p, _i32, C.POINTER(C.c_float)]),
+    "covt_decode_string": (_int, [_u8p, _sz, _i32p, _i32p, _i32p]),
+    "covt_version": (C.c_char_p, None),
+    "covt_device_count": (_int, [_i32p]),
+    "covt_release_scratch": (_int, [_vp, _int]),
+    "covt_scratch_blocks": (_i64, None),
+    # host plan
+    "covt_plan_create": (_int, [_u8p, _u64p, _u64p, _i32, _i32, _i32, _vpp]),
+    "covt_plan_create_ex": (_int, [_u8p, _u64p, _u64p, _i32, _i32, _i32, C.c_uint32, _vpp]),
+    "covt_plan_create_opts": (_int, [_u8p, _u64p, _u64p, _i32, _i32, _i32, _vp, _vpp]),
+    **_sig(None, [_vp], "covt_plan_options_init", "covt_plan_destroy", "covt_device_plan_destroy"),
+    **_sig(_i64, [_vp], "covt_plan_num_streams", "covt_plan_output_bytes", "covt_plan_num_descs",
+           "covt_plan_num_geometry_columns", "covt_plan_assembly_bytes", "covt_plan_wkb_bytes", "covt_plan_bbox_bytes",
+           "covt_plan_num_property_columns", "covt_plan_property_bytes"),
+    **_sig(_int, [_vp, _i64p, _i64p, _i64p], "covt_plan_totals", "covt_device_plan_totals"),
+    **_sig(_int, [_vp, _vp], "covt_plan_streams", "covt_plan_descs", "covt_plan_geometry_columns",
+           "covt_plan_geometry_descs", "covt_plan_wkb_columns", "covt_plan_wkb_descs", "covt_plan_bbox_columns",
+           "covt_plan_bbox_descs", "covt_plan_property_columns", "covt_plan_property_descs"),
+    **_sig(_int, [_vp, _i64p], "covt_plan_desc_streams", "covt_plan_family_counts", "covt_device_plan_family_counts"),
+    "covt_plan_tile_status": (_int, [_vp, _i32p]),
+    "covt_plan_release_device": (_int, [_vp]),
+    **_sig(_int, [_vp, _u8p, _u64, _vp, _vp], "covt_plan_decode_host", "covt_plan_assemble_host", "covt_plan_wkb_host",
+           "covt_plan_bbox_host", "covt_plan_properties_host"),
+    "covt_plan_decode_host_multi": (_int, [_vp, _u8p, _u64, _i32, _vp, _vp]),
+    "covt_plan_decode_host_shards": (_int, [_vp, _u8p, _u64, _i32, _i32p, _vp, _vp]),
+    # launches over device buffers
+    "covt_decode_streams_device": (_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "covt_decode_streams_device_grouped": (_int, [_vp, _vp, _i64p, _vp, _vp, _vp]),
+    "covt_decode_streams_device_grouped_mode": (_int, [_vp, _vp, _i64p, _vp, _vp, _vp, _i32]),
+    "covt_assemble_geometry_device": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "covt_materialize_properties_device": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "covt_geometry_wkb_device": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "covt_geometry_bbox_device": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    # device plan
+    "covt_device_plan_create": (_int, [_vp, _u64, _vp, _vp, _i32, _i32, _i32, _vp, _vpp]),
+    "covt_device_plan_create_opts": (_int, [_vp, _u64, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vpp]),
+    "covt_device_plan_pool_trim": (_int, [_int, _u64]),
+    **_sig(_i64, [_vp], "covt_device_plan_num_streams", "covt_device_plan_num_descs", "covt_device_plan_output_bytes",
+           "covt_device_plan_num_geometry_columns", "covt_device_plan_assembly_bytes", "covt_device_plan_wkb_bytes",
+           "covt_device_plan_bbox_bytes", "covt_device_plan_num_property_columns", "covt_device_plan_property_bytes"),
+    **_sig(_vp, [_vp], "covt_device_plan_descs_device", "covt_device_plan_streams_device",
+           "covt_device_plan_tile_status_device", "covt_device_plan_order_device",
+           "covt_device_plan_geometry_descs_device", "covt_device_plan_wkb_descs_device",
+           "covt_device_plan_bbox_descs_device", "covt_device_plan_property_descs_device"),
+    "covt_device_plan_copy": (_int, [_vp, _vp, _vp, _i32p]),
+    **_sig(_int, [_vp, _vp, _vp], "covt_device_plan_geometry_copy", "covt_device_plan_wkb_copy",
+           "covt_device_plan_bbox_copy", "covt_device_plan_property_copy"),
+    "covt_device_plan_geometry": (_int, [_vp, _vp]),
+    "covt_device_plan_decode": (_int, [_vp, _vp, _vp, _vp, _vp]),
+    **_sig(_int, [_vp] * 6, "covt_device_plan_assemble", "covt_device_plan_bbox"),
+    "covt_device_plan_materialize": (_int, [_vp] * 7),
+    "covt_device_plan_wkb": (_int, [_vp] * 8),
+}
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 
 def release_scratch(stream=None, all: bool = False, pinned: bool = False) -> int:
@@ -262,128 +305,9 @@ def lib() -> C.CDLL:
     if not os.path.exists(_LIB):
         raise ImportError("libcovt.so is not built (run __graft_entry__.build() or make -C cov-tiles_amd)")
     L = C.CDLL(_LIB)
-    u8p, i32p, i64p, vp = C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_void_p
-    sz = C.c_size_t
-    for name in ("covt_decode_varint", "covt_decode_zigzag_varint", "covt_decode_zigzag_delta_varint",
-                 "covt_decode_zigzag_delta_varint_coordinates"):
-        getattr(L, name).argtypes = [u8p, sz, i32p, C.c_int32, i32p]
-    L.covt_decode_rle.argtypes = [u8p, sz, C.c_int32, i32p, C.c_int32, i64p]
-    L.covt_decode_byte_rle.argtypes = [u8p, sz, C.c_int32, i32p, C.c_int32, u8p]
-    L.covt_decode_fastpfor_zigzag_delta.argtypes = [u8p, sz, C.c_int32, C.c_int32, i32p, i32p]
-    L.covt_decode_fastpfor_delta_coordinates.argtypes = [u8p, sz, C.c_int32, C.c_int32, i32p, i32p]
-    L.covt_decode_delta_varint_morton_codes.argtypes = [u8p, sz, i32p, C.c_int32, C.c_int32, i32p]
-    L.covt_decode_fastpfor_delta_morton_codes.argtypes = [u8p, sz, C.c_int32, C.c_int32, i32p, C.c_int32, i32p]
-    L.covt_plan_create.argtypes = [u8p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int32, C.c_int32,
-                                   C.c_int32, C.POINTER(vp)]
-    L.covt_plan_destroy.argtypes = [vp]
-    L.covt_plan_destroy.restype = None
-    L.covt_plan_num_streams.argtypes = [vp]
-    L.covt_plan_num_streams.restype = C.c_int64
-    L.covt_plan_output_bytes.argtypes = [vp]
-    L.covt_plan_output_bytes.restype = C.c_int64
-    L.covt_plan_totals.argtypes = [vp, i64p, i64p, i64p]
-    L.covt_plan_streams.argtypes = [vp, vp]
-    L.covt_plan_descs.argtypes = [vp, vp]
-    L.covt_plan_num_descs.argtypes = [vp]
-    L.covt_plan_num_descs.restype = C.c_int64
-    L.covt_plan_desc_streams.argtypes = [vp, i64p]
-    L.covt_plan_tile_status.argtypes = [vp, i32p]
-    L.covt_decode_streams_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp]
-    L.covt_decode_streams_device_grouped.argtypes = [vp, vp, i64p, vp, vp, vp]
-    L.covt_decode_streams_device_grouped_mode.argtypes = [vp, vp, i64p, vp, vp, vp, C.c_int32]
-    L.covt_plan_family_counts.argtypes = [vp, i64p]
-    L.covt_plan_decode_host.argtypes = [vp, u8p, C.c_uint64, vp, vp]
-    L.covt_plan_decode_host_multi.argtypes = [vp, u8p, C.c_uint64, C.c_int32, vp, vp]
-    L.covt_plan_decode_host_shards.argtypes = [vp, u8p, C.c_uint64, C.c_int32, i32p, vp, vp]
-    L.covt_plan_release_device.argtypes = [vp]
-    L.covt_decode_byte_rle_reencode.argtypes = [u8p, sz, C.c_int32, i32p, u8p]
-    L.covt_decode_floats_le.argtypes = [u8p, sz, i32p, C.c_int32, C.POINTER(C.c_float)]
-    L.covt_decode_string.argtypes = [u8p, sz, i32p, i32p, i32p]
-    L.covt_plan_num_geometry_columns.argtypes = [vp]
-    L.covt_plan_num_geometry_columns.restype = C.c_int64
-    L.covt_plan_assembly_bytes.argtypes = [vp]
-    L.covt_plan_assembly_bytes.restype = C.c_int64
-    L.covt_plan_geometry_columns.argtypes = [vp, vp]
-    L.covt_plan_geometry_descs.argtypes = [vp, vp]
-    L.covt_assemble_geometry_device.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp]
-    L.covt_release_scratch.argtypes = [vp, C.c_int]
-    L.covt_scratch_blocks.restype = C.c_int64
-    L.covt_device_plan_pool_trim.argtypes = [C.c_int, C.c_uint64]
-    L.covt_plan_assemble_host.argtypes = [vp, u8p, C.c_uint64, vp, vp]
-    L.covt_plan_create_ex.argtypes = [u8p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int32, C.c_int32,
-                                      C.c_int32, C.c_uint32, C.POINTER(vp)]
-    L.covt_plan_options_init.argtypes = [vp]
-    L.covt_plan_options_init.restype = None
-    L.covt_plan_create_opts.argtypes = [u8p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int32, C.c_int32,
-                                        C.c_int32, vp, C.POINTER(vp)]
-    L.covt_device_plan_create_opts.argtypes = [vp, C.c_uint64, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp,
-                                               C.POINTER(vp)]
-    L.covt_plan_num_property_columns.argtypes = [vp]
-    L.covt_plan_num_property_columns.restype = C.c_int64
-    L.covt_plan_property_bytes.argtypes = [vp]
-    L.covt_plan_property_bytes.restype = C.c_int64
-    L.covt_plan_property_columns.argtypes = [vp, vp]
-    L.covt_plan_property_descs.argtypes = [vp, vp]
-    L.covt_materialize_properties_device.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, vp]
-    L.covt_plan_properties_host.argtypes = [vp, u8p, C.c_uint64, vp, vp]
-    L.covt_device_plan_create.argtypes = [vp, C.c_uint64, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp,
-                                          C.POINTER(vp)]
-    L.covt_device_plan_destroy.argtypes = [vp]
-    L.covt_device_plan_destroy.restype = None
-    for name in ("covt_device_plan_num_streams", "covt_device_plan_num_descs", "covt_device_plan_output_bytes"):
-        getattr(L, name).argtypes = [vp]
-        getattr(L, name).restype = C.c_int64
-    L.covt_device_plan_totals.argtypes = [vp, i64p, i64p, i64p]
-    L.covt_device_plan_family_counts.argtypes = [vp, i64p]
-    for name in ("covt_device_plan_descs_device", "covt_device_plan_streams_device",
-                 "covt_device_plan_tile_status_device", "covt_device_plan_order_device"):
-        getattr(L, name).argtypes = [vp]
-        getattr(L, name).restype = vp
-    L.covt_device_plan_copy.argtypes = [vp, vp, vp, i32p]
-    L.covt_device_plan_decode.argtypes = [vp, vp, vp, vp, vp]
-    L.covt_device_plan_geometry.argtypes = [vp, vp]
-    L.covt_device_plan_num_geometry_columns.argtypes = [vp]
-    L.covt_device_plan_num_geometry_columns.restype = C.c_int64
-    L.covt_device_plan_assembly_bytes.argtypes = [vp]
-    L.covt_device_plan_assembly_bytes.restype = C.c_int64
-    L.covt_device_plan_geometry_descs_device.argtypes = [vp]
-    L.covt_device_plan_geometry_descs_device.restype = vp
-    L.covt_device_plan_geometry_copy.argtypes = [vp, vp, vp]
-    L.covt_device_plan_assemble.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.covt_device_plan_num_property_columns.argtypes = [vp]
-    L.covt_device_plan_num_property_columns.restype = C.c_int64
-    L.covt_device_plan_property_bytes.argtypes = [vp]
-    L.covt_device_plan_property_bytes.restype = C.c_int64
-    L.covt_device_plan_property_descs_device.argtypes = [vp]
-    L.covt_device_plan_property_descs_device.restype = vp
-    L.covt_device_plan_property_copy.argtypes = [vp, vp, vp]
-    L.covt_device_plan_materialize.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    L.covt_plan_wkb_bytes.argtypes = [vp]
-    L.covt_plan_wkb_bytes.restype = C.c_int64
-    L.covt_plan_wkb_columns.argtypes = [vp, vp]
-    L.covt_plan_wkb_descs.argtypes = [vp, vp]
-    L.covt_geometry_wkb_device.argtypes = [vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp]
-    L.covt_plan_wkb_host.argtypes = [vp, u8p, C.c_uint64, vp, vp]
-    L.covt_device_plan_wkb_bytes.argtypes = [vp]
-    L.covt_device_plan_wkb_bytes.restype = C.c_int64
-    L.covt_device_plan_wkb_descs_device.argtypes = [vp]
-    L.covt_device_plan_wkb_descs_device.restype = vp
-    L.covt_device_plan_wkb_copy.argtypes = [vp, vp, vp]
-    L.covt_device_plan_wkb.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    L.covt_plan_bbox_bytes.argtypes = [vp]
-    L.covt_plan_bbox_bytes.restype = C.c_int64
-    L.covt_plan_bbox_columns.argtypes = [vp, vp]
-    L.covt_plan_bbox_descs.argtypes = [vp, vp]
-    L.covt_geometry_bbox_device.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, vp]
-    L.covt_plan_bbox_host.argtypes = [vp, u8p, C.c_uint64, vp, vp]
-    L.covt_device_plan_bbox_bytes.argtypes = [vp]
-    L.covt_device_plan_bbox_bytes.restype = C.c_int64
-    L.covt_device_plan_bbox_descs_device.argtypes = [vp]
-    L.covt_device_plan_bbox_descs_device.restype = vp
-    L.covt_device_plan_bbox_copy.argtypes = [vp, vp, vp]
-    L.covt_device_plan_bbox.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.covt_version.restype = C.c_char_p
-    L.covt_device_count.argtypes = [i32p]
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -579,6 +503,60 @@ def pack_tiles(tiles: List[bytes], align: int = 16):
     return blob, offs, sizes
 
 
+class _Product(NamedTuple):
+    """A per-column product of a plan (assembly, WKB, bounding boxes, properties) as the bindings size,
+    allocate and read it back; the first four name attributes Plan and DevicePlan share."""
+    count: str  # number of columns
+    nbytes: str  # bytes of the product's buffer
+    descs: str  # Plan only: descriptors, launch order
+    records: str  # Plan only: records, tile order (their desc_index reorders the results)
+    info_dtype: np.dtype
+    desc_dtype: np.dtype  # (uint8: descriptors kept as bytes)
+    desc_size: int
+    res_dtype: np.dtype
+    res_words: tuple  # a result as torch elements: (dtype name, count)
+    zeroed: bool  # the buffer starts zeroed, not uninitialised
+    needs_geometry: bool  # DevicePlan: sized only after geometry()
+    attrs: tuple  # DeviceBatch attributes: (descriptors, buffer, results)
+
+    def alloc(self, owner, device):
+        """(buffer, results) on the device, sized by `owner` (a Plan or DevicePlan)."""
+        import torch
+
+        return ((torch.zeros if self.zeroed else torch.empty)(max(getattr(owner, self.nbytes), 16), dtype=torch.uint8,
+                                                              device=device),
+                torch.zeros(max(getattr(owner, self.count), 1) * self.res_words[1],
+                            dtype=getattr(torch, self.res_words[0]), device=device))
+
+
+_PRODUCTS = {
+    "geometry": _Product("num_geometry_columns", "assembly_bytes", "gdescs", "geom", GEOM_INFO_DTYPE,
+                         np.dtype(np.uint8), C.sizeof(GeomDesc), GEOM_RESULT_DTYPE, ("int32", 4), False, True,
+                         ("d_gdesc", "d_asm", "d_gres")),
+    "wkb": _Product("num_geometry_columns", "wkb_bytes", "wdescs", "wkb", WKB_INFO_DTYPE, WKB_DESC_DTYPE,
+                    WKB_DESC_DTYPE.itemsize, WKB_RESULT_DTYPE, ("int64", 2), False, True,
+                    ("d_wdesc", "d_wkb", "d_wres")),
+    "bbox": _Product("num_geometry_columns", "bbox_bytes", "bdescs", "bbox", BBOX_INFO_DTYPE, BBOX_DESC_DTYPE,
+                     BBOX_DESC_DTYPE.itemsize, BBOX_RESULT_DTYPE, ("int64", 5), False, True,
+                     ("d_bdesc", "d_bbox", "d_bres")),
+    "property": _Product("num_property_columns", "property_bytes", "pdescs", "props", PROP_INFO_DTYPE, PROP_DESC_DTYPE,
+                         PROP_DESC_DTYPE.itemsize, PROP_RESULT_DTYPE, ("int32", 2), True, False,
+                         ("d_pdesc", "d_props", "d_pres")),
+}
+
+
+def _stream(stream, device) -> int:
+    """The HIP stream handle of `stream`, or of torch's current stream on `device`."""
+    import torch
+
+    return (stream if stream is not None else torch.cuda.current_stream(device)).cuda_stream
+
+
+def _host_results(d_buf, nbytes: int, res: np.ndarray, index: np.ndarray):
+    """(the first nbytes of a device buffer, launch-order results reordered by `index`) on the host."""
+    return d_buf.cpu().numpy()[:nbytes], res[index] if index.size else res
+
+
 class Plan:
     """Host-side container walk of a tile batch -> per-stream descriptors (covt_plan_create)."""
 
@@ -695,23 +673,25 @@ class Plan:
         _raise(st, "covt_plan_decode_host")
         return out[:self.output_bytes], res[:self.num_streams]
 
+    def _product_host(self, kind: str, entry: str):
+        """One whole-plan entry point: (uint8 buffer of the product, its results in tile order)."""
+        q = _PRODUCTS[kind]
+        nbytes, n = getattr(self, q.nbytes), getattr(self, q.count)
+        buf = np.zeros(max(nbytes, 1), dtype=np.uint8)
+        res = np.zeros(max(n, 1), dtype=q.res_dtype)
+        _raise(getattr(lib(), entry)(self._h, _ptr(self.blob, C.c_uint8), self.blob.size, buf.ctypes.data,
+                                     res.ctypes.data), entry)
+        return buf[:nbytes], res[:n]
+
     def assemble_host(self):
         """H2D + decode + geometry assembly + D2H (covt_plan_assemble_host).
         Returns (uint8 assembly buffer, results[num_geometry_columns] in tile order)."""
-        asm = np.zeros(max(self.assembly_bytes, 1), dtype=np.uint8)
-        gres = np.zeros(max(self.num_geometry_columns, 1), dtype=GEOM_RESULT_DTYPE)
-        _raise(lib().covt_plan_assemble_host(self._h, _ptr(self.blob, C.c_uint8), self.blob.size, asm.ctypes.data,
-                                             gres.ctypes.data), "covt_plan_assemble_host")
-        return asm[:self.assembly_bytes], gres[:self.num_geometry_columns]
+        return self._product_host("geometry", "covt_plan_assemble_host")
 
     def wkb_host(self):
         """H2D + decode + geometry assembly + WKB serialization + D2H (covt_plan_wkb_host).
         Returns (uint8 WKB buffer, results[num_geometry_columns] in tile order); see wkb_column."""
-        buf = np.zeros(max(self.wkb_bytes, 1), dtype=np.uint8)
-        wres = np.zeros(max(self.num_geometry_columns, 1), dtype=WKB_RESULT_DTYPE)
-        _raise(lib().covt_plan_wkb_host(self._h, _ptr(self.blob, C.c_uint8), self.blob.size, buf.ctypes.data,
-                                        wres.ctypes.data), "covt_plan_wkb_host")
-        return buf[:self.wkb_bytes], wres[:self.num_geometry_columns]
+        return self._product_host("wkb", "covt_plan_wkb_host")
 
     def wkb_column(self, buf: np.ndarray, wres: np.ndarray, c: int) -> "WkbColumn":
         """Column c (tile order) of a WKB buffer -> WkbColumn (raises on its status)."""
@@ -723,11 +703,7 @@ class Plan:
     def bbox_host(self):
         """H2D + decode + geometry assembly + bounding boxes + D2H (covt_plan_bbox_host).
         Returns (uint8 bounding-box buffer, results[num_geometry_columns] in tile order); see bbox_column."""
-        buf = np.zeros(max(self.bbox_bytes, 1), dtype=np.uint8)
-        bres = np.zeros(max(self.num_geometry_columns, 1), dtype=BBOX_RESULT_DTYPE)
-        _raise(lib().covt_plan_bbox_host(self._h, _ptr(self.blob, C.c_uint8), self.blob.size, buf.ctypes.data,
-                                         bres.ctypes.data), "covt_plan_bbox_host")
-        return buf[:self.bbox_bytes], bres[:self.num_geometry_columns]
+        return self._product_host("bbox", "covt_plan_bbox_host")
 
     def bbox_column(self, buf: np.ndarray, bres: np.ndarray, c: int) -> "BboxColumn":
         """Column c (tile order) of a bounding-box buffer -> BboxColumn (raises on its status)."""
@@ -741,11 +717,7 @@ class Plan:
     def properties_host(self):
         """H2D + decode + property materialization + D2H (covt_plan_properties_host).
         Returns (uint8 property buffer, results[num_property_columns] in tile order)."""
-        buf = np.zeros(max(self.property_bytes, 1), dtype=np.uint8)
-        pres = np.zeros(max(self.num_property_columns, 1), dtype=PROP_RESULT_DTYPE)
-        _raise(lib().covt_plan_properties_host(self._h, _ptr(self.blob, C.c_uint8), self.blob.size,
-                                               buf.ctypes.data, pres.ctypes.data), "covt_plan_properties_host")
-        return buf[:self.property_bytes], pres[:self.num_property_columns]
+        return self._product_host("property", "covt_plan_properties_host")
 
     def property_name(self, c: int) -> str:
         """Column name of property (sub)column c, plus ':<lang>' for a localized language stream."""
@@ -852,13 +824,10 @@ class DeviceBatch:
     def decode(self, stream=None, launch: int = 0):
         """launch: LAUNCH_AUTO (0), LAUNCH_FUSED or LAUNCH_FORKED, optionally | LAUNCH_FPF_STREAM or LAUNCH_FPF_CLASSIC
         (covt_decode_streams_device_grouped_mode)."""
-        import torch
-
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
         st = lib().covt_decode_streams_device_grouped_mode(self.d_in.data_ptr(), self.d_desc.data_ptr(),
                                                            _ptr(self.plan.family_counts, C.c_int64),
-                                                           self.d_out.data_ptr(), self.d_res.data_ptr(), s.cuda_stream,
-                                                           launch)
+                                                           self.d_out.data_ptr(), self.d_res.data_ptr(),
+                                                           _stream(stream, self.device), launch)
         _raise(st, "covt_decode_streams_device_grouped_mode")
 
     def subset(self, mask) -> "DeviceSubset":
@@ -866,118 +835,86 @@ class DeviceBatch:
         device input and output buffers."""
         return DeviceSubset(self, mask)
 
-
-    def _asm_buffers(self):
+    def _buffers(self, kind: str):
+        """The device descriptors, buffer and results of a product (the attributes _PRODUCTS names), made once."""
         import torch
 
-        if getattr(self, "d_asm", None) is None:
-            p = self.plan
-            self.d_gdesc = torch.from_numpy(p.gdescs).to(self.device) if p.num_geometry_columns else \
-                torch.zeros(C.sizeof(GeomDesc), dtype=torch.uint8, device=self.device)
-            self.d_asm = torch.empty(max(p.assembly_bytes, 16), dtype=torch.uint8, device=self.device)
-            self.d_gres = torch.zeros(max(p.num_geometry_columns, 1) * 4, dtype=torch.int32, device=self.device)
+        q = _PRODUCTS[kind]
+        if getattr(self, q.attrs[1], None) is None:
+            descs = getattr(self.plan, q.descs).view(np.uint8).reshape(-1)
+            d_desc = torch.from_numpy(descs).to(self.device) if getattr(self.plan, q.count) else \
+                torch.zeros(q.desc_size, dtype=torch.uint8, device=self.device)
+            for name, t in zip(q.attrs, (d_desc,) + q.alloc(self.plan, self.device)):
+                setattr(self, name, t)
+
+    def _results(self, kind: str):
+        q = _PRODUCTS[kind]
+        n = getattr(self.plan, q.count)
+        return _host_results(getattr(self, q.attrs[1]), getattr(self.plan, q.nbytes),
+                             getattr(self, q.attrs[2]).cpu().numpy().view(q.res_dtype)[:n],
+                             getattr(self.plan, q.records)["desc_index"])
 
     def assemble(self, stream=None):
         """Enqueue the geometry assembly (after decode() on the same stream)."""
-        import torch
-
-        self._asm_buffers()
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        self._buffers("geometry")
         _raise(lib().covt_assemble_geometry_device(self.d_out.data_ptr(), self.d_res.data_ptr(),
                                                    self.d_gdesc.data_ptr(), self.plan.num_geometry_columns,
-                                                   self.d_asm.data_ptr(), self.d_gres.data_ptr(), s.cuda_stream),
-               "covt_assemble_geometry_device")
+                                                   self.d_asm.data_ptr(), self.d_gres.data_ptr(),
+                                                   _stream(stream, self.device)), "covt_assemble_geometry_device")
 
     def wkb(self, stream=None):
         """Enqueue the WKB serialization of every assembled geometry column (after assemble() on the
         same stream)."""
-        import torch
-
-        self._asm_buffers()
-        if getattr(self, "d_wkb", None) is None:
-            p = self.plan
-            self.d_wdesc = torch.from_numpy(p.wdescs.view(np.uint8).reshape(-1)).to(self.device) \
-                if p.num_geometry_columns else torch.zeros(32, dtype=torch.uint8, device=self.device)
-            self.d_wkb = torch.empty(max(p.wkb_bytes, 16), dtype=torch.uint8, device=self.device)
-            self.d_wres = torch.zeros(max(p.num_geometry_columns, 1) * 2, dtype=torch.int64, device=self.device)
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        self._buffers("geometry")
+        self._buffers("wkb")
         _raise(lib().covt_geometry_wkb_device(self.d_out.data_ptr(), self.d_gdesc.data_ptr(), self.d_asm.data_ptr(),
                                               self.d_gres.data_ptr(), self.d_wdesc.data_ptr(),
                                               self.plan.num_geometry_columns, self.d_wkb.data_ptr(),
-                                              self.d_wres.data_ptr(), s.cuda_stream), "covt_geometry_wkb_device")
+                                              self.d_wres.data_ptr(), _stream(stream, self.device)),
+               "covt_geometry_wkb_device")
 
     def wkb_results(self):
         """(WKB bytes, WKB results in tile order) copied to the host (after wkb())."""
-        buf = self.d_wkb.cpu().numpy()[:self.plan.wkb_bytes]
-        r = self.d_wres.cpu().numpy().view(WKB_RESULT_DTYPE)[:self.plan.num_geometry_columns]
-        return buf, r[self.plan.wkb["desc_index"]] if self.plan.num_geometry_columns else r
+        return self._results("wkb")
 
     def bbox(self, stream=None):
         """Enqueue the bounding boxes of every assembled geometry column (after assemble() on the same
         stream)."""
-        import torch
-
-        self._asm_buffers()
-        if getattr(self, "d_bbox", None) is None:
-            p = self.plan
-            self.d_bdesc = torch.from_numpy(p.bdescs.view(np.uint8).reshape(-1)).to(self.device) \
-                if p.num_geometry_columns else torch.zeros(16, dtype=torch.uint8, device=self.device)
-            self.d_bbox = torch.empty(max(p.bbox_bytes, 16), dtype=torch.uint8, device=self.device)
-            self.d_bres = torch.zeros(max(p.num_geometry_columns, 1) * 5, dtype=torch.int64, device=self.device)
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        self._buffers("geometry")
+        self._buffers("bbox")
         _raise(lib().covt_geometry_bbox_device(self.d_gdesc.data_ptr(), self.d_asm.data_ptr(), self.d_gres.data_ptr(),
                                                self.d_bdesc.data_ptr(), self.plan.num_geometry_columns,
-                                               self.d_bbox.data_ptr(), self.d_bres.data_ptr(), s.cuda_stream),
-               "covt_geometry_bbox_device")
+                                               self.d_bbox.data_ptr(), self.d_bres.data_ptr(),
+                                               _stream(stream, self.device)), "covt_geometry_bbox_device")
 
     def bbox_results(self):
         """(bounding-box bytes, results in tile order) copied to the host (after bbox())."""
-        buf = self.d_bbox.cpu().numpy()[:self.plan.bbox_bytes]
-        r = self.d_bres.cpu().numpy().view(BBOX_RESULT_DTYPE)[:self.plan.num_geometry_columns]
-        return buf, r[self.plan.bbox["desc_index"]] if self.plan.num_geometry_columns else r
-
-    def _prop_buffers(self):
-        import torch
-
-        if getattr(self, "d_props", None) is None:
-            p = self.plan
-            self.d_pdesc = torch.from_numpy(p.pdescs.view(np.uint8).reshape(-1)).to(self.device) \
-                if p.num_property_columns else torch.zeros(PROP_DESC_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
-            self.d_props = torch.zeros(max(p.property_bytes, 16), dtype=torch.uint8, device=self.device)
-            self.d_pres = torch.zeros(max(p.num_property_columns, 1) * 2, dtype=torch.int32, device=self.device)
+        return self._results("bbox")
 
     def materialize_properties(self, stream=None):
         """Enqueue the property-column materialization (after decode() on the same stream)."""
-        import torch
-
-        self._prop_buffers()
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        self._buffers("property")
         _raise(lib().covt_materialize_properties_device(self.d_in.data_ptr(), self.d_out.data_ptr(),
                                                         self.d_res.data_ptr(), self.d_pdesc.data_ptr(),
                                                         self.plan.num_property_columns, self.d_props.data_ptr(),
-                                                        self.d_pres.data_ptr(), s.cuda_stream),
+                                                        self.d_pres.data_ptr(), _stream(stream, self.device)),
                "covt_materialize_properties_device")
 
     def property_results(self):
         """(property bytes, results in tile order) copied to the host."""
-        self._prop_buffers()
-        buf = self.d_props.cpu().numpy()[:self.plan.property_bytes]
-        r = self.d_pres.cpu().numpy().view(PROP_RESULT_DTYPE)[:self.plan.num_property_columns]
-        return buf, r[self.plan.props["desc_index"]] if self.plan.num_property_columns else r
+        self._buffers("property")
+        return self._results("property")
 
     def assembly_results(self):
         """(assembly bytes, geometry results in tile order) copied to the host."""
-        self._asm_buffers()
-        asm = self.d_asm.cpu().numpy()[:self.plan.assembly_bytes]
-        g = self.d_gres.cpu().numpy().view(GEOM_RESULT_DTYPE)[:self.plan.num_geometry_columns]
-        return asm, g[self.plan.geom["desc_index"]] if self.plan.num_geometry_columns else g
+        self._buffers("geometry")
+        return self._results("geometry")
 
     def results(self):
         """(output bytes, results in plan order) copied to the host."""
-        out = self.d_out.cpu().numpy()[:self.plan.output_bytes]
-        res_launch = self.d_res.cpu().numpy().reshape(-1, 2)[:self.plan.num_descs]
-        res = res_launch[self.plan.streams["desc_index"]] if self.plan.num_streams else res_launch
-        return out, res
+        return _host_results(self.d_out, self.plan.output_bytes,
+                             self.d_res.cpu().numpy().reshape(-1, 2)[:self.plan.num_descs],
+                             self.plan.streams["desc_index"])
 
 
 class DevicePlan:
@@ -1002,13 +939,13 @@ class DevicePlan:
         if self.d_off.numel() != self.d_size.numel():
             raise IllegalArgumentException("offsets and sizes differ in length")
         self.n_tiles = int(self.d_off.numel())
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
         h = C.c_void_p()
         with torch.cuda.device(self.device):
             _raise(lib().covt_device_plan_create_opts(d_blob.data_ptr(), d_blob.numel(), self.d_off.data_ptr(),
                                                       self.d_size.data_ptr(), self.n_tiles, fmt, id_mode,
                                                       C.byref(options) if options is not None else None,
-                                                      s.cuda_stream, C.byref(h)), "covt_device_plan_create")
+                                                      _stream(stream, self.device), C.byref(h)),
+                   "covt_device_plan_create")
         self._h = h
         L = lib()
         self.num_streams = L.covt_device_plan_num_streams(h)
@@ -1042,30 +979,36 @@ class DevicePlan:
                "covt_device_plan_copy")
         return info, descs, st[:self.n_tiles]
 
+    def _copy(self, kind: str, entry: str):
+        """(a product's records in tile order, its descriptors in launch order) as host arrays."""
+        q = _PRODUCTS[kind]
+        if q.needs_geometry:
+            self.geometry()
+        n = getattr(self, q.count)
+        info = np.zeros(n, dtype=q.info_dtype)
+        descs = np.zeros(n * q.desc_size, dtype=np.uint8).view(q.desc_dtype)
+        _raise(getattr(lib(), entry)(self._h, info.ctypes.data, descs.ctypes.data), entry)
+        return info, descs
+
+    def _alloc(self, kind: str):
+        q = _PRODUCTS[kind]
+        if q.needs_geometry:
+            self.geometry()
+        return q.alloc(self, self.device)
+
     def property_copy(self):
         """(property records in tile order, property descriptors in materialization order) as host arrays
         (plans made with PLAN_PROPERTIES in the options' flags; Plan.props / Plan.pdescs of the host plan)."""
-        n = self.num_property_columns
-        pinfo = np.zeros(n, dtype=PROP_INFO_DTYPE)
-        pdesc = np.zeros(n, dtype=PROP_DESC_DTYPE)
-        _raise(lib().covt_device_plan_property_copy(self._h, pinfo.ctypes.data, pdesc.ctypes.data),
-               "covt_device_plan_property_copy")
-        return pinfo, pdesc
+        return self._copy("property", "covt_device_plan_property_copy")
 
     def alloc_properties(self):
         """(property buffer, property results) on the device, sized for this plan's property columns."""
-        import torch
-
-        return (torch.zeros(max(self.property_bytes, 16), dtype=torch.uint8, device=self.device),
-                torch.zeros(max(self.num_property_columns, 1) * 2, dtype=torch.int32, device=self.device))
+        return self._alloc("property")
 
     def materialize(self, d_out, d_res, d_props, d_pres, stream=None):
         """Enqueue the property materialization over this plan's property descriptors (after decode())."""
-        import torch
-
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
         _raise(lib().covt_device_plan_materialize(self._h, self.d_in.data_ptr(), d_out.data_ptr(), d_res.data_ptr(),
-                                                  d_props.data_ptr(), d_pres.data_ptr(), s.cuda_stream),
+                                                  d_props.data_ptr(), d_pres.data_ptr(), _stream(stream, self.device)),
                "covt_device_plan_materialize")
 
     def alloc(self):
@@ -1077,20 +1020,16 @@ class DevicePlan:
 
     def decode(self, d_out, d_res, stream=None):
         """Enqueue the grouped decode launch over this plan's descriptors."""
-        import torch
-
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
         _raise(lib().covt_device_plan_decode(self._h, self.d_in.data_ptr(), d_out.data_ptr(), d_res.data_ptr(),
-                                             s.cuda_stream), "covt_device_plan_decode")
+                                             _stream(stream, self.device)), "covt_device_plan_decode")
 
     def geometry(self, stream=None):
         """Build the geometry-column records and descriptors on the device (once; synchronises the
         stream): Plan.geom / Plan.gdescs / Plan.assembly_bytes without the host plan."""
         import torch
 
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device):
-            _raise(lib().covt_device_plan_geometry(self._h, s.cuda_stream), "covt_device_plan_geometry")
+            _raise(lib().covt_device_plan_geometry(self._h, _stream(stream, self.device)), "covt_device_plan_geometry")
         self.num_geometry_columns = lib().covt_device_plan_num_geometry_columns(self._h)
         self.assembly_bytes = lib().covt_device_plan_assembly_bytes(self._h)
         self.wkb_bytes = lib().covt_device_plan_wkb_bytes(self._h)
@@ -1099,83 +1038,48 @@ class DevicePlan:
 
     def geometry_copy(self):
         """(geometry records in tile order, geometry descriptors in launch order) as host arrays."""
-        self.geometry()
-        g = np.zeros(self.num_geometry_columns, dtype=GEOM_INFO_DTYPE)
-        d = np.zeros(self.num_geometry_columns * C.sizeof(GeomDesc), dtype=np.uint8)
-        _raise(lib().covt_device_plan_geometry_copy(self._h, g.ctypes.data, d.ctypes.data),
-               "covt_device_plan_geometry_copy")
-        return g, d
+        return self._copy("geometry", "covt_device_plan_geometry_copy")
 
     def alloc_assembly(self):
         """(assembly buffer, geometry results) on the device, sized for this plan's geometry columns."""
-        import torch
-
-        self.geometry()
-        return (torch.empty(max(self.assembly_bytes, 16), dtype=torch.uint8, device=self.device),
-                torch.zeros(max(self.num_geometry_columns, 1) * 4, dtype=torch.int32, device=self.device))
+        return self._alloc("geometry")
 
     def assemble(self, d_out, d_res, d_asm, d_gres, stream=None):
         """Enqueue the geometry assembly over this plan's geometry descriptors (after decode())."""
-        import torch
-
         self.geometry(stream)
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
         _raise(lib().covt_device_plan_assemble(self._h, d_out.data_ptr(), d_res.data_ptr(), d_asm.data_ptr(),
-                                               d_gres.data_ptr(), s.cuda_stream), "covt_device_plan_assemble")
-
+                                               d_gres.data_ptr(), _stream(stream, self.device)),
+               "covt_device_plan_assemble")
 
     def wkb_copy(self):
         """(WKB records in tile order, WKB descriptors in launch order) as host arrays (Plan.wkb / Plan.wdescs)."""
-        self.geometry()
-        w = np.zeros(self.num_geometry_columns, dtype=WKB_INFO_DTYPE)
-        d = np.zeros(self.num_geometry_columns, dtype=WKB_DESC_DTYPE)
-        _raise(lib().covt_device_plan_wkb_copy(self._h, w.ctypes.data, d.ctypes.data), "covt_device_plan_wkb_copy")
-        return w, d
+        return self._copy("wkb", "covt_device_plan_wkb_copy")
 
     def alloc_wkb(self):
         """(WKB buffer, WKB results) on the device, sized for this plan's geometry columns."""
-        import torch
-
-        self.geometry()
-        return (torch.empty(max(self.wkb_bytes, 16), dtype=torch.uint8, device=self.device),
-                torch.zeros(max(self.num_geometry_columns, 1) * 2, dtype=torch.int64, device=self.device))
+        return self._alloc("wkb")
 
     def wkb(self, d_out, d_res, d_asm, d_gres, d_wkb, d_wres, stream=None):
         """Enqueue the WKB serialization over this plan's descriptors (after assemble() on the same stream)."""
-        import torch
-
         self.geometry(stream)
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
         _raise(lib().covt_device_plan_wkb(self._h, d_out.data_ptr(), d_res.data_ptr(), d_asm.data_ptr(),
-                                          d_gres.data_ptr(), d_wkb.data_ptr(), d_wres.data_ptr(), s.cuda_stream),
-               "covt_device_plan_wkb")
-
+                                          d_gres.data_ptr(), d_wkb.data_ptr(), d_wres.data_ptr(),
+                                          _stream(stream, self.device)), "covt_device_plan_wkb")
 
     def bbox_copy(self):
         """(bounding-box records in tile order, descriptors in launch order) as host arrays (Plan.bbox /
         Plan.bdescs)."""
-        self.geometry()
-        b = np.zeros(self.num_geometry_columns, dtype=BBOX_INFO_DTYPE)
-        d = np.zeros(self.num_geometry_columns, dtype=BBOX_DESC_DTYPE)
-        _raise(lib().covt_device_plan_bbox_copy(self._h, b.ctypes.data, d.ctypes.data), "covt_device_plan_bbox_copy")
-        return b, d
+        return self._copy("bbox", "covt_device_plan_bbox_copy")
 
     def alloc_bbox(self):
         """(bounding-box buffer, results) on the device, sized for this plan's geometry columns."""
-        import torch
-
-        self.geometry()
-        return (torch.empty(max(self.bbox_bytes, 16), dtype=torch.uint8, device=self.device),
-                torch.zeros(max(self.num_geometry_columns, 1) * 5, dtype=torch.int64, device=self.device))
+        return self._alloc("bbox")
 
     def bbox(self, d_asm, d_gres, d_bbox, d_bres, stream=None):
         """Enqueue the bounding boxes over this plan's descriptors (after assemble() on the same stream)."""
-        import torch
-
         self.geometry(stream)
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
         _raise(lib().covt_device_plan_bbox(self._h, d_asm.data_ptr(), d_gres.data_ptr(), d_bbox.data_ptr(),
-                                           d_bres.data_ptr(), s.cuda_stream), "covt_device_plan_bbox")
+                                           d_bres.data_ptr(), _stream(stream, self.device)), "covt_device_plan_bbox")
 
 
 class DeviceSubset:
@@ -1194,13 +1098,10 @@ class DeviceSubset:
         self.d_res = torch.zeros(max(self.num_descs, 1) * 2, dtype=torch.int32, device=batch.device)
 
     def decode(self, stream=None):
-        import torch
-
         b = self.batch
-        s = stream if stream is not None else torch.cuda.current_stream(b.device)
         _raise(lib().covt_decode_streams_device_grouped(b.d_in.data_ptr(), self.d_desc.data_ptr(),
                                                         _ptr(self.family_counts, C.c_int64), b.d_out.data_ptr(),
-                                                        self.d_res.data_ptr(), s.cuda_stream),
+                                                        self.d_res.data_ptr(), _stream(stream, b.device)),
                "covt_decode_streams_device_grouped")
 
     def decode_graph(self):
@@ -1406,10 +1307,11 @@ def version() -> str:
 
 
 # the files whose sha256 (in this order) the Makefile compiles into covt_version() as "src:<16 hex>"
-_BUILD_SOURCES = ("csrc/covt_decode.hip", "csrc/covt_assemble.hip", "csrc/covt_props.hip", "csrc/covt_plan_device.hip",
-                  "csrc/covt_wkb.hip", "csrc/covt_bbox.hip", "csrc/covt_host.cpp", "../include/covt.h", "csrc/covt_internal.h", "csrc/covt_wave.h",
-                  "csrc/covt_walk.h", "csrc/covt_props_plan.h", "csrc/covt_scratch.h", "csrc/covt_coop.h",
-                  "csrc/covt_wkb_plan.h", "csrc/covt_bbox_plan.h")
+_BUILD_SOURCES = (  # the Makefile's SRC, then its HDR, one to one
+    ("csrc/covt_decode.hip", "csrc/covt_assemble.hip", "csrc/covt_props.hip", "csrc/covt_plan_device.hip",
+     "csrc/covt_wkb.hip", "csrc/covt_bbox.hip", "csrc/covt_host.cpp")
+    + ("../include/covt.h", "csrc/covt_internal.h", "csrc/covt_wave.h", "csrc/covt_walk.h", "csrc/covt_props_plan.h",
+       "csrc/covt_scratch.h", "csrc/covt_coop.h", "csrc/covt_wkb_plan.h", "csrc/covt_bbox_plan.h"))
 
 
 def source_build_id() -> str:

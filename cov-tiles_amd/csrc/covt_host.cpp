@@ -923,54 +923,56 @@ void plan_geometry(covt_plan* p, int32_t nthr) {
     });
 }
 
-// WKB columns (include/covt.h "Geometry as WKB"): one per geometry column, slices laid out in tile order
-// next to the assembly layout (covt_wkb_plan.h), descriptors in the geometry descriptors' order.
-void plan_wkb(covt_plan* p) {
+// Products computed per geometry column (WKB, bounding boxes): one column each, slices laid out in tile
+// order by the product's layout rule, descriptors in the geometry descriptors' order.  `layout` is the rule
+// (column, offset, descriptor) -> next offset, `fill` copies the product's own offsets into the record.
+template <class Info, class Desc, class Layout, class Fill>
+int64_t plan_geometry_product(const covt_plan* p, std::vector<Info>& info, std::vector<Desc>& descs, Layout layout,
+                              Fill fill) {
     const size_t nc = p->ginfo.size();
-    p->winfo.resize(nc);
-    p->wdescs.resize(nc);
+    info.resize(nc);
+    descs.resize(nc);
     int64_t off = 0;
     for (size_t c = 0; c < nc; ++c) {
         const covt_geom_info& g = p->ginfo[c];
-        covt_wkb_desc d{};
-        off = wkb_column_layout(g.n_features, g.part_cap, g.ring_cap, g.coord_cap, (uint32_t)g.flags, off, d);
-        covt_wkb_info w{};
-        w.tile = g.tile;
-        w.layer = g.layer;
-        w.n_features = d.n_features;
-        w.desc_index = g.desc_index;
-        w.offsets_off = d.offsets_off;
-        w.bytes_off = d.bytes_off;
-        w.byte_cap = d.byte_cap;
-        w.flags = d.flags;
-        p->winfo[c] = w;
-        p->wdescs[(size_t)g.desc_index] = d;
+        Desc d{};
+        off = layout(g, off, d);
+        Info r{};
+        r.tile = g.tile;
+        r.layer = g.layer;
+        r.n_features = d.n_features;
+        r.desc_index = g.desc_index;
+        r.flags = d.flags;
+        fill(r, d);
+        info[c] = r;
+        descs[(size_t)g.desc_index] = d;
     }
-    p->wkb_bytes = off;
+    return off;
 }
 
-// Bounding-box columns (include/covt.h "Geometry bounding boxes"): one per geometry column, slices laid
-// out in tile order in a buffer of their own (covt_bbox_plan.h), descriptors in the geometry descriptors' order.
+// WKB columns (include/covt.h "Geometry as WKB"): slices next to the assembly layout (covt_wkb_plan.h).
+void plan_wkb(covt_plan* p) {
+    p->wkb_bytes = plan_geometry_product(
+        p, p->winfo, p->wdescs,
+        [](const covt_geom_info& g, int64_t off, covt_wkb_desc& d) {
+            return wkb_column_layout(g.n_features, g.part_cap, g.ring_cap, g.coord_cap, (uint32_t)g.flags, off, d);
+        },
+        [](covt_wkb_info& w, const covt_wkb_desc& d) {
+            w.offsets_off = d.offsets_off;
+            w.bytes_off = d.bytes_off;
+            w.byte_cap = d.byte_cap;
+        });
+}
+
+// Bounding-box columns (include/covt.h "Geometry bounding boxes"): slices in a buffer of their own
+// (covt_bbox_plan.h).
 void plan_bbox(covt_plan* p) {
-    const size_t nc = p->ginfo.size();
-    p->binfo.resize(nc);
-    p->bdescs.resize(nc);
-    int64_t off = 0;
-    for (size_t c = 0; c < nc; ++c) {
-        const covt_geom_info& g = p->ginfo[c];
-        covt_bbox_desc d{};
-        off = bbox_column_layout(g.n_features, (uint32_t)g.flags, off, d);
-        covt_bbox_info b{};
-        b.tile = g.tile;
-        b.layer = g.layer;
-        b.n_features = d.n_features;
-        b.desc_index = g.desc_index;
-        b.off = d.off;
-        b.flags = d.flags;
-        p->binfo[c] = b;
-        p->bdescs[(size_t)g.desc_index] = d;
-    }
-    p->bbox_bytes = off;
+    p->bbox_bytes = plan_geometry_product(
+        p, p->binfo, p->bdescs,
+        [](const covt_geom_info& g, int64_t off, covt_bbox_desc& d) {
+            return bbox_column_layout(g.n_features, (uint32_t)g.flags, off, d);
+        },
+        [](covt_bbox_info& b, const covt_bbox_desc& d) { b.off = d.off; });
 }
 
 // Property (sub)columns (include/covt.h "Property columns"; CovtParser.decodePropertyColumn
@@ -1922,277 +1924,171 @@ int decode_host_shards(const covt_plan* p, const uint8_t* bytes, uint64_t n_byte
 
 }  // namespace
 
+namespace {
+
+// the *_columns / *_descs accessors: the plan's records as they lie
+template <class T>
+int copy_records(const std::vector<T>* v, T* out) {
+    if (!v || (!out && !v->empty())) return COVT_ERR_INVALID_ARG;
+    if (!v->empty()) std::memcpy(out, v->data(), v->size() * sizeof(T));
+    return COVT_OK;
+}
+
+// Device memory and the stream of one whole-plan call, released by scope.
+struct DevMem {
+    void* p = nullptr;
+    DevMem() = default;
+    DevMem(const DevMem&) = delete;
+    DevMem& operator=(const DevMem&) = delete;
+    ~DevMem() { if (p) (void)hipFree(p); }
+    template <class T>
+    T* as() const { return static_cast<T*>(p); }
+};
+struct OwnStream {
+    hipStream_t s = nullptr;
+    OwnStream() = default;
+    OwnStream(const OwnStream&) = delete;
+    OwnStream& operator=(const OwnStream&) = delete;
+    ~OwnStream() { if (s) (void)hipStreamDestroy(s); }
+};
+
+// what a product's launch may read: the tiles, the decoded streams and, after assembly, the geometry
+struct PlanDev {
+    const uint8_t* in;
+    const uint8_t* out;
+    const covt_stream_result* res;
+    const covt_geom_desc* gdesc;  // null unless the assembly ran first
+    const uint8_t* asm_buf;
+    const covt_geom_result* gres;
+};
+
+// Whole plan on the current device, the one pipeline of the four *_host entry points below: the
+// caller's tile bytes [0, n_bytes) go to the device as they lie (the plan's offsets index them), then
+// decode, the assembly if the product reads it, the product's own launch and the copies back, on one
+// stream.  A product is its descriptor table `descs` (launch order), its records `info` (tile order;
+// their desc_index reorders the results), its buffer of `out_bytes` and launch(dev, d_descs, n, d_buf,
+// d_results, stream).  The first error wins; host_res is written on success only.
+template <class Info, class Desc, class Res, class Launch>
+int plan_product_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, const std::vector<Info>& info,
+                      const std::vector<Desc>& descs, int64_t out_bytes, uint8_t* host_out, Res* host_res,
+                      bool assemble_first, Launch launch) {
+    if ((!bytes && n_bytes) || (!host_out && out_bytes) || (!host_res && !info.empty())) return COVT_ERR_INVALID_ARG;
+    for (int32_t t = 0; t < p->n_tiles; ++t)
+        if (p->tile_off[(size_t)t] + p->tile_size[(size_t)t] > n_bytes) return COVT_ERR_INVALID_ARG;
+    OwnStream own;
+    if (hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking) != hipSuccess) return COVT_ERR_DEVICE;
+    hipStream_t s = own.s;
+    const size_t nd = p->descs.size(), nc = descs.size(), ng = p->gdescs.size();
+    int st = COVT_OK;
+    auto chk = [&](hipError_t e) { if (e != hipSuccess && st == COVT_OK) st = COVT_ERR_DEVICE; };
+    auto bytes_of = [](int64_t n) { return (size_t)std::max<int64_t>(n, 16); };
+    auto rows_of = [](size_t n, size_t elem) { return std::max<size_t>(n, 1) * elem; };
+    DevMem m_in, m_out, m_asm, m_buf, m_desc, m_res, m_gdesc, m_gres, m_pdesc, m_pres;
+    chk(hipMalloc(&m_in.p, (size_t)n_bytes + COVT_INPUT_PADDING));
+    chk(hipMalloc(&m_out.p, bytes_of(p->out_bytes)));
+    if (assemble_first) chk(hipMalloc(&m_asm.p, bytes_of(p->asm_bytes)));
+    chk(hipMalloc(&m_buf.p, bytes_of(out_bytes)));
+    chk(hipMalloc(&m_desc.p, rows_of(nd, sizeof(covt_stream_desc))));
+    chk(hipMalloc(&m_res.p, rows_of(nd, sizeof(covt_stream_result))));
+    if (assemble_first) {
+        chk(hipMalloc(&m_gdesc.p, rows_of(ng, sizeof(covt_geom_desc))));
+        chk(hipMalloc(&m_gres.p, rows_of(ng, sizeof(covt_geom_result))));
+    }
+    chk(hipMalloc(&m_pdesc.p, rows_of(nc, sizeof(Desc))));
+    chk(hipMalloc(&m_pres.p, rows_of(nc, sizeof(Res))));
+    uint8_t* d_in = m_in.as<uint8_t>();
+    const PlanDev dev{d_in, m_out.as<uint8_t>(), m_res.as<covt_stream_result>(), m_gdesc.as<covt_geom_desc>(),
+                      m_asm.as<uint8_t>(), m_gres.as<covt_geom_result>()};
+    std::vector<Res> res(nc);
+    if (st == COVT_OK) {
+        if (n_bytes) chk(hipMemcpyAsync(d_in, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, s));
+        chk(hipMemsetAsync(d_in + n_bytes, 0, COVT_INPUT_PADDING, s));
+        if (nd) chk(hipMemcpyAsync(m_desc.p, p->descs.data(), nd * sizeof(covt_stream_desc), hipMemcpyHostToDevice, s));
+        if (assemble_first && ng)
+            chk(hipMemcpyAsync(m_gdesc.p, p->gdescs.data(), ng * sizeof(covt_geom_desc), hipMemcpyHostToDevice, s));
+        if (nc) chk(hipMemcpyAsync(m_pdesc.p, descs.data(), nc * sizeof(Desc), hipMemcpyHostToDevice, s));
+        if (st == COVT_OK && ((uintptr_t)d_in & 15)) st = COVT_ERR_DEVICE;
+        if (st == COVT_OK)
+            st = launch_grouped(d_in, m_desc.as<covt_stream_desc>(), p->fam_counts, m_out.as<uint8_t>(),
+                                m_res.as<covt_stream_result>(), s);
+        if (st == COVT_OK && assemble_first)
+            st = covt_assemble_geometry_device(dev.out, dev.res, dev.gdesc, (int64_t)ng, m_asm.as<uint8_t>(),
+                                               m_gres.as<covt_geom_result>(), s);
+        if (st == COVT_OK) st = launch(dev, m_pdesc.as<Desc>(), (int64_t)nc, m_buf.as<uint8_t>(), m_pres.as<Res>(), s);
+        if (st == COVT_OK && out_bytes)
+            chk(hipMemcpyAsync(host_out, m_buf.p, (size_t)out_bytes, hipMemcpyDeviceToHost, s));
+        if (st == COVT_OK && nc) chk(hipMemcpyAsync(res.data(), m_pres.p, nc * sizeof(Res), hipMemcpyDeviceToHost, s));
+        chk(hipStreamSynchronize(s));
+    }
+    if (st == COVT_OK)
+        for (size_t k = 0; k < nc; ++k) host_res[k] = res[(size_t)info[k].desc_index];
+    return st;
+}
+
+}  // namespace
+
 extern "C" {
 
 int64_t covt_plan_num_geometry_columns(const covt_plan* p) { return p ? (int64_t)p->ginfo.size() : 0; }
 int64_t covt_plan_assembly_bytes(const covt_plan* p) { return p ? p->asm_bytes : 0; }
-int covt_plan_geometry_columns(const covt_plan* p, covt_geom_info* out) {
-    if (!p || (!out && !p->ginfo.empty())) return COVT_ERR_INVALID_ARG;
-    if (!p->ginfo.empty()) std::memcpy(out, p->ginfo.data(), p->ginfo.size() * sizeof(covt_geom_info));
-    return COVT_OK;
-}
-int covt_plan_geometry_descs(const covt_plan* p, covt_geom_desc* out) {
-    if (!p || (!out && !p->gdescs.empty())) return COVT_ERR_INVALID_ARG;
-    if (!p->gdescs.empty()) std::memcpy(out, p->gdescs.data(), p->gdescs.size() * sizeof(covt_geom_desc));
-    return COVT_OK;
-}
+int covt_plan_geometry_columns(const covt_plan* p, covt_geom_info* out) { return copy_records(p ? &p->ginfo : nullptr, out); }
+int covt_plan_geometry_descs(const covt_plan* p, covt_geom_desc* out) { return copy_records(p ? &p->gdescs : nullptr, out); }
 
-// Whole plan on the current device: the caller's tile bytes [0, n_bytes) go to the device as they
-// lie (the plan's offsets index them), then decode, assembly and the copies back on one stream.
+// decode, then the assembly as the product
 int covt_plan_assemble_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, uint8_t* host_asm,
                             covt_geom_result* host_gres) {
-    if (!p || (!bytes && n_bytes) || (!host_asm && p->asm_bytes) || (!host_gres && !p->ginfo.empty()))
-        return COVT_ERR_INVALID_ARG;
-    for (int32_t t = 0; t < p->n_tiles; ++t)
-        if (p->tile_off[(size_t)t] + p->tile_size[(size_t)t] > n_bytes) return COVT_ERR_INVALID_ARG;
-    hipStream_t s;
-    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return COVT_ERR_DEVICE;
-    const size_t nd = p->descs.size(), nc = p->gdescs.size();
-    uint8_t *d_in = nullptr, *d_out = nullptr, *d_asm = nullptr;
-    covt_stream_desc* d_desc = nullptr;
-    covt_stream_result* d_res = nullptr;
-    covt_geom_desc* d_gdesc = nullptr;
-    covt_geom_result* d_gres = nullptr;
-    int st = COVT_OK;
-    auto chk = [&](hipError_t e) { if (e != hipSuccess && st == COVT_OK) st = COVT_ERR_DEVICE; };
-    chk(hipMalloc(&d_in, (size_t)n_bytes + COVT_INPUT_PADDING));
-    chk(hipMalloc(&d_out, (size_t)std::max<int64_t>(p->out_bytes, 16)));
-    chk(hipMalloc(&d_asm, (size_t)std::max<int64_t>(p->asm_bytes, 16)));
-    chk(hipMalloc(&d_desc, std::max<size_t>(nd, 1) * sizeof(covt_stream_desc)));
-    chk(hipMalloc(&d_res, std::max<size_t>(nd, 1) * sizeof(covt_stream_result)));
-    chk(hipMalloc(&d_gdesc, std::max<size_t>(nc, 1) * sizeof(covt_geom_desc)));
-    chk(hipMalloc(&d_gres, std::max<size_t>(nc, 1) * sizeof(covt_geom_result)));
-    std::vector<covt_geom_result> gres(nc);
-    if (st == COVT_OK) {
-        if (n_bytes) chk(hipMemcpyAsync(d_in, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, s));
-        chk(hipMemsetAsync(d_in + n_bytes, 0, COVT_INPUT_PADDING, s));
-        if (nd) chk(hipMemcpyAsync(d_desc, p->descs.data(), nd * sizeof(covt_stream_desc), hipMemcpyHostToDevice, s));
-        if (nc)
-            chk(hipMemcpyAsync(d_gdesc, p->gdescs.data(), nc * sizeof(covt_geom_desc), hipMemcpyHostToDevice, s));
-        if (st == COVT_OK && ((uintptr_t)d_in & 15)) st = COVT_ERR_DEVICE;
-        if (st == COVT_OK) st = launch_grouped(d_in, d_desc, p->fam_counts, d_out, d_res, s);
-        if (st == COVT_OK)
-            st = covt_assemble_geometry_device(d_out, d_res, d_gdesc, (int64_t)nc, d_asm, d_gres, s);
-        if (st == COVT_OK && p->asm_bytes)
-            chk(hipMemcpyAsync(host_asm, d_asm, (size_t)p->asm_bytes, hipMemcpyDeviceToHost, s));
-        if (st == COVT_OK && nc)
-            chk(hipMemcpyAsync(gres.data(), d_gres, nc * sizeof(covt_geom_result), hipMemcpyDeviceToHost, s));
-        chk(hipStreamSynchronize(s));
-    }
-    if (st == COVT_OK)
-        for (size_t k = 0; k < nc; ++k) host_gres[k] = gres[(size_t)p->ginfo[k].desc_index];
-    for (void* q : {(void*)d_in, (void*)d_out, (void*)d_asm, (void*)d_desc, (void*)d_res, (void*)d_gdesc, (void*)d_gres})
-        if (q) (void)hipFree(q);
-    (void)hipStreamDestroy(s);
-    return st;
+    if (!p) return COVT_ERR_INVALID_ARG;
+    return plan_product_host(p, bytes, n_bytes, p->ginfo, p->gdescs, p->asm_bytes, host_asm, host_gres, false,
+                             [](const PlanDev& d, const covt_geom_desc* gdesc, int64_t n, uint8_t* buf,
+                                covt_geom_result* gres, hipStream_t s) {
+                                 return covt_assemble_geometry_device(d.out, d.res, gdesc, n, buf, gres, s);
+                             });
 }
 
 int64_t covt_plan_wkb_bytes(const covt_plan* p) { return p ? p->wkb_bytes : 0; }
-int covt_plan_wkb_columns(const covt_plan* p, covt_wkb_info* out) {
-    if (!p || (!out && !p->winfo.empty())) return COVT_ERR_INVALID_ARG;
-    if (!p->winfo.empty()) std::memcpy(out, p->winfo.data(), p->winfo.size() * sizeof(covt_wkb_info));
-    return COVT_OK;
-}
-int covt_plan_wkb_descs(const covt_plan* p, covt_wkb_desc* out) {
-    if (!p || (!out && !p->wdescs.empty())) return COVT_ERR_INVALID_ARG;
-    if (!p->wdescs.empty()) std::memcpy(out, p->wdescs.data(), p->wdescs.size() * sizeof(covt_wkb_desc));
-    return COVT_OK;
-}
+int covt_plan_wkb_columns(const covt_plan* p, covt_wkb_info* out) { return copy_records(p ? &p->winfo : nullptr, out); }
+int covt_plan_wkb_descs(const covt_plan* p, covt_wkb_desc* out) { return copy_records(p ? &p->wdescs : nullptr, out); }
 
-// Whole plan on the current device: tile bytes H2D as they lie, decode, assembly, WKB serialization, the
-// WKB buffer and results back on one stream.
+// decode, assembly, WKB serialization
 int covt_plan_wkb_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, uint8_t* host_wkb,
                        covt_wkb_result* host_wres) {
-    if (!p || (!bytes && n_bytes) || (!host_wkb && p->wkb_bytes) || (!host_wres && !p->winfo.empty()))
-        return COVT_ERR_INVALID_ARG;
-    for (int32_t t = 0; t < p->n_tiles; ++t)
-        if (p->tile_off[(size_t)t] + p->tile_size[(size_t)t] > n_bytes) return COVT_ERR_INVALID_ARG;
-    hipStream_t s;
-    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return COVT_ERR_DEVICE;
-    const size_t nd = p->descs.size(), nc = p->gdescs.size();
-    uint8_t *d_in = nullptr, *d_out = nullptr, *d_asm = nullptr, *d_wkb = nullptr;
-    covt_stream_desc* d_desc = nullptr;
-    covt_stream_result* d_res = nullptr;
-    covt_geom_desc* d_gdesc = nullptr;
-    covt_geom_result* d_gres = nullptr;
-    covt_wkb_desc* d_wdesc = nullptr;
-    covt_wkb_result* d_wres = nullptr;
-    int st = COVT_OK;
-    auto chk = [&](hipError_t e) { if (e != hipSuccess && st == COVT_OK) st = COVT_ERR_DEVICE; };
-    chk(hipMalloc(&d_in, (size_t)n_bytes + COVT_INPUT_PADDING));
-    chk(hipMalloc(&d_out, (size_t)std::max<int64_t>(p->out_bytes, 16)));
-    chk(hipMalloc(&d_asm, (size_t)std::max<int64_t>(p->asm_bytes, 16)));
-    chk(hipMalloc(&d_wkb, (size_t)std::max<int64_t>(p->wkb_bytes, 16)));
-    chk(hipMalloc(&d_desc, std::max<size_t>(nd, 1) * sizeof(covt_stream_desc)));
-    chk(hipMalloc(&d_res, std::max<size_t>(nd, 1) * sizeof(covt_stream_result)));
-    chk(hipMalloc(&d_gdesc, std::max<size_t>(nc, 1) * sizeof(covt_geom_desc)));
-    chk(hipMalloc(&d_gres, std::max<size_t>(nc, 1) * sizeof(covt_geom_result)));
-    chk(hipMalloc(&d_wdesc, std::max<size_t>(nc, 1) * sizeof(covt_wkb_desc)));
-    chk(hipMalloc(&d_wres, std::max<size_t>(nc, 1) * sizeof(covt_wkb_result)));
-    std::vector<covt_wkb_result> wres(nc);
-    if (st == COVT_OK) {
-        if (n_bytes) chk(hipMemcpyAsync(d_in, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, s));
-        chk(hipMemsetAsync(d_in + n_bytes, 0, COVT_INPUT_PADDING, s));
-        if (nd) chk(hipMemcpyAsync(d_desc, p->descs.data(), nd * sizeof(covt_stream_desc), hipMemcpyHostToDevice, s));
-        if (nc) {
-            chk(hipMemcpyAsync(d_gdesc, p->gdescs.data(), nc * sizeof(covt_geom_desc), hipMemcpyHostToDevice, s));
-            chk(hipMemcpyAsync(d_wdesc, p->wdescs.data(), nc * sizeof(covt_wkb_desc), hipMemcpyHostToDevice, s));
-        }
-        if (st == COVT_OK && ((uintptr_t)d_in & 15)) st = COVT_ERR_DEVICE;
-        if (st == COVT_OK) st = launch_grouped(d_in, d_desc, p->fam_counts, d_out, d_res, s);
-        if (st == COVT_OK)
-            st = covt_assemble_geometry_device(d_out, d_res, d_gdesc, (int64_t)nc, d_asm, d_gres, s);
-        if (st == COVT_OK)
-            st = covt_geometry_wkb_device(d_out, d_gdesc, d_asm, d_gres, d_wdesc, (int64_t)nc, d_wkb, d_wres, s);
-        if (st == COVT_OK && p->wkb_bytes)
-            chk(hipMemcpyAsync(host_wkb, d_wkb, (size_t)p->wkb_bytes, hipMemcpyDeviceToHost, s));
-        if (st == COVT_OK && nc)
-            chk(hipMemcpyAsync(wres.data(), d_wres, nc * sizeof(covt_wkb_result), hipMemcpyDeviceToHost, s));
-        chk(hipStreamSynchronize(s));
-    }
-    if (st == COVT_OK)
-        for (size_t k = 0; k < nc; ++k) host_wres[k] = wres[(size_t)p->winfo[k].desc_index];
-    for (void* q : {(void*)d_in, (void*)d_out, (void*)d_asm, (void*)d_wkb, (void*)d_desc, (void*)d_res, (void*)d_gdesc,
-                    (void*)d_gres, (void*)d_wdesc, (void*)d_wres})
-        if (q) (void)hipFree(q);
-    (void)hipStreamDestroy(s);
-    return st;
+    if (!p) return COVT_ERR_INVALID_ARG;
+    return plan_product_host(p, bytes, n_bytes, p->winfo, p->wdescs, p->wkb_bytes, host_wkb, host_wres, true,
+                             [](const PlanDev& d, const covt_wkb_desc* wdesc, int64_t n, uint8_t* buf,
+                                covt_wkb_result* wres, hipStream_t s) {
+                                 return covt_geometry_wkb_device(d.out, d.gdesc, d.asm_buf, d.gres, wdesc, n, buf, wres, s);
+                             });
 }
 
 int64_t covt_plan_bbox_bytes(const covt_plan* p) { return p ? p->bbox_bytes : 0; }
-int covt_plan_bbox_columns(const covt_plan* p, covt_bbox_info* out) {
-    if (!p || (!out && !p->binfo.empty())) return COVT_ERR_INVALID_ARG;
-    if (!p->binfo.empty()) std::memcpy(out, p->binfo.data(), p->binfo.size() * sizeof(covt_bbox_info));
-    return COVT_OK;
-}
-int covt_plan_bbox_descs(const covt_plan* p, covt_bbox_desc* out) {
-    if (!p || (!out && !p->bdescs.empty())) return COVT_ERR_INVALID_ARG;
-    if (!p->bdescs.empty()) std::memcpy(out, p->bdescs.data(), p->bdescs.size() * sizeof(covt_bbox_desc));
-    return COVT_OK;
-}
+int covt_plan_bbox_columns(const covt_plan* p, covt_bbox_info* out) { return copy_records(p ? &p->binfo : nullptr, out); }
+int covt_plan_bbox_descs(const covt_plan* p, covt_bbox_desc* out) { return copy_records(p ? &p->bdescs : nullptr, out); }
 
-// Whole plan on the current device: tile bytes H2D as they lie, decode, assembly, bounding boxes, the
-// bounding-box buffer and results back on one stream.
+// decode, assembly, bounding boxes
 int covt_plan_bbox_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, uint8_t* host_bbox,
                         covt_bbox_result* host_bres) {
-    if (!p || (!bytes && n_bytes) || (!host_bbox && p->bbox_bytes) || (!host_bres && !p->binfo.empty()))
-        return COVT_ERR_INVALID_ARG;
-    for (int32_t t = 0; t < p->n_tiles; ++t)
-        if (p->tile_off[(size_t)t] + p->tile_size[(size_t)t] > n_bytes) return COVT_ERR_INVALID_ARG;
-    hipStream_t s;
-    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return COVT_ERR_DEVICE;
-    const size_t nd = p->descs.size(), nc = p->gdescs.size();
-    uint8_t *d_in = nullptr, *d_out = nullptr, *d_asm = nullptr, *d_bbox = nullptr;
-    covt_stream_desc* d_desc = nullptr;
-    covt_stream_result* d_res = nullptr;
-    covt_geom_desc* d_gdesc = nullptr;
-    covt_geom_result* d_gres = nullptr;
-    covt_bbox_desc* d_bdesc = nullptr;
-    covt_bbox_result* d_bres = nullptr;
-    int st = COVT_OK;
-    auto chk = [&](hipError_t e) { if (e != hipSuccess && st == COVT_OK) st = COVT_ERR_DEVICE; };
-    chk(hipMalloc(&d_in, (size_t)n_bytes + COVT_INPUT_PADDING));
-    chk(hipMalloc(&d_out, (size_t)std::max<int64_t>(p->out_bytes, 16)));
-    chk(hipMalloc(&d_asm, (size_t)std::max<int64_t>(p->asm_bytes, 16)));
-    chk(hipMalloc(&d_bbox, (size_t)std::max<int64_t>(p->bbox_bytes, 16)));
-    chk(hipMalloc(&d_desc, std::max<size_t>(nd, 1) * sizeof(covt_stream_desc)));
-    chk(hipMalloc(&d_res, std::max<size_t>(nd, 1) * sizeof(covt_stream_result)));
-    chk(hipMalloc(&d_gdesc, std::max<size_t>(nc, 1) * sizeof(covt_geom_desc)));
-    chk(hipMalloc(&d_gres, std::max<size_t>(nc, 1) * sizeof(covt_geom_result)));
-    chk(hipMalloc(&d_bdesc, std::max<size_t>(nc, 1) * sizeof(covt_bbox_desc)));
-    chk(hipMalloc(&d_bres, std::max<size_t>(nc, 1) * sizeof(covt_bbox_result)));
-    std::vector<covt_bbox_result> bres(nc);
-    if (st == COVT_OK) {
-        if (n_bytes) chk(hipMemcpyAsync(d_in, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, s));
-        chk(hipMemsetAsync(d_in + n_bytes, 0, COVT_INPUT_PADDING, s));
-        if (nd) chk(hipMemcpyAsync(d_desc, p->descs.data(), nd * sizeof(covt_stream_desc), hipMemcpyHostToDevice, s));
-        if (nc) {
-            chk(hipMemcpyAsync(d_gdesc, p->gdescs.data(), nc * sizeof(covt_geom_desc), hipMemcpyHostToDevice, s));
-            chk(hipMemcpyAsync(d_bdesc, p->bdescs.data(), nc * sizeof(covt_bbox_desc), hipMemcpyHostToDevice, s));
-        }
-        if (st == COVT_OK && ((uintptr_t)d_in & 15)) st = COVT_ERR_DEVICE;
-        if (st == COVT_OK) st = launch_grouped(d_in, d_desc, p->fam_counts, d_out, d_res, s);
-        if (st == COVT_OK)
-            st = covt_assemble_geometry_device(d_out, d_res, d_gdesc, (int64_t)nc, d_asm, d_gres, s);
-        if (st == COVT_OK)
-            st = covt_geometry_bbox_device(d_gdesc, d_asm, d_gres, d_bdesc, (int64_t)nc, d_bbox, d_bres, s);
-        if (st == COVT_OK && p->bbox_bytes)
-            chk(hipMemcpyAsync(host_bbox, d_bbox, (size_t)p->bbox_bytes, hipMemcpyDeviceToHost, s));
-        if (st == COVT_OK && nc)
-            chk(hipMemcpyAsync(bres.data(), d_bres, nc * sizeof(covt_bbox_result), hipMemcpyDeviceToHost, s));
-        chk(hipStreamSynchronize(s));
-    }
-    if (st == COVT_OK)
-        for (size_t k = 0; k < nc; ++k) host_bres[k] = bres[(size_t)p->binfo[k].desc_index];
-    for (void* q : {(void*)d_in, (void*)d_out, (void*)d_asm, (void*)d_bbox, (void*)d_desc, (void*)d_res, (void*)d_gdesc,
-                    (void*)d_gres, (void*)d_bdesc, (void*)d_bres})
-        if (q) (void)hipFree(q);
-    (void)hipStreamDestroy(s);
-    return st;
+    if (!p) return COVT_ERR_INVALID_ARG;
+    return plan_product_host(p, bytes, n_bytes, p->binfo, p->bdescs, p->bbox_bytes, host_bbox, host_bres, true,
+                             [](const PlanDev& d, const covt_bbox_desc* bdesc, int64_t n, uint8_t* buf,
+                                covt_bbox_result* bres, hipStream_t s) {
+                                 return covt_geometry_bbox_device(d.gdesc, d.asm_buf, d.gres, bdesc, n, buf, bres, s);
+                             });
 }
 
 int64_t covt_plan_num_property_columns(const covt_plan* p) { return p ? (int64_t)p->pinfo.size() : 0; }
 int64_t covt_plan_property_bytes(const covt_plan* p) { return p ? p->prop_bytes : 0; }
-int covt_plan_property_columns(const covt_plan* p, covt_prop_info* out) {
-    if (!p || (!out && !p->pinfo.empty())) return COVT_ERR_INVALID_ARG;
-    if (!p->pinfo.empty()) std::memcpy(out, p->pinfo.data(), p->pinfo.size() * sizeof(covt_prop_info));
-    return COVT_OK;
-}
-int covt_plan_property_descs(const covt_plan* p, covt_prop_desc* out) {
-    if (!p || (!out && !p->pdescs.empty())) return COVT_ERR_INVALID_ARG;
-    if (!p->pdescs.empty()) std::memcpy(out, p->pdescs.data(), p->pdescs.size() * sizeof(covt_prop_desc));
-    return COVT_OK;
-}
+int covt_plan_property_columns(const covt_plan* p, covt_prop_info* out) { return copy_records(p ? &p->pinfo : nullptr, out); }
+int covt_plan_property_descs(const covt_plan* p, covt_prop_desc* out) { return copy_records(p ? &p->pdescs : nullptr, out); }
 
-// Whole plan on the current device: tile bytes H2D as they lie, decode, property materialization,
-// copies back on one stream.
+// decode, property materialization
 int covt_plan_properties_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, uint8_t* host_props,
                               covt_prop_result* host_pres) {
-    if (!p || (!bytes && n_bytes) || (!host_props && p->prop_bytes) || (!host_pres && !p->pinfo.empty()))
-        return COVT_ERR_INVALID_ARG;
-    for (int32_t t = 0; t < p->n_tiles; ++t)
-        if (p->tile_off[(size_t)t] + p->tile_size[(size_t)t] > n_bytes) return COVT_ERR_INVALID_ARG;
-    hipStream_t s;
-    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return COVT_ERR_DEVICE;
-    const size_t nd = p->descs.size(), nc = p->pdescs.size();
-    uint8_t *d_in = nullptr, *d_out = nullptr, *d_props = nullptr;
-    covt_stream_desc* d_desc = nullptr;
-    covt_stream_result* d_res = nullptr;
-    covt_prop_desc* d_pdesc = nullptr;
-    covt_prop_result* d_pres = nullptr;
-    int st = COVT_OK;
-    auto chk = [&](hipError_t e) { if (e != hipSuccess && st == COVT_OK) st = COVT_ERR_DEVICE; };
-    chk(hipMalloc(&d_in, (size_t)n_bytes + COVT_INPUT_PADDING));
-    chk(hipMalloc(&d_out, (size_t)std::max<int64_t>(p->out_bytes, 16)));
-    chk(hipMalloc(&d_props, (size_t)std::max<int64_t>(p->prop_bytes, 16)));
-    chk(hipMalloc(&d_desc, std::max<size_t>(nd, 1) * sizeof(covt_stream_desc)));
-    chk(hipMalloc(&d_res, std::max<size_t>(nd, 1) * sizeof(covt_stream_result)));
-    chk(hipMalloc(&d_pdesc, std::max<size_t>(nc, 1) * sizeof(covt_prop_desc)));
-    chk(hipMalloc(&d_pres, std::max<size_t>(nc, 1) * sizeof(covt_prop_result)));
-    std::vector<covt_prop_result> pres(nc);
-    if (st == COVT_OK) {
-        if (n_bytes) chk(hipMemcpyAsync(d_in, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, s));
-        chk(hipMemsetAsync(d_in + n_bytes, 0, COVT_INPUT_PADDING, s));
-        if (nd) chk(hipMemcpyAsync(d_desc, p->descs.data(), nd * sizeof(covt_stream_desc), hipMemcpyHostToDevice, s));
-        if (nc)
-            chk(hipMemcpyAsync(d_pdesc, p->pdescs.data(), nc * sizeof(covt_prop_desc), hipMemcpyHostToDevice, s));
-        if (st == COVT_OK && ((uintptr_t)d_in & 15)) st = COVT_ERR_DEVICE;
-        if (st == COVT_OK) st = launch_grouped(d_in, d_desc, p->fam_counts, d_out, d_res, s);
-        if (st == COVT_OK)
-            st = covt_materialize_properties_device(d_in, d_out, d_res, d_pdesc, (int64_t)nc, d_props, d_pres, s);
-        if (st == COVT_OK && p->prop_bytes)
-            chk(hipMemcpyAsync(host_props, d_props, (size_t)p->prop_bytes, hipMemcpyDeviceToHost, s));
-        if (st == COVT_OK && nc)
-            chk(hipMemcpyAsync(pres.data(), d_pres, nc * sizeof(covt_prop_result), hipMemcpyDeviceToHost, s));
-        chk(hipStreamSynchronize(s));
-    }
-    if (st == COVT_OK)
-        for (size_t k = 0; k < nc; ++k) host_pres[k] = pres[(size_t)p->pinfo[k].desc_index];
-    for (void* q : {(void*)d_in, (void*)d_out, (void*)d_props, (void*)d_desc, (void*)d_res, (void*)d_pdesc,
-                    (void*)d_pres})
-        if (q) (void)hipFree(q);
-    (void)hipStreamDestroy(s);
-    return st;
+    if (!p) return COVT_ERR_INVALID_ARG;
+    return plan_product_host(p, bytes, n_bytes, p->pinfo, p->pdescs, p->prop_bytes, host_props, host_pres, false,
+                             [](const PlanDev& d, const covt_prop_desc* pdesc, int64_t n, uint8_t* buf,
+                                covt_prop_result* pres, hipStream_t s) {
+                                 return covt_materialize_properties_device(d.in, d.out, d.res, pdesc, n, buf, pres, s);
+                             });
 }
 
 }  // extern "C"

@@ -2741,64 +2741,93 @@ __global__ void geom_descs(const covt_stream_info* __restrict__ info, covt_geom_
     gdesc[k] = d;
 }
 
-// WKB columns (covt_host.cpp plan_wkb): slices in tile order from the shared layout rule
-// (covt_wkb_plan.h), a record per column and its descriptor at the geometry descriptor's row.
-__global__ void wkb_col_bytes(const covt_geom_info* __restrict__ ginfo, int64_t nc, int64_t* __restrict__ wbytes) {
+// Products computed per geometry column (covt_host.cpp plan_geometry_product): slices in tile order from
+// the product's layout rule, a record per column and its descriptor at the geometry descriptor's row.  A
+// product names its record and descriptor types, the rule and the offsets the record repeats.
+struct WkbProduct {  // covt_wkb_plan.h
+    using Info = covt_wkb_info;
+    using Desc = covt_wkb_desc;
+    static __device__ int64_t layout(const covt_geom_info& g, int64_t off, Desc& d) {
+        return wkb_column_layout(g.n_features, g.part_cap, g.ring_cap, g.coord_cap, (uint32_t)g.flags, off, d);
+    }
+    static __device__ void fill(Info& w, const Desc& d) {
+        w.offsets_off = d.offsets_off;
+        w.bytes_off = d.bytes_off;
+        w.byte_cap = d.byte_cap;
+    }
+};
+struct BboxProduct {  // covt_bbox_plan.h
+    using Info = covt_bbox_info;
+    using Desc = covt_bbox_desc;
+    static __device__ int64_t layout(const covt_geom_info& g, int64_t off, Desc& d) {
+        return bbox_column_layout(g.n_features, (uint32_t)g.flags, off, d);
+    }
+    static __device__ void fill(Info& b, const Desc& d) { b.off = d.off; }
+};
+template <class P>
+__global__ void product_col_bytes(const covt_geom_info* __restrict__ ginfo, int64_t nc, int64_t* __restrict__ bytes) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= nc) return;
-    const covt_geom_info& g = ginfo[c];
-    covt_wkb_desc d{};
-    wbytes[c] = wkb_column_layout(g.n_features, g.part_cap, g.ring_cap, g.coord_cap, (uint32_t)g.flags, 0, d);
+    typename P::Desc d{};
+    bytes[c] = P::layout(ginfo[c], 0, d);
 }
-__global__ void wkb_records(const covt_geom_info* __restrict__ ginfo, int64_t nc, const int64_t* __restrict__ woff,
-                            covt_wkb_info* __restrict__ winfo, covt_wkb_desc* __restrict__ wdesc) {
+template <class P>
+__global__ void product_records(const covt_geom_info* __restrict__ ginfo, int64_t nc, const int64_t* __restrict__ off,
+                                typename P::Info* __restrict__ info, typename P::Desc* __restrict__ desc) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= nc) return;
     const covt_geom_info& g = ginfo[c];
-    covt_wkb_desc d{};
-    (void)wkb_column_layout(g.n_features, g.part_cap, g.ring_cap, g.coord_cap, (uint32_t)g.flags, woff[c], d);
-    covt_wkb_info w{};
-    w.tile = g.tile;
-    w.layer = g.layer;
-    w.n_features = d.n_features;
-    w.desc_index = g.desc_index;
-    w.offsets_off = d.offsets_off;
-    w.bytes_off = d.bytes_off;
-    w.byte_cap = d.byte_cap;
-    w.flags = d.flags;
-    winfo[c] = w;
-    wdesc[g.desc_index] = d;
-}
-
-// Bounding-box columns (covt_host.cpp plan_bbox): slices in tile order from the shared layout rule
-// (covt_bbox_plan.h), a record per column and its descriptor at the geometry descriptor's row.
-__global__ void bbox_col_bytes(const covt_geom_info* __restrict__ ginfo, int64_t nc, int64_t* __restrict__ bbytes) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= nc) return;
-    const covt_geom_info& g = ginfo[c];
-    covt_bbox_desc d{};
-    bbytes[c] = bbox_column_layout(g.n_features, (uint32_t)g.flags, 0, d);
-}
-__global__ void bbox_records(const covt_geom_info* __restrict__ ginfo, int64_t nc, const int64_t* __restrict__ boff,
-                             covt_bbox_info* __restrict__ binfo, covt_bbox_desc* __restrict__ bdesc) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= nc) return;
-    const covt_geom_info& g = ginfo[c];
-    covt_bbox_desc d{};
-    (void)bbox_column_layout(g.n_features, (uint32_t)g.flags, boff[c], d);
-    covt_bbox_info b{};
-    b.tile = g.tile;
-    b.layer = g.layer;
-    b.n_features = d.n_features;
-    b.desc_index = g.desc_index;
-    b.off = d.off;
-    b.flags = d.flags;
-    binfo[c] = b;
-    bdesc[g.desc_index] = d;
+    typename P::Desc d{};
+    (void)P::layout(g, off[c], d);
+    typename P::Info r{};
+    r.tile = g.tile;
+    r.layer = g.layer;
+    r.n_features = d.n_features;
+    r.desc_index = g.desc_index;
+    r.flags = d.flags;
+    P::fill(r, d);
+    info[c] = r;
+    desc[g.desc_index] = d;
 }
 
 size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// One product of covt_device_plan_geometry.  Its slice of the geometry arena: records | descriptors | column
+// bytes | column offsets.  Over the nc finished geometry records (tile order): the bytes kernel, their scan, the
+// records kernel and the copy of the total to *total, which holds after the caller's synchronize.
+template <class P>
+size_t product_arena_bytes(size_t m) {
+    return up256(m * sizeof(typename P::Info)) + up256(m * sizeof(typename P::Desc)) + 2 * up256((m + 1) * 8);
+}
+template <class P>
+int plan_product(uint8_t* slice, size_t m, int64_t nc, const covt_geom_info* ginfo, void* scan_mem, size_t scan_tmp,
+                 hipStream_t s, typename P::Info*& info, typename P::Desc*& desc, int64_t* total) {
+    info = (typename P::Info*)slice;
+    desc = (typename P::Desc*)(slice + up256(m * sizeof(typename P::Info)));
+    int64_t* bytes = (int64_t*)((uint8_t*)desc + up256(m * sizeof(typename P::Desc)));
+    int64_t* off = (int64_t*)((uint8_t*)bytes + up256((m + 1) * 8));
+    if (hipMemsetAsync(bytes, 0, (m + 1) * 8, s) != hipSuccess) return COVT_ERR_DEVICE;
+    if (nc <= 0) return COVT_OK;
+    const int cb = (int)((nc + 255) / 256);
+    product_col_bytes<P><<<cb, 256, 0, s>>>(ginfo, nc, bytes);
+    if (hipGetLastError() != hipSuccess) return COVT_ERR_DEVICE;
+    if (hipcub::DeviceScan::ExclusiveSum(scan_mem, scan_tmp, bytes, off, (int)(nc + 1), s) != hipSuccess)
+        return COVT_ERR_DEVICE;
+    product_records<P><<<cb, 256, 0, s>>>(ginfo, nc, off, info, desc);
+    if (hipGetLastError() != hipSuccess) return COVT_ERR_DEVICE;
+    return hipMemcpyAsync(total, off + nc, 8, hipMemcpyDeviceToHost, s) == hipSuccess ? COVT_OK : COVT_ERR_DEVICE;
+}
+
+// the *_copy entry points: n records and n descriptors of a built plan to the host (either may be null)
+template <class Info, class Desc>
+int copy_to_host(int64_t n, Info* infos, const Info* d_infos, Desc* descs, const Desc* d_descs) {
+    if (n <= 0) return COVT_OK;
+    if (infos && hipMemcpy(infos, d_infos, (size_t)n * sizeof(Info), hipMemcpyDeviceToHost) != hipSuccess)
+        return COVT_ERR_DEVICE;
+    if (descs && hipMemcpy(descs, d_descs, (size_t)n * sizeof(Desc), hipMemcpyDeviceToHost) != hipSuccess)
+        return COVT_ERR_DEVICE;
+    return COVT_OK;
+}
 
 }  // namespace
 
@@ -3328,11 +3357,8 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     const size_t o_gd = up256(m * sizeof(covt_geom_info)), o_cb = o_gd + up256(m * sizeof(covt_geom_desc)),
                  o_co = o_cb + up256((m + 1) * 8), o_k0 = o_co + up256((m + 1) * 8), o_k1 = o_k0 + up256(m * 8),
                  o_v0 = o_k1 + up256(m * 8), o_v1 = o_v0 + up256(m * 4), o_st = o_v1 + up256(m * 4),
-                 o_cs = o_st + up256(sort_tmp), o_wi = o_cs + up256(cscan_tmp),
-                 o_wd = o_wi + up256(m * sizeof(covt_wkb_info)), o_wb = o_wd + up256(m * sizeof(covt_wkb_desc)),
-                 o_wo = o_wb + up256((m + 1) * 8), o_bi = o_wo + up256((m + 1) * 8),
-                 o_bd = o_bi + up256(m * sizeof(covt_bbox_info)), o_bb = o_bd + up256(m * sizeof(covt_bbox_desc)),
-                 o_bo = o_bb + up256((m + 1) * 8), total = o_bo + up256((m + 1) * 8);
+                 o_cs = o_st + up256(sort_tmp), o_wkb = o_cs + up256(cscan_tmp),
+                 o_bbox = o_wkb + product_arena_bytes<WkbProduct>(m), total = o_bbox + product_arena_bytes<BboxProduct>(m);
     // the arena is the plan's only on success: a failed build frees it (a retry allocates afresh)
     void* arena = nullptr;
     if (plan_malloc(&arena, total, p->dev, s) != hipSuccess) return COVT_ERR_DEVICE;
@@ -3344,14 +3370,6 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     uint64_t *k0 = (uint64_t*)(g + o_k0), *k1 = (uint64_t*)(g + o_k1);
     uint32_t *v0 = (uint32_t*)(g + o_v0), *v1 = (uint32_t*)(g + o_v1);
     if (hipMemsetAsync(colbytes, 0, (m + 1) * 8, s) != hipSuccess) return COVT_ERR_DEVICE;
-    covt_wkb_info* winfo = (covt_wkb_info*)(g + o_wi);
-    covt_wkb_desc* wdesc = (covt_wkb_desc*)(g + o_wd);
-    int64_t *wbytes = (int64_t*)(g + o_wb), *woff = (int64_t*)(g + o_wo);
-    if (hipMemsetAsync(wbytes, 0, (m + 1) * 8, s) != hipSuccess) return COVT_ERR_DEVICE;
-    covt_bbox_info* binfo = (covt_bbox_info*)(g + o_bi);
-    covt_bbox_desc* bdesc = (covt_bbox_desc*)(g + o_bd);
-    int64_t *bbytes = (int64_t*)(g + o_bb), *boff = (int64_t*)(g + o_bo);
-    if (hipMemsetAsync(bbytes, 0, (m + 1) * 8, s) != hipSuccess) return COVT_ERR_DEVICE;
     int64_t asm_bytes = 0, wkb_bytes = 0, bbox_bytes = 0;
     if (nc > 0) {
         geom_columns<<<(int)((ns + 255) / 256), 256, 0, s>>>(p->d_info, ns, p->format, gst, gpos, p->d_ginfo, colbytes);
@@ -3365,37 +3383,24 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
             return COVT_ERR_DEVICE;
         geom_descs<<<cb, 256, 0, s>>>(p->d_info, p->d_ginfo, v1, nc, p->d_gdesc);
         if (hipGetLastError() != hipSuccess) return COVT_ERR_DEVICE;
-        // the WKB layout over the finished records (tile order), descriptors at the geometry descriptors' rows
-        wkb_col_bytes<<<cb, 256, 0, s>>>(p->d_ginfo, nc, wbytes);
-        if (hipGetLastError() != hipSuccess) return COVT_ERR_DEVICE;
-        if (hipcub::DeviceScan::ExclusiveSum(g + o_cs, cscan_tmp, wbytes, woff, (int)(nc + 1), s) != hipSuccess)
-            return COVT_ERR_DEVICE;
-        wkb_records<<<cb, 256, 0, s>>>(p->d_ginfo, nc, woff, winfo, wdesc);
-        if (hipGetLastError() != hipSuccess) return COVT_ERR_DEVICE;
-        if (hipMemcpyAsync(&wkb_bytes, woff + nc, 8, hipMemcpyDeviceToHost, s) != hipSuccess) return COVT_ERR_DEVICE;
-        // the bounding-box layout, the same way
-        bbox_col_bytes<<<cb, 256, 0, s>>>(p->d_ginfo, nc, bbytes);
-        if (hipGetLastError() != hipSuccess) return COVT_ERR_DEVICE;
-        if (hipcub::DeviceScan::ExclusiveSum(g + o_cs, cscan_tmp, bbytes, boff, (int)(nc + 1), s) != hipSuccess)
-            return COVT_ERR_DEVICE;
-        bbox_records<<<cb, 256, 0, s>>>(p->d_ginfo, nc, boff, binfo, bdesc);
-        if (hipGetLastError() != hipSuccess) return COVT_ERR_DEVICE;
-        if (hipMemcpyAsync(&bbox_bytes, boff + nc, 8, hipMemcpyDeviceToHost, s) != hipSuccess) return COVT_ERR_DEVICE;
-        if (hipMemcpyAsync(&asm_bytes, coloff + nc, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            return COVT_ERR_DEVICE;
     }
+    // the products' layouts over the finished records, descriptors at the geometry descriptors' rows
+    int st = plan_product<WkbProduct>(g + o_wkb, m, nc, p->d_ginfo, g + o_cs, cscan_tmp, s, p->d_winfo, p->d_wdesc,
+                                      &wkb_bytes);
+    if (st == COVT_OK)
+        st = plan_product<BboxProduct>(g + o_bbox, m, nc, p->d_ginfo, g + o_cs, cscan_tmp, s, p->d_binfo, p->d_bdesc,
+                                       &bbox_bytes);
+    if (st) return st;
+    if (nc > 0 && (hipMemcpyAsync(&asm_bytes, coloff + nc, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                   hipStreamSynchronize(s) != hipSuccess))
+        return COVT_ERR_DEVICE;
     if (p->geo_arena) (void)hipFreeAsync(p->geo_arena, s);
     p->geo_arena = arena;
     free_arena.q = nullptr;
     p->n_geo = nc;
     p->asm_bytes = asm_bytes;
     p->wkb_bytes = wkb_bytes;
-    p->d_winfo = winfo;
-    p->d_wdesc = wdesc;
     p->bbox_bytes = bbox_bytes;
-    p->d_binfo = binfo;
-    p->d_bdesc = bdesc;
     p->geo_built = true;
     return COVT_OK;
 }
@@ -3405,12 +3410,7 @@ int64_t covt_device_plan_property_bytes(const covt_device_plan* p) { return p ? 
 const covt_prop_desc* covt_device_plan_property_descs_device(const covt_device_plan* p) { return p ? p->d_pdesc : nullptr; }
 int covt_device_plan_property_copy(const covt_device_plan* p, covt_prop_info* infos, covt_prop_desc* descs) {
     if (!p) return COVT_ERR_INVALID_ARG;
-    if (p->n_props == 0) return COVT_OK;
-    if (infos && hipMemcpy(infos, p->d_pinfo, (size_t)p->n_props * sizeof(covt_prop_info), hipMemcpyDeviceToHost) != hipSuccess)
-        return COVT_ERR_DEVICE;
-    if (descs && hipMemcpy(descs, p->d_pdesc, (size_t)p->n_props * sizeof(covt_prop_desc), hipMemcpyDeviceToHost) != hipSuccess)
-        return COVT_ERR_DEVICE;
-    return COVT_OK;
+    return copy_to_host(p->n_props, infos, p->d_pinfo, descs, p->d_pdesc);
 }
 int covt_device_plan_materialize(const covt_device_plan* p, const uint8_t* d_in, const uint8_t* d_decoded,
                                  const covt_stream_result* d_res, uint8_t* d_props, covt_prop_result* d_pres,
@@ -3427,12 +3427,7 @@ const covt_geom_desc* covt_device_plan_geometry_descs_device(const covt_device_p
 
 int covt_device_plan_geometry_copy(const covt_device_plan* p, covt_geom_info* infos, covt_geom_desc* descs) {
     if (!p || !p->geo_built) return COVT_ERR_INVALID_ARG;
-    const size_t nc = (size_t)p->n_geo;
-    if (infos && nc && hipMemcpy(infos, p->d_ginfo, nc * sizeof(covt_geom_info), hipMemcpyDeviceToHost) != hipSuccess)
-        return COVT_ERR_DEVICE;
-    if (descs && nc && hipMemcpy(descs, p->d_gdesc, nc * sizeof(covt_geom_desc), hipMemcpyDeviceToHost) != hipSuccess)
-        return COVT_ERR_DEVICE;
-    return COVT_OK;
+    return copy_to_host(p->n_geo, infos, p->d_ginfo, descs, p->d_gdesc);
 }
 
 int64_t covt_device_plan_wkb_bytes(const covt_device_plan* p) { return p && p->geo_built ? p->wkb_bytes : 0; }
@@ -3441,12 +3436,7 @@ const covt_wkb_desc* covt_device_plan_wkb_descs_device(const covt_device_plan* p
 }
 int covt_device_plan_wkb_copy(const covt_device_plan* p, covt_wkb_info* infos, covt_wkb_desc* descs) {
     if (!p || !p->geo_built) return COVT_ERR_INVALID_ARG;
-    const size_t nc = (size_t)p->n_geo;
-    if (infos && nc && hipMemcpy(infos, p->d_winfo, nc * sizeof(covt_wkb_info), hipMemcpyDeviceToHost) != hipSuccess)
-        return COVT_ERR_DEVICE;
-    if (descs && nc && hipMemcpy(descs, p->d_wdesc, nc * sizeof(covt_wkb_desc), hipMemcpyDeviceToHost) != hipSuccess)
-        return COVT_ERR_DEVICE;
-    return COVT_OK;
+    return copy_to_host(p->n_geo, infos, p->d_winfo, descs, p->d_wdesc);
 }
 int covt_device_plan_wkb(covt_device_plan* p, const uint8_t* d_decoded, const covt_stream_result* d_res,
                          const uint8_t* d_asm, const covt_geom_result* d_gres, uint8_t* d_wkb,
@@ -3465,12 +3455,7 @@ const covt_bbox_desc* covt_device_plan_bbox_descs_device(const covt_device_plan*
 }
 int covt_device_plan_bbox_copy(const covt_device_plan* p, covt_bbox_info* infos, covt_bbox_desc* descs) {
     if (!p || !p->geo_built) return COVT_ERR_INVALID_ARG;
-    const size_t nc = (size_t)p->n_geo;
-    if (infos && nc && hipMemcpy(infos, p->d_binfo, nc * sizeof(covt_bbox_info), hipMemcpyDeviceToHost) != hipSuccess)
-        return COVT_ERR_DEVICE;
-    if (descs && nc && hipMemcpy(descs, p->d_bdesc, nc * sizeof(covt_bbox_desc), hipMemcpyDeviceToHost) != hipSuccess)
-        return COVT_ERR_DEVICE;
-    return COVT_OK;
+    return copy_to_host(p->n_geo, infos, p->d_binfo, descs, p->d_bdesc);
 }
 int covt_device_plan_bbox(covt_device_plan* p, const uint8_t* d_asm, const covt_geom_result* d_gres, uint8_t* d_bbox,
                           covt_bbox_result* d_bres, void* hip_stream) {

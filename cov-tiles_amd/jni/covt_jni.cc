@@ -8,6 +8,7 @@
 #include <jni.h>
 
 #include <algorithm>
+#include <array>
 #include <cstring>
 #include <vector>
 
@@ -49,6 +50,28 @@ jintArray int_result(JNIEnv* env, jsize n, F&& f) {
     jintArray r = env->NewIntArray(n);
     env->SetIntArrayRegion(r, 0, n, out.data());
     return r;
+}
+
+// N records as one long[] of N rows of K longs; row(record) is a record's row
+template <size_t K, class T, class Row>
+jlongArray long_rows(JNIEnv* env, const std::vector<T>& recs, Row&& row) {
+    std::vector<jlong> rows(recs.size() * K);
+    for (size_t i = 0; i < recs.size(); ++i) {
+        const std::array<jlong, K> r = row(recs[i]);
+        std::copy(r.begin(), r.end(), rows.begin() + K * i);
+    }
+    jlongArray a = env->NewLongArray((jsize)rows.size());
+    env->SetLongArrayRegion(a, 0, (jsize)rows.size(), rows.data());
+    return a;
+}
+
+// The address of a direct output buffer that holds `need` bytes.  A heap buffer has no address, a short one
+// would be overrun: null with an IllegalArgumentException pending either way.
+uint8_t* direct_out(JNIEnv* env, jobject out, int64_t need) {
+    uint8_t* dst = static_cast<uint8_t*>(env->GetDirectBufferAddress(out));
+    if (dst && env->GetDirectBufferCapacity(out) >= need) return dst;
+    check(env, COVT_ERR_INVALID_ARG);
+    return nullptr;
 }
 
 }  // namespace
@@ -206,34 +229,20 @@ JNIEXPORT jlongArray JNICALL BFN(streams)(JNIEnv* env, jclass, jlong h) {
     const int64_t n = covt_plan_num_streams(plan_of(h));
     std::vector<covt_stream_info> info((size_t)n);
     if (!check(env, covt_plan_streams(plan_of(h), info.data()))) return nullptr;
-    std::vector<jlong> rows((size_t)n * 15);
-    for (int64_t i = 0; i < n; ++i) {
-        const covt_stream_info& s = info[(size_t)i];
-        const jlong r[15] = {s.tile, s.layer, s.column_kind, s.stream_type, s.encoding, s.column_type, s.num_values,
-                             s.byte_length, s.num_bits, s.op, s.elem_bytes, s.desc_index, s.in_off, s.out_off,
-                             s.out_elems};
-        std::copy(r, r + 15, rows.begin() + 15 * i);
-    }
-    jlongArray a = env->NewLongArray((jsize)rows.size());
-    env->SetLongArrayRegion(a, 0, (jsize)rows.size(), rows.data());
-    return a;
+    return long_rows<15>(env, info, [](const covt_stream_info& s) -> std::array<jlong, 15> {
+        return {s.tile, s.layer, s.column_kind, s.stream_type, s.encoding, s.column_type, s.num_values, s.byte_length,
+                s.num_bits, s.op, s.elem_bytes, s.desc_index, s.in_off, s.out_off, s.out_elems};
+    });
 }
 JNIEXPORT jlongArray JNICALL BFN(propertyColumns)(JNIEnv* env, jclass, jlong h) {
     const int64_t n = covt_plan_num_property_columns(plan_of(h));
     std::vector<covt_prop_info> info((size_t)n);
     if (!check(env, covt_plan_property_columns(plan_of(h), info.data()))) return nullptr;
-    std::vector<jlong> rows((size_t)n * 22);
-    for (int64_t i = 0; i < n; ++i) {
-        const covt_prop_info& q = info[(size_t)i];
-        const jlong r[22] = {q.tile, q.layer, q.column, q.type, q.column_type, q.n_features, q.n_data, q.n_dict,
-                             q.lang, q.name_len, q.lang_len, q.dict_bytes, q.stream[0], q.stream[1], q.stream[2],
-                             q.desc_index, q.name_off, q.lang_off, q.out_off[0], q.out_off[1], q.out_off[2],
-                             q.out_off[3]};
-        std::copy(r, r + 22, rows.begin() + 22 * i);
-    }
-    jlongArray a = env->NewLongArray((jsize)rows.size());
-    env->SetLongArrayRegion(a, 0, (jsize)rows.size(), rows.data());
-    return a;
+    return long_rows<22>(env, info, [](const covt_prop_info& q) -> std::array<jlong, 22> {
+        return {q.tile, q.layer, q.column, q.type, q.column_type, q.n_features, q.n_data, q.n_dict,
+                q.lang, q.name_len, q.lang_len, q.dict_bytes, q.stream[0], q.stream[1], q.stream[2],
+                q.desc_index, q.name_off, q.lang_off, q.out_off[0], q.out_off[1], q.out_off[2], q.out_off[3]};
+    });
 }
 JNIEXPORT jintArray JNICALL BFN(decode)(JNIEnv* env, jclass, jlong h, jobject tiles, jobject out) {
     const int64_t n = covt_plan_num_streams(plan_of(h));
@@ -266,36 +275,19 @@ JNIEXPORT jlongArray JNICALL BFN(wkbColumns)(JNIEnv* env, jclass, jlong h) {
     const int64_t n = covt_plan_num_geometry_columns(plan_of(h));
     std::vector<covt_wkb_info> info((size_t)n);
     if (!check(env, covt_plan_wkb_columns(plan_of(h), info.data()))) return nullptr;
-    std::vector<jlong> rows((size_t)n * 7);
-    for (int64_t i = 0; i < n; ++i) {
-        const covt_wkb_info& w = info[(size_t)i];
-        const jlong r[7] = {w.tile, w.layer, w.n_features, w.desc_index, w.offsets_off, w.bytes_off, w.byte_cap};
-        std::copy(r, r + 7, rows.begin() + 7 * i);
-    }
-    jlongArray a = env->NewLongArray((jsize)rows.size());
-    env->SetLongArrayRegion(a, 0, (jsize)rows.size(), rows.data());
-    return a;
+    return long_rows<7>(env, info, [](const covt_wkb_info& w) -> std::array<jlong, 7> {
+        return {w.tile, w.layer, w.n_features, w.desc_index, w.offsets_off, w.bytes_off, w.byte_cap};
+    });
 }
 JNIEXPORT jlongArray JNICALL BFN(geometryWkb)(JNIEnv* env, jclass, jlong h, jobject tiles, jobject out) {
     const int64_t n = covt_plan_num_geometry_columns(plan_of(h));
-    // a heap buffer has no address, a short one would be overrun: IllegalArgumentException either way
-    uint8_t* dst = static_cast<uint8_t*>(env->GetDirectBufferAddress(out));
-    if (!dst || env->GetDirectBufferCapacity(out) < covt_plan_wkb_bytes(plan_of(h))) {
-        check(env, COVT_ERR_INVALID_ARG);
-        return nullptr;
-    }
+    uint8_t* dst = direct_out(env, out, covt_plan_wkb_bytes(plan_of(h)));
+    if (!dst) return nullptr;
     std::vector<covt_wkb_result> res((size_t)n);
     if (!check(env, covt_plan_wkb_host(plan_of(h), direct(env, tiles), (uint64_t)env->GetDirectBufferCapacity(tiles),
                                        dst, res.data())))
         return nullptr;
-    std::vector<jlong> rows((size_t)n * 2);
-    for (int64_t i = 0; i < n; ++i) {
-        rows[(size_t)(2 * i)] = res[(size_t)i].status;
-        rows[(size_t)(2 * i + 1)] = res[(size_t)i].n_bytes;
-    }
-    jlongArray a = env->NewLongArray((jsize)rows.size());
-    env->SetLongArrayRegion(a, 0, (jsize)rows.size(), rows.data());
-    return a;
+    return long_rows<2>(env, res, [](const covt_wkb_result& r) -> std::array<jlong, 2> { return {r.status, r.n_bytes}; });
 }
 
 // Geometry bounding boxes (include/covt.h "Geometry bounding boxes"): the bbox covering column beside the
@@ -305,38 +297,24 @@ JNIEXPORT jlongArray JNICALL BFN(bboxColumns)(JNIEnv* env, jclass, jlong h) {
     const int64_t n = covt_plan_num_geometry_columns(plan_of(h));
     std::vector<covt_bbox_info> info((size_t)n);
     if (!check(env, covt_plan_bbox_columns(plan_of(h), info.data()))) return nullptr;
-    std::vector<jlong> rows((size_t)n * 5);
-    for (int64_t i = 0; i < n; ++i) {
-        const covt_bbox_info& b = info[(size_t)i];
-        const jlong r[5] = {b.tile, b.layer, b.n_features, b.desc_index, b.off};
-        std::copy(r, r + 5, rows.begin() + 5 * i);
-    }
-    jlongArray a = env->NewLongArray((jsize)rows.size());
-    env->SetLongArrayRegion(a, 0, (jsize)rows.size(), rows.data());
-    return a;
+    return long_rows<5>(env, info, [](const covt_bbox_info& b) -> std::array<jlong, 5> {
+        return {b.tile, b.layer, b.n_features, b.desc_index, b.off};
+    });
 }
 JNIEXPORT jlongArray JNICALL BFN(geometryBbox)(JNIEnv* env, jclass, jlong h, jobject tiles, jobject out) {
     const int64_t n = covt_plan_num_geometry_columns(plan_of(h));
-    // a heap buffer has no address, a short one would be overrun: IllegalArgumentException either way
-    uint8_t* dst = static_cast<uint8_t*>(env->GetDirectBufferAddress(out));
-    if (!dst || env->GetDirectBufferCapacity(out) < covt_plan_bbox_bytes(plan_of(h))) {
-        check(env, COVT_ERR_INVALID_ARG);
-        return nullptr;
-    }
+    uint8_t* dst = direct_out(env, out, covt_plan_bbox_bytes(plan_of(h)));
+    if (!dst) return nullptr;
     std::vector<covt_bbox_result> res((size_t)n);
     if (!check(env, covt_plan_bbox_host(plan_of(h), direct(env, tiles), (uint64_t)env->GetDirectBufferCapacity(tiles),
                                         dst, res.data())))
         return nullptr;
-    std::vector<jlong> rows((size_t)n * 6);
-    for (int64_t i = 0; i < n; ++i) {
-        rows[(size_t)(6 * i)] = res[(size_t)i].status;
-        rows[(size_t)(6 * i + 1)] = res[(size_t)i].n_empty;
+    return long_rows<6>(env, res, [](const covt_bbox_result& r) {
+        std::array<jlong, 6> row{r.status, r.n_empty};
         // the extent's doubles as their bits (Double.longBitsToDouble on the Java side)
-        std::memcpy(&rows[(size_t)(6 * i + 2)], res[(size_t)i].extent, 32);
-    }
-    jlongArray a = env->NewLongArray((jsize)rows.size());
-    env->SetLongArrayRegion(a, 0, (jsize)rows.size(), rows.data());
-    return a;
+        std::memcpy(&row[2], r.extent, 32);
+        return row;
+    });
 }
 
 }  // extern "C"
