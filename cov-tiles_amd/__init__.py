@@ -159,6 +159,12 @@ BBOX_INFO_DTYPE = np.dtype([("tile", np.int32), ("layer", np.int32), ("n_feature
                             ("reserved", np.int32)])
 BBOX_TOO_LARGE = 0x1
 assert BBOX_DESC_DTYPE.itemsize == 16 and BBOX_RESULT_DTYPE.itemsize == 40 and BBOX_INFO_DTYPE.itemsize == 32
+# georeferenced geometry (include/covt.h "Georeferenced geometry")
+CRS_TILE, CRS_WEB_MERCATOR, CRS_CRS84 = 0, 1, 2
+GEO_IDENTITY, GEO_AFFINE, GEO_AFFINE_LAT = 0, 1, 2
+GEO_XFORM_DTYPE = np.dtype([("sx", np.float64), ("ox", np.float64), ("sy", np.float64), ("oy", np.float64),
+                            ("kind", np.int32), ("reserved", np.int32)])
+assert GEO_XFORM_DTYPE.itemsize == 40
 
 class PlanOptions(C.Structure):
     """covt_plan_options (include/covt.h): the plan-layout options.  ``PlanOptions()`` holds the
@@ -242,6 +248,14 @@ _SIGNATURES = {
     "covt_materialize_properties_device": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "covt_geometry_wkb_device": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "covt_geometry_bbox_device": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    # georeferenced geometry
+    "covt_geo_transform": (_int, [_i32, _i32, _i32, _i32, _i32, _vp]),
+    "covt_plan_geometry_extents": (_int, [_vp, _vp]),
+    "covt_plan_geo_transforms": (_int, [_vp, _i32, _vp, _vp, C.POINTER(C.c_uint32)]),
+    "covt_geometry_wkb_projected_device": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, C.c_uint32, _vp]),
+    "covt_geometry_bbox_projected_device": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, C.c_uint32, _vp]),
+    **_sig(_int, [_vp, _u8p, _u64, _i32, _vp, _vp, _vp], "covt_plan_wkb_projected_host",
+           "covt_plan_bbox_projected_host"),
     # device plan
     "covt_device_plan_create": (_int, [_vp, _u64, _vp, _vp, _i32, _i32, _i32, _vp, _vpp]),
     "covt_device_plan_create_opts": (_int, [_vp, _u64, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vpp]),
@@ -316,6 +330,22 @@ def device_count() -> int:
     n = C.c_int32(0)
     lib().covt_device_count(C.byref(n))
     return n.value
+
+
+def geo_transform(crs: int, z: int, x: int, y: int, extent: int) -> np.ndarray:
+    """covt_geo_transform: the transform of tile z/x/y for a layer of `extent` pixels a side, one
+    GEO_XFORM_DTYPE record (include/covt.h "Georeferenced geometry"); raises on an invalid argument."""
+    out = np.zeros(1, dtype=GEO_XFORM_DTYPE)
+    _raise(lib().covt_geo_transform(crs, z, x, y, extent, out.ctypes.data), "covt_geo_transform")
+    return out[0]
+
+
+def _zxy(tile_zxy, n_tiles: int) -> np.ndarray:
+    """z, x, y of every tile as a C-contiguous int32 [n_tiles, 3] array."""
+    a = np.ascontiguousarray(tile_zxy, dtype=np.int32).reshape(-1)
+    if a.size != 3 * n_tiles:
+        raise IllegalArgumentException("tile_zxy must hold z, x, y of each of the %d tiles" % n_tiles)
+    return a
 
 
 def _u8(buf) -> np.ndarray:
@@ -603,6 +633,10 @@ class Plan:
         if self.num_geometry_columns:
             L.covt_plan_geometry_columns(h, self.geom.ctypes.data)
             L.covt_plan_geometry_descs(h, self.gdescs.ctypes.data)
+        # the extent of each geometry column's layer (include/covt.h "Georeferenced geometry")
+        self.geometry_extents = np.zeros(self.num_geometry_columns, dtype=np.int32)
+        if self.num_geometry_columns:
+            L.covt_plan_geometry_extents(h, self.geometry_extents.ctypes.data)
         # geometry as WKB (include/covt.h "Geometry as WKB"): one column per geometry column
         self.wkb_bytes = int(L.covt_plan_wkb_bytes(h))
         self.wkb = np.zeros(self.num_geometry_columns, dtype=WKB_INFO_DTYPE)
@@ -673,25 +707,44 @@ class Plan:
         _raise(st, "covt_plan_decode_host")
         return out[:self.output_bytes], res[:self.num_streams]
 
-    def _product_host(self, kind: str, entry: str):
-        """One whole-plan entry point: (uint8 buffer of the product, its results in tile order)."""
+    def _product_host(self, kind: str, entry: str, crs=None, tile_zxy=None):
+        """One whole-plan entry point: (uint8 buffer of the product, its results in tile order).  With `crs`
+        the entry point's _projected_ twin, which takes the CRS and the tiles' addresses."""
         q = _PRODUCTS[kind]
         nbytes, n = getattr(self, q.nbytes), getattr(self, q.count)
         buf = np.zeros(max(nbytes, 1), dtype=np.uint8)
         res = np.zeros(max(n, 1), dtype=q.res_dtype)
-        _raise(getattr(lib(), entry)(self._h, _ptr(self.blob, C.c_uint8), self.blob.size, buf.ctypes.data,
-                                     res.ctypes.data), entry)
+        if crs is None:
+            _raise(getattr(lib(), entry)(self._h, _ptr(self.blob, C.c_uint8), self.blob.size, buf.ctypes.data,
+                                         res.ctypes.data), entry)
+        else:
+            entry = entry.replace("_host", "_projected_host")
+            zxy = _zxy(tile_zxy, self.n_tiles) if tile_zxy is not None else None
+            _raise(getattr(lib(), entry)(self._h, _ptr(self.blob, C.c_uint8), self.blob.size, crs,
+                                         zxy.ctypes.data if zxy is not None else None, buf.ctypes.data,
+                                         res.ctypes.data), entry)
         return buf[:nbytes], res[:n]
+
+    def geo_transforms(self, crs: int, tile_zxy=None):
+        """covt_plan_geo_transforms: (the transform table of this plan's geometry columns for `crs` in launch
+        order, GEO_XFORM_DTYPE; kinds, the OR of 1 << kind over it).  tile_zxy: z, x, y of every tile."""
+        table = np.zeros(self.num_geometry_columns, dtype=GEO_XFORM_DTYPE)
+        kinds = C.c_uint32(0)
+        zxy = _zxy(tile_zxy, self.n_tiles) if tile_zxy is not None else None
+        _raise(lib().covt_plan_geo_transforms(self._h, crs, zxy.ctypes.data if zxy is not None else None,
+                                              table.ctypes.data, C.byref(kinds)), "covt_plan_geo_transforms")
+        return table, int(kinds.value)
 
     def assemble_host(self):
         """H2D + decode + geometry assembly + D2H (covt_plan_assemble_host).
         Returns (uint8 assembly buffer, results[num_geometry_columns] in tile order)."""
         return self._product_host("geometry", "covt_plan_assemble_host")
 
-    def wkb_host(self):
-        """H2D + decode + geometry assembly + WKB serialization + D2H (covt_plan_wkb_host).
+    def wkb_host(self, crs=None, tile_zxy=None):
+        """H2D + decode + geometry assembly + WKB serialization + D2H (covt_plan_wkb_host; with `crs` and the
+        tiles' z, x, y covt_plan_wkb_projected_host: coordinates in that CRS instead of tile pixels).
         Returns (uint8 WKB buffer, results[num_geometry_columns] in tile order); see wkb_column."""
-        return self._product_host("wkb", "covt_plan_wkb_host")
+        return self._product_host("wkb", "covt_plan_wkb_host", crs, tile_zxy)
 
     def wkb_column(self, buf: np.ndarray, wres: np.ndarray, c: int) -> "WkbColumn":
         """Column c (tile order) of a WKB buffer -> WkbColumn (raises on its status)."""
@@ -700,10 +753,11 @@ class Plan:
         o, b = int(w["offsets_off"]), int(w["bytes_off"])
         return WkbColumn(buf[o:o + 4 * (int(w["n_features"]) + 1)].view(np.int32), buf[b:b + int(r["n_bytes"])])
 
-    def bbox_host(self):
-        """H2D + decode + geometry assembly + bounding boxes + D2H (covt_plan_bbox_host).
+    def bbox_host(self, crs=None, tile_zxy=None):
+        """H2D + decode + geometry assembly + bounding boxes + D2H (covt_plan_bbox_host; with `crs` and the
+        tiles' z, x, y covt_plan_bbox_projected_host: boxes in that CRS instead of tile pixels).
         Returns (uint8 bounding-box buffer, results[num_geometry_columns] in tile order); see bbox_column."""
-        return self._product_host("bbox", "covt_plan_bbox_host")
+        return self._product_host("bbox", "covt_plan_bbox_host", crs, tile_zxy)
 
     def bbox_column(self, buf: np.ndarray, bres: np.ndarray, c: int) -> "BboxColumn":
         """Column c (tile order) of a bounding-box buffer -> BboxColumn (raises on its status)."""
@@ -862,11 +916,35 @@ class DeviceBatch:
                                                    self.d_asm.data_ptr(), self.d_gres.data_ptr(),
                                                    _stream(stream, self.device)), "covt_assemble_geometry_device")
 
-    def wkb(self, stream=None):
+    def _xf(self, xf):
+        """The device copy of a (table, kinds) pair of Plan.geo_transforms, uploaded once and kept on the
+        batch (a pair with another table replaces it) -> (device pointer, kinds)."""
+        import torch
+
+        table, kinds = xf
+        table = np.ascontiguousarray(table, dtype=GEO_XFORM_DTYPE)
+        if table.size != self.plan.num_geometry_columns:
+            raise IllegalArgumentException("the transform table must hold one entry per geometry column")
+        kept = getattr(self, "_xf_host", None)
+        if kept is None or kept.tobytes() != table.tobytes():
+            raw = table.view(np.uint8).reshape(-1)
+            self.d_xf = torch.from_numpy(raw.copy()).to(self.device) if table.size else \
+                torch.zeros(GEO_XFORM_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+            self._xf_host = table.copy()
+        return self.d_xf.data_ptr(), int(kinds)
+
+    def wkb(self, stream=None, xf=None):
         """Enqueue the WKB serialization of every assembled geometry column (after assemble() on the
-        same stream)."""
+        same stream).  xf: the (table, kinds) pair of Plan.geo_transforms -> coordinates in its CRS."""
         self._buffers("geometry")
         self._buffers("wkb")
+        if xf is not None:
+            d_xf, kinds = self._xf(xf)
+            _raise(lib().covt_geometry_wkb_projected_device(
+                self.d_out.data_ptr(), self.d_gdesc.data_ptr(), self.d_asm.data_ptr(), self.d_gres.data_ptr(),
+                self.d_wdesc.data_ptr(), self.plan.num_geometry_columns, self.d_wkb.data_ptr(), self.d_wres.data_ptr(),
+                d_xf, kinds, _stream(stream, self.device)), "covt_geometry_wkb_projected_device")
+            return
         _raise(lib().covt_geometry_wkb_device(self.d_out.data_ptr(), self.d_gdesc.data_ptr(), self.d_asm.data_ptr(),
                                               self.d_gres.data_ptr(), self.d_wdesc.data_ptr(),
                                               self.plan.num_geometry_columns, self.d_wkb.data_ptr(),
@@ -877,11 +955,18 @@ class DeviceBatch:
         """(WKB bytes, WKB results in tile order) copied to the host (after wkb())."""
         return self._results("wkb")
 
-    def bbox(self, stream=None):
+    def bbox(self, stream=None, xf=None):
         """Enqueue the bounding boxes of every assembled geometry column (after assemble() on the same
-        stream)."""
+        stream).  xf: the (table, kinds) pair of Plan.geo_transforms -> boxes in its CRS."""
         self._buffers("geometry")
         self._buffers("bbox")
+        if xf is not None:
+            d_xf, kinds = self._xf(xf)
+            _raise(lib().covt_geometry_bbox_projected_device(
+                self.d_gdesc.data_ptr(), self.d_asm.data_ptr(), self.d_gres.data_ptr(), self.d_bdesc.data_ptr(),
+                self.plan.num_geometry_columns, self.d_bbox.data_ptr(), self.d_bres.data_ptr(), d_xf, kinds,
+                _stream(stream, self.device)), "covt_geometry_bbox_projected_device")
+            return
         _raise(lib().covt_geometry_bbox_device(self.d_gdesc.data_ptr(), self.d_asm.data_ptr(), self.d_gres.data_ptr(),
                                                self.d_bdesc.data_ptr(), self.plan.num_geometry_columns,
                                                self.d_bbox.data_ptr(), self.d_bres.data_ptr(),
@@ -1059,9 +1144,19 @@ class DevicePlan:
         """(WKB buffer, WKB results) on the device, sized for this plan's geometry columns."""
         return self._alloc("wkb")
 
-    def wkb(self, d_out, d_res, d_asm, d_gres, d_wkb, d_wres, stream=None):
-        """Enqueue the WKB serialization over this plan's descriptors (after assemble() on the same stream)."""
+    def wkb(self, d_out, d_res, d_asm, d_gres, d_wkb, d_wres, stream=None, d_xf=None, kinds: int = 0):
+        """Enqueue the WKB serialization over this plan's descriptors (after assemble() on the same stream).
+        d_xf: a device tensor holding one GEO_XFORM_DTYPE entry per geometry column in launch order (the
+        device plan does not read extents: the table comes from a host plan or the caller), kinds its promise."""
         self.geometry(stream)
+        if d_xf is not None:
+            L = lib()
+            _raise(L.covt_geometry_wkb_projected_device(
+                d_out.data_ptr(), L.covt_device_plan_geometry_descs_device(self._h), d_asm.data_ptr(),
+                d_gres.data_ptr(), L.covt_device_plan_wkb_descs_device(self._h), self.num_geometry_columns,
+                d_wkb.data_ptr(), d_wres.data_ptr(), d_xf.data_ptr(), kinds, _stream(stream, self.device)),
+                "covt_geometry_wkb_projected_device")
+            return
         _raise(lib().covt_device_plan_wkb(self._h, d_out.data_ptr(), d_res.data_ptr(), d_asm.data_ptr(),
                                           d_gres.data_ptr(), d_wkb.data_ptr(), d_wres.data_ptr(),
                                           _stream(stream, self.device)), "covt_device_plan_wkb")
@@ -1075,9 +1170,18 @@ class DevicePlan:
         """(bounding-box buffer, results) on the device, sized for this plan's geometry columns."""
         return self._alloc("bbox")
 
-    def bbox(self, d_asm, d_gres, d_bbox, d_bres, stream=None):
-        """Enqueue the bounding boxes over this plan's descriptors (after assemble() on the same stream)."""
+    def bbox(self, d_asm, d_gres, d_bbox, d_bres, stream=None, d_xf=None, kinds: int = 0):
+        """Enqueue the bounding boxes over this plan's descriptors (after assemble() on the same stream).
+        d_xf / kinds: as wkb()."""
         self.geometry(stream)
+        if d_xf is not None:
+            L = lib()
+            _raise(L.covt_geometry_bbox_projected_device(
+                L.covt_device_plan_geometry_descs_device(self._h), d_asm.data_ptr(), d_gres.data_ptr(),
+                L.covt_device_plan_bbox_descs_device(self._h), self.num_geometry_columns, d_bbox.data_ptr(),
+                d_bres.data_ptr(), d_xf.data_ptr(), kinds, _stream(stream, self.device)),
+                "covt_geometry_bbox_projected_device")
+            return
         _raise(lib().covt_device_plan_bbox(self._h, d_asm.data_ptr(), d_gres.data_ptr(), d_bbox.data_ptr(),
                                            d_bres.data_ptr(), _stream(stream, self.device)), "covt_device_plan_bbox")
 
@@ -1242,6 +1346,7 @@ class LayerColumns:
     properties: Optional[dict] = None
     wkb: Optional[WkbColumn] = None  # the layer's geometries, one WKB value per feature
     bbox: Optional[BboxColumn] = None  # their bounding boxes, the bbox covering column beside wkb
+    crs: int = CRS_TILE  # the CRS of wkb and bbox (geometry.vertexBuffer stays in tile pixels)
 
 
 _GEOM_FIELD = {GEOMETRY_TYPES: "geometryTypes", GEOMETRY_OFFSETS: "geometryOffsets", PART_OFFSETS: "partOffsets",
@@ -1269,21 +1374,27 @@ def split_layers(plan: Plan, out: np.ndarray, res: np.ndarray, tile: int = 0) ->
 class CovtParser:
     @staticmethod
     def decode_covt(covt_buffer: bytes, fmt: int = FORMAT_GENC, id_mode: int = ID_FORMAT,
-                    properties: bool = False) -> List[LayerColumns]:
+                    properties: bool = False, tile_id=None, crs: int = CRS_TILE) -> List[LayerColumns]:
         """CovtParser.decodeCovt (CovtParser.java:53-133) decoded on the GPU: Id + Geometry columns, and with
-        ``properties`` every property column as a PropertyColumn (LayerColumns.properties, by name)."""
+        ``properties`` every property column as a PropertyColumn (LayerColumns.properties, by name).
+        ``tile_id`` = (z, x, y) and ``crs`` give every layer's wkb / bbox in that CRS (LayerColumns.crs)."""
+        if crs != CRS_TILE and tile_id is None:
+            raise IllegalArgumentException("a CRS other than CRS_TILE needs the tile's (z, x, y)")
+        geo = (crs, [tile_id]) if crs != CRS_TILE else (None, None)
         plan = Plan.from_tiles([covt_buffer], fmt, id_mode, PLAN_PROPERTIES if properties else 0)
         _raise(int(plan.tile_status[0]), "decodeLayerMetadata")
         out, res = plan.decode_host()
         layers = split_layers(plan, out, res, 0)
+        for lc in layers:
+            lc.crs = crs
         if plan.num_geometry_columns:
-            wbuf, wres = plan.wkb_host()
+            wbuf, wres = plan.wkb_host(*geo)
             by_layer = {lc.layer: lc for lc in layers}
             for c in range(plan.num_geometry_columns):
                 lc = by_layer.get(int(plan.wkb["layer"][c]))
                 if lc is not None and int(wres["status"][c]) == OK:  # (a failed column keeps wkb = None)
                     lc.wkb = plan.wkb_column(wbuf, wres, c)
-            bbuf, bres = plan.bbox_host()
+            bbuf, bres = plan.bbox_host(*geo)
             for c in range(plan.num_geometry_columns):
                 lc = by_layer.get(int(plan.bbox["layer"][c]))
                 if lc is not None and int(bres["status"][c]) == OK:  # (a failed column keeps bbox = None)
@@ -1311,7 +1422,8 @@ _BUILD_SOURCES = (  # the Makefile's SRC, then its HDR, one to one
     ("csrc/covt_decode.hip", "csrc/covt_assemble.hip", "csrc/covt_props.hip", "csrc/covt_plan_device.hip",
      "csrc/covt_wkb.hip", "csrc/covt_bbox.hip", "csrc/covt_host.cpp")
     + ("../include/covt.h", "csrc/covt_internal.h", "csrc/covt_wave.h", "csrc/covt_walk.h", "csrc/covt_props_plan.h",
-       "csrc/covt_scratch.h", "csrc/covt_coop.h", "csrc/covt_wkb_plan.h", "csrc/covt_bbox_plan.h"))
+       "csrc/covt_scratch.h", "csrc/covt_coop.h", "csrc/covt_wkb_plan.h", "csrc/covt_bbox_plan.h",
+       "csrc/covt_geo_plan.h"))
 
 
 def source_build_id() -> str:

@@ -24,6 +24,11 @@
 //      int32 atomic min / max / add per wave and value folds them into the result that launch 1 initialised
 //      (order-independent, so still deterministic).
 //   3. finish: the int32 extent -> float64, NaN where the column has no coordinate or failed.
+//
+// The projected pass (include/covt.h "Georeferenced geometry") is the same three launches instantiated on
+// the transform: boxes stay int32 up to the stores, and each of the four store sites (a chunk's features, the
+// feature the wave finishes, the one the workgroup finishes, the extent) maps the box's two ends per axis and
+// takes their fmin / fmax (bb_map).  GEO 0 is the plain pass and compiles to what it was.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -32,6 +37,7 @@
 #include "covt.h"
 #include "covt_bbox_plan.h"
 #include "covt_coop.h"
+#include "covt_geo_plan.h"
 #include "covt_wave.h"
 
 namespace covt {
@@ -192,13 +198,50 @@ struct __attribute__((aligned(16))) BboxSmem {
     i32x4 red[kBboxWaves];
 };
 
-__device__ __forceinline__ void bb_put(const BboxCol& c, int32_t f, i32x4 box, bool any) {
+// The column's transform as the kernels hold it (uniform): nothing for the plain pass (GEO 0), the affine
+// coefficients for a launch without latitudes (GEO 1: a tile-local column maps by 0 + 1 * p), and with them
+// whether y goes on through the Gudermannian (GEO 2).
+template <int GEO>
+struct BboxGeo {
+    covt_geo_xform t;
+    bool lat;
+};
+template <>
+struct BboxGeo<0> {};
+template <int GEO>
+__device__ __forceinline__ BboxGeo<GEO> bb_geo(const covt_geo_xform* __restrict__ xf, int64_t col) {
+    BboxGeo<GEO> g;
+    if constexpr (GEO != 0) {
+        g.t = xf[col];
+        g.lat = GEO == 2 && g.t.kind == COVT_GEO_AFFINE_LAT;
+        if (g.t.kind == COVT_GEO_IDENTITY) g.t = geo_identity_affine();
+    }
+    return g;
+}
+// an int32 box as its four float64 (xmin, ymin, xmax, ymax): per axis the fmin / fmax of the two transformed
+// ends, so a map that flips an axis (sy < 0) needs no sign test
+template <int GEO>
+__device__ __forceinline__ void bb_map(const BboxGeo<GEO>& geo, i32x4 box, double (&o)[4]) {
+    o[0] = (double)box.x, o[1] = (double)box.y, o[2] = (double)box.z, o[3] = (double)box.w;
+    if constexpr (GEO != 0) {
+        const double x0 = geo_x(geo.t, o[0]), x1 = geo_x(geo.t, o[2]);
+        double y0 = geo_y<false>(geo.t, o[1]), y1 = geo_y<false>(geo.t, o[3]);
+        if constexpr (GEO == 2)
+            if (geo.lat) y0 = geo_lat(y0), y1 = geo_lat(y1);  // (uniform over the column)
+        o[0] = fmin(x0, x1), o[1] = fmin(y0, y1), o[2] = fmax(x0, x1), o[3] = fmax(y0, y1);
+    }
+}
+
+template <int GEO>
+__device__ __forceinline__ void bb_put(const BboxCol& c, const BboxGeo<GEO>& geo, int32_t f, i32x4 box, bool any) {
     const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    double o[4];
+    bb_map<GEO>(geo, box, o);
     // (the four arrays of covt_bbox_plan.h; byte offsets are multiples of 8)
-    c.out[bbox_array_off(c.n, 0) / 8 + f] = any ? (double)box.x : nan;
-    c.out[bbox_array_off(c.n, 1) / 8 + f] = any ? (double)box.y : nan;
-    c.out[bbox_array_off(c.n, 2) / 8 + f] = any ? (double)box.z : nan;
-    c.out[bbox_array_off(c.n, 3) / 8 + f] = any ? (double)box.w : nan;
+    c.out[bbox_array_off(c.n, 0) / 8 + f] = any ? o[0] : nan;
+    c.out[bbox_array_off(c.n, 1) / 8 + f] = any ? o[1] : nan;
+    c.out[bbox_array_off(c.n, 2) / 8 + f] = any ? o[2] : nan;
+    c.out[bbox_array_off(c.n, 3) / 8 + f] = any ? o[3] : nan;
 }
 
 // the column's status before any work: the assembly's, then the layout's
@@ -212,14 +255,20 @@ __device__ __forceinline__ int32_t bbox_precheck(const covt_geom_desc& gd, const
 }
 
 // ---- 1. init ------------------------------------------------------------------------------------------
+// (GEO: a projected launch; then the kind of the column's transform under the caller's promise `kinds`)
+template <bool GEO>
 __global__ __launch_bounds__(256) void bbox_init_kernel(const covt_geom_desc* __restrict__ gdescs,
                                                         const covt_geom_result* __restrict__ gres,
                                                         const covt_bbox_desc* __restrict__ bdescs, int64_t n_cols,
-                                                        covt_bbox_result* __restrict__ bres) {
+                                                        covt_bbox_result* __restrict__ bres,
+                                                        const covt_geo_xform* __restrict__ xf, uint32_t kinds) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= n_cols) return;
     int32_t* r = (int32_t*)(bres + c);
-    r[0] = bbox_precheck(gdescs[c], gres[c], bdescs[c]);
+    int32_t st = bbox_precheck(gdescs[c], gres[c], bdescs[c]);
+    if constexpr (GEO)
+        if (st == COVT_OK) st = geo_kind_status(xf[c].kind, kinds);
+    r[0] = st;
     r[1] = 0;
     r[2] = INT32_MAX;  // the int32 extent, folded by the boxes kernel's atomics
     r[3] = INT32_MAX;
@@ -230,12 +279,14 @@ __global__ __launch_bounds__(256) void bbox_init_kernel(const covt_geom_desc* __
 
 // ---- 2. boxes -----------------------------------------------------------------------------------------
 // blockIdx.x: the column; each of its gridDim.y * kBboxWaves waves takes a run of consecutive chunks
+template <int GEO>
 __global__ __launch_bounds__(64 * kBboxWaves) void bbox_kernel(const covt_geom_desc* __restrict__ gdescs,
                                                                const uint8_t* __restrict__ asmb,
                                                                const covt_geom_result* __restrict__ gres,
                                                                const covt_bbox_desc* __restrict__ bdescs,
                                                                uint8_t* __restrict__ bbox,
-                                                               covt_bbox_result* __restrict__ bres) {
+                                                               covt_bbox_result* __restrict__ bres,
+                                                               const covt_geo_xform* __restrict__ xf) {
     __shared__ BboxSmem sm;
     const int64_t col = blockIdx.x;
     int32_t* const rcol = (int32_t*)(bres + col);
@@ -243,6 +294,7 @@ __global__ __launch_bounds__(64 * kBboxWaves) void bbox_kernel(const covt_geom_d
     const covt_geom_desc gd = gdescs[col];
     const covt_bbox_desc bd = bdescs[col];
     const covt_geom_result gr = gres[col];
+    const BboxGeo<GEO> geo = bb_geo<GEO>(xf, col);
     BboxCol c;
     c.geo = (const int32_t*)(asmb + gd.out_off[0]);
     c.part = (const int32_t*)(asmb + gd.out_off[1]);
@@ -331,7 +383,7 @@ __global__ __launch_bounds__(64 * kBboxWaves) void bbox_kernel(const covt_geom_d
                     const uint32_t at = (uint32_t)(e - 1 - a);
                     const bool any = e > s && process && at < (uint32_t)kBboxChunk;
                     const i32x4 box = any ? res[at] : bb_id();
-                    bb_put(c, f, box, any);
+                    bb_put<GEO>(c, geo, f, box, any);
                     ext = bb_join(ext, box);
                     n_empty += any ? 0 : 1;
                 }
@@ -354,7 +406,7 @@ __global__ __launch_bounds__(64 * kBboxWaves) void bbox_kernel(const covt_geom_d
                     for (int32_t i = B + 2 * l; i < e; i += 128) box = bb_take2(c, box, i, e);
                     box = bb_join(carry, bb_wave_join(box));
                     if (l == 0) {
-                        bb_put(c, fc, box, true);
+                        bb_put<GEO>(c, geo, fc, box, true);
                         ext = bb_join(ext, box);
                     }
                 }
@@ -382,7 +434,7 @@ __global__ __launch_bounds__(64 * kBboxWaves) void bbox_kernel(const covt_geom_d
             box = sm.wide_box[k];
 #pragma unroll
             for (int i = 0; i < kBboxWaves; ++i) box = bb_join(box, sm.red[i]);
-            bb_put(c, f, box, true);
+            bb_put<GEO>(c, geo, f, box, true);
             ext = bb_join(ext, box);
         }
         __syncthreads();
@@ -402,18 +454,38 @@ __global__ __launch_bounds__(64 * kBboxWaves) void bbox_kernel(const covt_geom_d
 }
 
 // ---- 3. finish ----------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void bbox_finish_kernel(int64_t n_cols, covt_bbox_result* __restrict__ bres) {
+template <int GEO>
+__global__ __launch_bounds__(256) void bbox_finish_kernel(int64_t n_cols, covt_bbox_result* __restrict__ bres,
+                                                          const covt_geo_xform* __restrict__ xf) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= n_cols) return;
     const int32_t* r = (const int32_t*)(bres + c);
     const int32_t x0 = r[2], y0 = r[3], x1 = r[4], y1 = r[5];
     const bool any = r[0] == COVT_OK && x0 <= x1;
     const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    double o[4];
+    bb_map<GEO>(bb_geo<GEO>(xf, c), i32x4{x0, y0, x1, y1}, o);  // (a column that failed: not stored)
     double* e = bres[c].extent;
-    e[0] = any ? (double)x0 : nan;
-    e[1] = any ? (double)y0 : nan;
-    e[2] = any ? (double)x1 : nan;
-    e[3] = any ? (double)y1 : nan;
+    e[0] = any ? o[0] : nan;
+    e[1] = any ? o[1] : nan;
+    e[2] = any ? o[2] : nan;
+    e[3] = any ? o[3] : nan;
+}
+
+// GEO 0: the plain pass; 1: transforms without a latitude; 2: with
+template <int GEO>
+int bbox_launch(const covt_geom_desc* d_gdesc, const uint8_t* d_asm, const covt_geom_result* d_gres,
+                const covt_bbox_desc* d_bdesc, int64_t n_columns, uint8_t* d_bbox, covt_bbox_result* d_bres,
+                const covt_geo_xform* d_xf, uint32_t kinds, hipStream_t s) {
+    const unsigned cols256 = (unsigned)((n_columns + 255) / 256);
+    hipLaunchKernelGGL(bbox_init_kernel<GEO != 0>, dim3(cols256), dim3(256), 0, s, d_gdesc, d_gres, d_bdesc, n_columns,
+                       d_bres, d_xf, kinds);
+    // small batches: up to 64 workgroups per column (a 72k-coordinate column: a chunk or two per wave)
+    const int64_t gy = std::max<int64_t>(1, std::min<int64_t>(kBboxMaxBlocksY, kBboxSmallBlocks / n_columns));
+    hipLaunchKernelGGL(bbox_kernel<GEO>, dim3((unsigned)n_columns, (unsigned)gy), dim3(64 * kBboxWaves), 0, s, d_gdesc,
+                       d_asm, d_gres, d_bdesc, d_bbox, d_bres, d_xf);
+    hipLaunchKernelGGL(bbox_finish_kernel<GEO>, dim3(cols256), dim3(256), 0, s, n_columns, d_bres, d_xf);
+    return hipGetLastError() == hipSuccess ? COVT_OK : COVT_ERR_DEVICE;
 }
 
 }  // namespace covt
@@ -425,13 +497,22 @@ extern "C" int covt_geometry_bbox_device(const covt_geom_desc* d_gdesc, const ui
         return COVT_ERR_INVALID_ARG;
     if (n_columns == 0) return COVT_OK;
     if (n_columns > 0x7fffffff) return COVT_ERR_INVALID_ARG;
+    return covt::bbox_launch<0>(d_gdesc, d_asm, d_gres, d_bdesc, n_columns, d_bbox, d_bres, nullptr, 0u,
+                                (hipStream_t)hip_stream);
+}
+
+extern "C" int covt_geometry_bbox_projected_device(const covt_geom_desc* d_gdesc, const uint8_t* d_asm,
+                                                   const covt_geom_result* d_gres, const covt_bbox_desc* d_bdesc,
+                                                   int64_t n_columns, uint8_t* d_bbox, covt_bbox_result* d_bres,
+                                                   const covt_geo_xform* d_xf, uint32_t kinds, void* hip_stream) {
+    if (n_columns < 0 || (kinds & ~7u) ||
+        (n_columns && (!d_gdesc || !d_asm || !d_gres || !d_bdesc || !d_bbox || !d_bres || !d_xf)))
+        return COVT_ERR_INVALID_ARG;
+    if (n_columns == 0) return COVT_OK;
+    if (n_columns > 0x7fffffff) return COVT_ERR_INVALID_ARG;
     hipStream_t s = (hipStream_t)hip_stream;
-    const unsigned cols256 = (unsigned)((n_columns + 255) / 256);
-    hipLaunchKernelGGL(covt::bbox_init_kernel, dim3(cols256), dim3(256), 0, s, d_gdesc, d_gres, d_bdesc, n_columns, d_bres);
-    // small batches: up to 64 workgroups per column (a 72k-coordinate column: a chunk or two per wave)
-    const int64_t gy = std::max<int64_t>(1, std::min<int64_t>(covt::kBboxMaxBlocksY, covt::kBboxSmallBlocks / n_columns));
-    hipLaunchKernelGGL(covt::bbox_kernel, dim3((unsigned)n_columns, (unsigned)gy), dim3(64 * covt::kBboxWaves), 0, s,
-                       d_gdesc, d_asm, d_gres, d_bdesc, d_bbox, d_bres);
-    hipLaunchKernelGGL(covt::bbox_finish_kernel, dim3(cols256), dim3(256), 0, s, n_columns, d_bres);
-    return hipGetLastError() == hipSuccess ? COVT_OK : COVT_ERR_DEVICE;
+    // the latitude code (device sinh, atan and their registers) only where the caller's table may need it
+    return (kinds & (1u << COVT_GEO_AFFINE_LAT))
+               ? covt::bbox_launch<2>(d_gdesc, d_asm, d_gres, d_bdesc, n_columns, d_bbox, d_bres, d_xf, kinds, s)
+               : covt::bbox_launch<1>(d_gdesc, d_asm, d_gres, d_bdesc, n_columns, d_bbox, d_bres, d_xf, kinds, s);
 }

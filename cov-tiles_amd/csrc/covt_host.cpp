@@ -25,6 +25,7 @@
 #include "covt_props_plan.h"
 #include "covt_wkb_plan.h"
 #include "covt_bbox_plan.h"
+#include "covt_geo_plan.h"
 
 namespace {
 
@@ -66,8 +67,10 @@ int genc_stream_type(const uint8_t* s, uint64_t n) {
 }
 
 // Gen C container (all committed fixtures), SURVEY.md Appendix A.1.  Geometry streams are laid
-// out in StreamType order whatever their metadata order; other columns in metadata order.
-int walk_genc(const uint8_t* t, size_t len, std::vector<RawStream>& out, std::vector<PropRaw>* props) {
+// out in StreamType order whatever their metadata order; other columns in metadata order.  `extents` gets
+// every layer's extent as its header states it (-1 where it does not fit int32), one entry per layer.
+int walk_genc(const uint8_t* t, size_t len, std::vector<RawStream>& out, std::vector<PropRaw>* props,
+              std::vector<int32_t>& extents) {
     size_t o = 0;
     uint64_t version, nlayers;
     if (!rd_uv(t, len, o, version) || !rd_uv(t, len, o, nlayers)) return COVT_ERR_TRUNCATED;
@@ -82,6 +85,7 @@ int walk_genc(const uint8_t* t, size_t len, std::vector<RawStream>& out, std::ve
         if (!rd_uv(t, len, o, extent) || !rd_uv(t, len, o, nfeat) || !rd_uv(t, len, o, ncols))
             return COVT_ERR_TRUNCATED;
         if (ncols > 4096) return COVT_ERR_BAD_HEADER;
+        extents.push_back(extent > 0x7fffffffull ? -1 : (int32_t)extent);
         cols.assign(ncols, CM{});
         for (auto& c : cols) {
             uint64_t cn, ns;
@@ -195,7 +199,8 @@ int32_t byte_rle_length(const uint8_t* t, size_t len, size_t o, int32_t n) {
 
 // Gen D container: CovtParser.decodeLayerMetadata (CovtParser.java:574-652) + the column loop
 // of decodeCovt (:56-85).  Streams of a column follow TreeMap<StreamType> order.
-int walk_gend(const uint8_t* t, size_t len, std::vector<RawStream>& out, std::vector<PropRaw>* props) {
+int walk_gend(const uint8_t* t, size_t len, std::vector<RawStream>& out, std::vector<PropRaw>* props,
+              std::vector<int32_t>& extents) {
     size_t o = 0;
     int32_t layer = 0;
     struct SM { int enc; int32_t nv, bl; bool have; };
@@ -213,6 +218,7 @@ int walk_gend(const uint8_t* t, size_t len, std::vector<RawStream>& out, std::ve
         if (!rd_j4(t, len, o, extent) || !rd_j4(t, len, o, nfeat) || !rd_j4(t, len, o, ncols))
             return COVT_ERR_TRUNCATED;
         if (ncols < 0 || ncols > 4096) return COVT_ERR_BAD_HEADER;
+        extents.push_back(extent);
         cols.assign((size_t)ncols, CM{});
         for (int32_t ci = 0; ci < ncols; ++ci) {
             CM& c = cols[(size_t)ci];
@@ -786,6 +792,7 @@ struct covt_plan {
     int32_t format = COVT_FORMAT_GENC;
     std::vector<covt_geom_info> ginfo;   // geometry columns, tile order
     std::vector<covt_geom_desc> gdescs;  // launch order: largest first
+    std::vector<int32_t> gextent;        // the extent of each geometry column's layer, tile order
     int64_t asm_bytes = 0;
     std::vector<covt_wkb_info> winfo;    // WKB columns, tile order (one per geometry column)
     std::vector<covt_wkb_desc> wdescs;   // launch order (that of gdescs)
@@ -982,8 +989,12 @@ void plan_bbox(covt_plan* p) {
 // present stream was decoded (data encodings, non-dictionary strings).
 // Stream / property records of a range of tiles, built by one host thread with output offsets and
 // stream indices local to the range; covt_plan_create_ex rebases and concatenates the parts.
+struct LayerExtent {
+    int32_t tile, layer, extent;
+};
 struct PlanPart {
     std::vector<covt_stream_info> info;
+    std::vector<LayerExtent> extents;  // every (tile, layer) of the range, in tile and layer order
     std::vector<covt_prop_info> pinfo;
     std::vector<uint16_t> pflags;
     int64_t out_off = 0, in_bytes = 0, out_payload = 0, vertices = 0;
@@ -1397,7 +1408,8 @@ int covt_plan_create_opts(const uint8_t* bytes, const uint64_t* tile_offsets, co
         int32_t t0 = 0, t1 = 0;
         std::vector<RawStream> rs;
         std::vector<PropRaw> props;
-        std::vector<int32_t> rs_end, props_end;  // per tile of the chunk: end index in rs / props
+        std::vector<int32_t> ext;                // every layer's extent, tile after tile
+        std::vector<int32_t> rs_end, props_end, ext_end;  // per tile of the chunk: end index in rs / props / ext
     };
     const int32_t n_thr = (int32_t)std::max<int64_t>(
         1, std::min<int64_t>({o.plan_threads > 0 ? (int64_t)o.plan_threads
@@ -1410,15 +1422,17 @@ int covt_plan_create_opts(const uint8_t* bytes, const uint64_t* tile_offsets, co
         c->props_end.reserve((size_t)(c->t1 - c->t0));
         for (int32_t t = c->t0; t < c->t1; ++t) {
             const uint8_t* tile = bytes + tile_offsets[t];
-            const size_t r0 = c->rs.size(), q0 = c->props.size();
+            const size_t r0 = c->rs.size(), q0 = c->props.size(), e0 = c->ext.size();
             std::vector<PropRaw>* pp = (flags & COVT_PLAN_PROPERTIES) ? &c->props : nullptr;
-            const int st = format == COVT_FORMAT_GENC ? walk_genc(tile, (size_t)tile_sizes[t], c->rs, pp)
-                                                      : walk_gend(tile, (size_t)tile_sizes[t], c->rs, pp);
+            const int st = format == COVT_FORMAT_GENC ? walk_genc(tile, (size_t)tile_sizes[t], c->rs, pp, c->ext)
+                                                      : walk_gend(tile, (size_t)tile_sizes[t], c->rs, pp, c->ext);
             p->tile_status[(size_t)t] = st;
             if (st) {  // a failed tile contributes nothing
                 c->rs.resize(r0);
                 c->props.resize(q0);
+                c->ext.resize(e0);
             }
+            c->ext_end.push_back((int32_t)c->ext.size());
             c->rs_end.push_back((int32_t)c->rs.size());
             c->props_end.push_back((int32_t)c->props.size());
         }
@@ -1442,9 +1456,11 @@ int covt_plan_create_opts(const uint8_t* bytes, const uint64_t* tile_offsets, co
             const Chunk& c = chunks[(size_t)k];
             PlanPart& pp = parts[(size_t)k];
             pp.info.reserve(c.rs.size());
-            int32_t r = 0, q = 0;
+            int32_t r = 0, q = 0, e = 0;
             for (int32_t t = c.t0; t < c.t1; ++t) {
                 const int32_t re = c.rs_end[(size_t)(t - c.t0)], qe = c.props_end[(size_t)(t - c.t0)];
+                for (int32_t e0 = e, ee = c.ext_end[(size_t)(t - c.t0)]; e < ee; ++e)
+                    pp.extents.push_back(LayerExtent{t, e - e0, c.ext[(size_t)e]});
                 for (; r < re; ++r) {
                     const RawStream& s = c.rs[(size_t)r];
                     int op, elem;
@@ -1687,6 +1703,16 @@ int covt_plan_create_opts(const uint8_t* bytes, const uint64_t* tile_offsets, co
         }
     });
     plan_geometry(p, n_thr);
+    {
+        // the extent of every geometry column's layer: both lists are in (tile, layer) order, the layers'
+        // holding every layer and the columns' those with a geometry column
+        p->gextent.assign(p->ginfo.size(), 0);
+        size_t c = 0;
+        for (const PlanPart& pp : parts)
+            for (const LayerExtent& le : pp.extents)
+                if (c < p->ginfo.size() && p->ginfo[c].tile == le.tile && p->ginfo[c].layer == le.layer)
+                    p->gextent[c++] = le.extent;
+    }
     plan_wkb(p);
     plan_bbox(p);
     plan_property_layout(p);
@@ -2072,6 +2098,90 @@ int covt_plan_bbox_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_byt
                              [](const PlanDev& d, const covt_bbox_desc* bdesc, int64_t n, uint8_t* buf,
                                 covt_bbox_result* bres, hipStream_t s) {
                                  return covt_geometry_bbox_device(d.gdesc, d.asm_buf, d.gres, bdesc, n, buf, bres, s);
+                             });
+}
+
+// ---- georeferenced geometry (include/covt.h "Georeferenced geometry") ----
+int covt_geo_transform(int32_t crs, int32_t z, int32_t x, int32_t y, int32_t extent, covt_geo_xform* out) {
+    if (!out) return COVT_ERR_INVALID_ARG;
+    return geo_transform(crs, z, x, y, extent, *out);
+}
+
+int covt_plan_geometry_extents(const covt_plan* p, int32_t* out) { return copy_records(p ? &p->gextent : nullptr, out); }
+
+int covt_plan_geo_transforms(const covt_plan* p, int32_t crs, const int32_t* tile_zxy, covt_geo_xform* out,
+                             uint32_t* kinds) {
+    if (!p || !kinds || (!out && !p->ginfo.empty())) return COVT_ERR_INVALID_ARG;
+    if (crs != COVT_CRS_TILE && crs != COVT_CRS_WEB_MERCATOR && crs != COVT_CRS_CRS84) return COVT_ERR_INVALID_ARG;
+    if (!tile_zxy && crs != COVT_CRS_TILE && !p->ginfo.empty()) return COVT_ERR_INVALID_ARG;
+    uint32_t k = 0;
+    for (size_t c = 0; c < p->ginfo.size(); ++c) {
+        const covt_geom_info& g = p->ginfo[c];
+        covt_geo_xform t;
+        const int32_t* a = tile_zxy ? tile_zxy + 3 * (size_t)g.tile : nullptr;
+        const int st = a ? geo_transform(crs, a[0], a[1], a[2], p->gextent[c], t) : geo_transform(crs, 0, 0, 0, 1, t);
+        if (st) return st;
+        out[(size_t)g.desc_index] = t;
+        k |= 1u << t.kind;
+    }
+    *kinds = k;
+    return COVT_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// a plan's transform table for `crs` on the host and, once a product's launch has uploaded it, on the device
+struct GeoTable {
+    std::vector<covt_geo_xform> xf;
+    uint32_t kinds = 0;
+    DevMem dev;
+    int make(const covt_plan* p, int32_t crs, const int32_t* tile_zxy) {
+        xf.resize(p->ginfo.size());
+        return covt_plan_geo_transforms(p, crs, tile_zxy, xf.data(), &kinds);
+    }
+    // one more small H2D in the product's launch closure (the stream orders it before the kernels)
+    int upload(hipStream_t s) {
+        if (hipMalloc(&dev.p, std::max<size_t>(xf.size(), 1) * sizeof(covt_geo_xform)) != hipSuccess) return COVT_ERR_DEVICE;
+        if (!xf.empty() && hipMemcpyAsync(dev.p, xf.data(), xf.size() * sizeof(covt_geo_xform), hipMemcpyHostToDevice, s) !=
+                               hipSuccess)
+            return COVT_ERR_DEVICE;
+        return COVT_OK;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+// decode, assembly, WKB serialization in `crs`
+int covt_plan_wkb_projected_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, int32_t crs,
+                                 const int32_t* tile_zxy, uint8_t* host_wkb, covt_wkb_result* host_wres) {
+    if (!p) return COVT_ERR_INVALID_ARG;
+    GeoTable g;  // (outlives the pipeline's synchronize)
+    if (const int st = g.make(p, crs, tile_zxy)) return st;
+    return plan_product_host(p, bytes, n_bytes, p->winfo, p->wdescs, p->wkb_bytes, host_wkb, host_wres, true,
+                             [&g](const PlanDev& d, const covt_wkb_desc* wdesc, int64_t n, uint8_t* buf,
+                                  covt_wkb_result* wres, hipStream_t s) {
+                                 if (const int st = g.upload(s)) return st;
+                                 return covt_geometry_wkb_projected_device(d.out, d.gdesc, d.asm_buf, d.gres, wdesc, n, buf,
+                                                                           wres, g.dev.as<covt_geo_xform>(), g.kinds, s);
+                             });
+}
+
+// decode, assembly, bounding boxes in `crs`
+int covt_plan_bbox_projected_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, int32_t crs,
+                                  const int32_t* tile_zxy, uint8_t* host_bbox, covt_bbox_result* host_bres) {
+    if (!p) return COVT_ERR_INVALID_ARG;
+    GeoTable g;
+    if (const int st = g.make(p, crs, tile_zxy)) return st;
+    return plan_product_host(p, bytes, n_bytes, p->binfo, p->bdescs, p->bbox_bytes, host_bbox, host_bres, true,
+                             [&g](const PlanDev& d, const covt_bbox_desc* bdesc, int64_t n, uint8_t* buf,
+                                  covt_bbox_result* bres, hipStream_t s) {
+                                 if (const int st = g.upload(s)) return st;
+                                 return covt_geometry_bbox_projected_device(d.gdesc, d.asm_buf, d.gres, bdesc, n, buf, bres,
+                                                                            g.dev.as<covt_geo_xform>(), g.kinds, s);
                              });
 }
 

@@ -22,6 +22,11 @@
 // and the 4-byte counts go through vector types of alignment 1: gfx950 runs with unaligned access
 // mode on, and the compiler keeps them as single global_store_dwordx4 / _dword instructions (DESIGN.md
 // section 8e has the ISA check and why the LDS-staged alternative was not built).
+//
+// The projected pass (include/covt.h "Georeferenced geometry") is the same launch instantiated on the
+// transform: a coordinate is converted at one place (wkb_write_coords), and there the column's map is applied
+// to the two doubles; byte counts and addresses do not change.  GEO 0 is the plain pass and compiles to what
+// it was; GEO 1 carries no latitude code.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -29,6 +34,7 @@
 
 #include "covt.h"
 #include "covt_coop.h"
+#include "covt_geo_plan.h"
 #include "covt_wave.h"
 #include "covt_wkb_plan.h"
 
@@ -99,13 +105,15 @@ __device__ __forceinline__ int32_t wkb_precheck(const covt_geom_desc& gd, const 
 template <int NW, int IPL>
 __device__ void wkb_scan_column(const uint8_t* __restrict__ dec, const covt_geom_desc& gd,
                                 const uint8_t* __restrict__ asmb, const covt_geom_result& gr, const covt_wkb_desc& wd,
-                                uint8_t* __restrict__ wkb, covt_wkb_result& res, AsmSmemT<NW, IPL>& sm) {
+                                uint8_t* __restrict__ wkb, covt_wkb_result& res, AsmSmemT<NW, IPL>& sm,
+                                int32_t geo_status = COVT_OK) {
     constexpr int K = Coop<NW, IPL>::K;
     const int l = Coop<NW, IPL>::tid();
     auto ioff = [&](int k) { return NW == 1 ? 64 * k + l : IPL * l + k; };
     res.reserved = 0;
     res.n_bytes = 0;
     res.status = wkb_precheck(gd, gr, wd);
+    if (res.status == COVT_OK) res.status = geo_status;  // (a projected launch: the column's transform kind)
     if (res.status != COVT_OK) return;
     const WkbCol c = wkb_col(dec, gd, asmb, wd, wkb);
     int buf = 0;
@@ -133,11 +141,20 @@ __device__ void wkb_scan_column(const uint8_t* __restrict__ dec, const covt_geom
     res.n_bytes = (int64_t)B;
 }
 
+// the status of column c's transform in a projected launch (GEO; xf, kinds: its table and promise)
+template <bool GEO>
+__device__ __forceinline__ int32_t wkb_geo_status(const covt_geo_xform* __restrict__ xf, uint32_t kinds, int64_t c) {
+    if constexpr (GEO) return geo_kind_status(xf[c].kind, kinds);
+    return COVT_OK;
+}
+
 // one wave per column
+template <bool GEO>
 __global__ __launch_bounds__(64 * kWkbWriteWaves) void wkb_scan_kernel(
     const uint8_t* __restrict__ dec, const covt_geom_desc* __restrict__ gdescs, const uint8_t* __restrict__ asmb,
     const covt_geom_result* __restrict__ gres, const covt_wkb_desc* __restrict__ wdescs, int64_t n_cols,
-    uint8_t* __restrict__ wkb, covt_wkb_result* __restrict__ wres) {
+    uint8_t* __restrict__ wkb, covt_wkb_result* __restrict__ wres, const covt_geo_xform* __restrict__ xf,
+    uint32_t kinds) {
     __shared__ AsmSmemT<1, kWkbIpl> smem[kWkbWriteWaves];
     const int w = threadIdx.x >> 6;
     const int64_t c = uni64((int64_t)blockIdx.x * kWkbWriteWaves + w);
@@ -146,15 +163,17 @@ __global__ __launch_bounds__(64 * kWkbWriteWaves) void wkb_scan_kernel(
     const covt_geom_result gr = gres[c];
     const covt_wkb_desc wd = wdescs[c];
     covt_wkb_result r;
-    wkb_scan_column<1, kWkbIpl>(dec, gd, asmb, gr, wd, wkb, r, smem[w]);
+    wkb_scan_column<1, kWkbIpl>(dec, gd, asmb, gr, wd, wkb, r, smem[w], wkb_geo_status<GEO>(xf, kinds, c));
     if (lane_id() == 0) wres[c] = r;
 }
 
 // a workgroup per column (small batches: a long column's scan in steps of 4096 features)
+template <bool GEO>
 __global__ __launch_bounds__(64 * kWkbCoopWaves) void wkb_scan_coop_kernel(
     const uint8_t* __restrict__ dec, const covt_geom_desc* __restrict__ gdescs, const uint8_t* __restrict__ asmb,
     const covt_geom_result* __restrict__ gres, const covt_wkb_desc* __restrict__ wdescs, int64_t n_cols,
-    uint8_t* __restrict__ wkb, covt_wkb_result* __restrict__ wres) {
+    uint8_t* __restrict__ wkb, covt_wkb_result* __restrict__ wres, const covt_geo_xform* __restrict__ xf,
+    uint32_t kinds) {
     __shared__ AsmSmemT<kWkbCoopWaves, kWkbIpl> smem;
     const int64_t c = blockIdx.x;
     if (c >= n_cols) return;
@@ -162,7 +181,7 @@ __global__ __launch_bounds__(64 * kWkbCoopWaves) void wkb_scan_coop_kernel(
     const covt_geom_result gr = gres[c];
     const covt_wkb_desc wd = wdescs[c];
     covt_wkb_result r;
-    wkb_scan_column<kWkbCoopWaves, kWkbIpl>(dec, gd, asmb, gr, wd, wkb, r, smem);
+    wkb_scan_column<kWkbCoopWaves, kWkbIpl>(dec, gd, asmb, gr, wd, wkb, r, smem, wkb_geo_status<GEO>(xf, kinds, c));
     if (threadIdx.x == 0) wres[c] = r;
 }
 
@@ -256,10 +275,36 @@ __device__ __forceinline__ void wkb_put_header(uint8_t* p, uint32_t code, uint32
     wkb_put_u32(p + 5, count);
 }
 
+// The column's transform as the write kernel holds it (uniform): nothing for the plain pass (GEO 0), the
+// affine coefficients for a launch without latitudes (GEO 1: a tile-local column maps by 0 + 1 * p), and
+// with them whether y goes on through the Gudermannian (GEO 2).
+template <int GEO>
+struct WkbGeo {
+    covt_geo_xform t;
+    bool lat;
+};
+template <>
+struct WkbGeo<0> {};
+template <int GEO>
+__device__ __forceinline__ WkbGeo<GEO> wkb_geo(const covt_geo_xform* __restrict__ xf, int64_t col) {
+    WkbGeo<GEO> g;
+    if constexpr (GEO != 0) {
+        g.t = xf[col];
+        g.lat = GEO == 2 && g.t.kind == COVT_GEO_AFFINE_LAT;
+        if (g.t.kind == COVT_GEO_IDENTITY) g.t = geo_identity_affine();
+    }
+    return g;
+}
+
+// The latitude as a call, not inlined: inlined into the unrolled item loop the four items' sinh / atan
+// temporaries are live at once (140 VGPRs, 3 waves a SIMD against the plain pass's 68 and 7).
+__device__ __attribute__((noinline)) double wkb_lat(double t) { return geo_lat(t); }
+
 // one wave, one chunk of coordinates [v0, v0 + L), 1 <= L <= kWkbChunk; the levels' windows start at or
 // before the chunk's first owners
+template <int GEO>
 __device__ __forceinline__ void wkb_write_coords(const WkbCol& c, WkbLevel& lr, WkbLevel& lp, WkbLevel& lf,
-                                                 int32_t v0, int32_t L, int64_t nb) {
+                                                 int32_t v0, int32_t L, int64_t nb, const WkbGeo<GEO>& geo) {
     const int l = lane_id();
     uint64_t xy[kWkbIpl];
 #pragma unroll
@@ -309,6 +354,12 @@ __device__ __forceinline__ void wkb_write_coords(const WkbCol& c, WkbLevel& lr, 
             f64x2u d;
             d.x = (double)(int32_t)(uint32_t)xy[k];
             d.y = (double)(int32_t)(uint32_t)(xy[k] >> 32);
+            if constexpr (GEO != 0) {
+                d.x = geo_x(geo.t, d.x);
+                d.y = geo_y<false>(geo.t, d.y);
+                if constexpr (GEO == 2)
+                    if (geo.lat) d.y = wkb_lat(d.y);  // (uniform over the column)
+            }
             __builtin_nontemporal_store(d, (gw_f64x2u*)(c.bytes + pos));
         }
     }
@@ -422,10 +473,11 @@ __device__ __forceinline__ void wkb_share(int32_t items, int32_t wave, int32_t w
 
 // blockIdx.x: the column; each of its gridDim.y * kWkbWriteWaves waves takes a run of consecutive chunks of
 // every item kind
+template <int GEO>
 __global__ __launch_bounds__(64 * kWkbWriteWaves) void wkb_write_kernel(
     const uint8_t* __restrict__ dec, const covt_geom_desc* __restrict__ gdescs, const uint8_t* __restrict__ asmb,
     const covt_geom_result* __restrict__ gres, const covt_wkb_desc* __restrict__ wdescs,
-    uint8_t* __restrict__ wkb, const covt_wkb_result* __restrict__ wres) {
+    uint8_t* __restrict__ wkb, const covt_wkb_result* __restrict__ wres, const covt_geo_xform* __restrict__ xf) {
     __shared__ WkbSmem smem[kWkbWriteWaves];
     const int64_t col = blockIdx.x;
     const covt_wkb_result wr = wres[col];  // (the size scan's, earlier on this stream)
@@ -436,6 +488,7 @@ __global__ __launch_bounds__(64 * kWkbWriteWaves) void wkb_write_kernel(
     const WkbCol c = wkb_col(dec, gd, asmb, wd, wkb);
     const int32_t P = gr.num_parts, R = gr.num_rings, V = gr.num_coords;
     const int64_t nb = wr.n_bytes;
+    const WkbGeo<GEO> geo = wkb_geo<GEO>(xf, col);
     const int w = threadIdx.x >> 6;
     const int32_t wave = uni((int32_t)(blockIdx.y * kWkbWriteWaves + w));
     const int32_t waves = (int32_t)(gridDim.y * kWkbWriteWaves);
@@ -449,7 +502,7 @@ __global__ __launch_bounds__(64 * kWkbWriteWaves) void wkb_write_kernel(
         lp.seek(lr.ws);
         lf.seek(lp.ws);
         for (int32_t j = cb; j < ce; ++j)
-            wkb_write_coords(c, lr, lp, lf, j * kWkbChunk, min(kWkbChunk, V - j * kWkbChunk), nb);
+            wkb_write_coords<GEO>(c, lr, lp, lf, j * kWkbChunk, min(kWkbChunk, V - j * kWkbChunk), nb, geo);
     }
     wkb_share(R, wave, waves, cb, ce);
     if (cb < ce) {
@@ -469,6 +522,28 @@ __global__ __launch_bounds__(64 * kWkbWriteWaves) void wkb_write_kernel(
         wkb_write_features(c, j * kWkbChunk, min(kWkbChunk, c.n - j * kWkbChunk), nb);
 }
 
+// GEO 0: the plain pass; 1: transforms without a latitude; 2: with
+template <int GEO>
+int wkb_launch(const uint8_t* d_decoded, const covt_geom_desc* d_gdesc, const uint8_t* d_asm,
+               const covt_geom_result* d_gres, const covt_wkb_desc* d_wdesc, int64_t n_columns, uint8_t* d_wkb,
+               covt_wkb_result* d_wres, const covt_geo_xform* d_xf, uint32_t kinds, hipStream_t s) {
+    constexpr bool G = GEO != 0;
+    const bool small = n_columns <= kWkbCoopMaxColumns;
+    if (small) {
+        hipLaunchKernelGGL(wkb_scan_coop_kernel<G>, dim3((unsigned)n_columns), dim3(64 * kWkbCoopWaves), 0, s, d_decoded,
+                           d_gdesc, d_asm, d_gres, d_wdesc, n_columns, d_wkb, d_wres, d_xf, kinds);
+    } else {
+        const int64_t blocks = (n_columns + kWkbWriteWaves - 1) / kWkbWriteWaves;
+        hipLaunchKernelGGL(wkb_scan_kernel<G>, dim3((unsigned)blocks), dim3(64 * kWkbWriteWaves), 0, s, d_decoded,
+                           d_gdesc, d_asm, d_gres, d_wdesc, n_columns, d_wkb, d_wres, d_xf, kinds);
+    }
+    // small batches: up to 64 workgroups per column (a 72k-coordinate column: a chunk or two per wave)
+    const int64_t gy = small ? std::max<int64_t>(1, std::min<int64_t>(64, kWkbSmallBlocks / n_columns)) : 1;
+    hipLaunchKernelGGL(wkb_write_kernel<GEO>, dim3((unsigned)n_columns, (unsigned)gy), dim3(64 * kWkbWriteWaves), 0, s,
+                       d_decoded, d_gdesc, d_asm, d_gres, d_wdesc, d_wkb, d_wres, d_xf);
+    return hipGetLastError() == hipSuccess ? COVT_OK : COVT_ERR_DEVICE;
+}
+
 }  // namespace covt
 
 extern "C" int covt_geometry_wkb_device(const uint8_t* d_decoded, const covt_geom_desc* d_gdesc, const uint8_t* d_asm,
@@ -478,19 +553,23 @@ extern "C" int covt_geometry_wkb_device(const uint8_t* d_decoded, const covt_geo
         return COVT_ERR_INVALID_ARG;
     if (n_columns == 0) return COVT_OK;
     if (n_columns > 0x7fffffff) return COVT_ERR_INVALID_ARG;
+    return covt::wkb_launch<0>(d_decoded, d_gdesc, d_asm, d_gres, d_wdesc, n_columns, d_wkb, d_wres, nullptr, 0u,
+                               (hipStream_t)hip_stream);
+}
+
+extern "C" int covt_geometry_wkb_projected_device(const uint8_t* d_decoded, const covt_geom_desc* d_gdesc,
+                                                  const uint8_t* d_asm, const covt_geom_result* d_gres,
+                                                  const covt_wkb_desc* d_wdesc, int64_t n_columns, uint8_t* d_wkb,
+                                                  covt_wkb_result* d_wres, const covt_geo_xform* d_xf, uint32_t kinds,
+                                                  void* hip_stream) {
+    if (n_columns < 0 || (kinds & ~7u) ||
+        (n_columns && (!d_decoded || !d_gdesc || !d_asm || !d_gres || !d_wdesc || !d_wkb || !d_wres || !d_xf)))
+        return COVT_ERR_INVALID_ARG;
+    if (n_columns == 0) return COVT_OK;
+    if (n_columns > 0x7fffffff) return COVT_ERR_INVALID_ARG;
     hipStream_t s = (hipStream_t)hip_stream;
-    const bool small = n_columns <= covt::kWkbCoopMaxColumns;
-    if (small) {
-        hipLaunchKernelGGL(covt::wkb_scan_coop_kernel, dim3((unsigned)n_columns), dim3(64 * covt::kWkbCoopWaves), 0, s,
-                           d_decoded, d_gdesc, d_asm, d_gres, d_wdesc, n_columns, d_wkb, d_wres);
-    } else {
-        const int64_t blocks = (n_columns + covt::kWkbWriteWaves - 1) / covt::kWkbWriteWaves;
-        hipLaunchKernelGGL(covt::wkb_scan_kernel, dim3((unsigned)blocks), dim3(64 * covt::kWkbWriteWaves), 0, s,
-                           d_decoded, d_gdesc, d_asm, d_gres, d_wdesc, n_columns, d_wkb, d_wres);
-    }
-    // small batches: up to 64 workgroups per column (a 72k-coordinate column: a chunk or two per wave)
-    const int64_t gy = small ? std::max<int64_t>(1, std::min<int64_t>(64, covt::kWkbSmallBlocks / n_columns)) : 1;
-    hipLaunchKernelGGL(covt::wkb_write_kernel, dim3((unsigned)n_columns, (unsigned)gy), dim3(64 * covt::kWkbWriteWaves),
-                       0, s, d_decoded, d_gdesc, d_asm, d_gres, d_wdesc, d_wkb, d_wres);
-    return hipGetLastError() == hipSuccess ? COVT_OK : COVT_ERR_DEVICE;
+    // the latitude code (device sinh, atan and their registers) only where the caller's table may need it
+    return (kinds & (1u << COVT_GEO_AFFINE_LAT))
+               ? covt::wkb_launch<2>(d_decoded, d_gdesc, d_asm, d_gres, d_wdesc, n_columns, d_wkb, d_wres, d_xf, kinds, s)
+               : covt::wkb_launch<1>(d_decoded, d_gdesc, d_asm, d_gres, d_wdesc, n_columns, d_wkb, d_wres, d_xf, kinds, s);
 }

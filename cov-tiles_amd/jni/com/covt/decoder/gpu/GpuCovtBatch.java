@@ -38,6 +38,9 @@ public final class GpuCovtBatch implements AutoCloseable {
     /** Fields per row of {@link #geometryBbox}: status, n_empty, then the column's extent xmin, ymin,
      * xmax, ymax as the bits of their doubles (Double.longBitsToDouble; NaN without a coordinate). */
     public static final int BBOX_RESULT_FIELDS = 6;
+    /** Coordinate reference systems of the georeferenced overloads (include/covt.h "Georeferenced
+     * geometry"): tile pixels (the plain methods' output), EPSG:3857 metres, OGC:CRS84 lon/lat degrees. */
+    public static final int CRS_TILE = 0, CRS_WEB_MERCATOR = 1, CRS_CRS84 = 2;
 
     private final ByteBuffer tiles;
     private final int numTiles;
@@ -108,6 +111,23 @@ public final class GpuCovtBatch implements AutoCloseable {
         return geometryWkb(live(), tiles, out);
     }
 
+    /** {@link #geometryWkb(ByteBuffer)} with every coordinate in {@code crs} instead of tile pixels: the
+     * container does not hold a tile's address, so {@code tileZxy} gives z, x, y of every tile of the batch
+     * (3 per tile, tile order).  Byte counts, offsets and the returned rows are those of the plain method;
+     * Web Mercator coordinates and longitudes are bit-exact IEEE-754 evaluations of the header's formulas.
+     * A wrong array length or an invalid address throws IllegalArgumentException. */
+    public long[] geometryWkb(ByteBuffer out, int crs, int[] tileZxy) {
+        if (!out.isDirect() || out.capacity() < wkbBytes()) throw new IllegalArgumentException("output buffer");
+        return geometryWkbProjected(live(), tiles, out, crs, addresses(tileZxy), numTiles);
+    }
+
+    private long[] addresses(int[] tileZxy) {
+        if (tileZxy == null || tileZxy.length != 3 * numTiles) throw new IllegalArgumentException("tileZxy: z, x, y per tile");
+        long[] a = new long[tileZxy.length];
+        for (int i = 0; i < a.length; i++) a[i] = tileZxy[i];
+        return a;
+    }
+
     /** Bytes {@link #geometryBbox} writes. */
     public long bboxBytes() { return bboxBytes(live()); }
 
@@ -121,6 +141,13 @@ public final class GpuCovtBatch implements AutoCloseable {
     public long[] geometryBbox(ByteBuffer out) {
         if (!out.isDirect() || out.capacity() < bboxBytes()) throw new IllegalArgumentException("output buffer");
         return geometryBbox(live(), tiles, out);
+    }
+
+    /** {@link #geometryBbox(ByteBuffer)} in {@code crs} (see {@link #geometryWkb(ByteBuffer, int, int[])}): the
+     * boxes and the extents of the returned rows are in that CRS, so the column prunes across tiles. */
+    public long[] geometryBbox(ByteBuffer out, int crs, int[] tileZxy) {
+        if (!out.isDirect() || out.capacity() < bboxBytes()) throw new IllegalArgumentException("output buffer");
+        return geometryBboxProjected(live(), tiles, out, crs, addresses(tileZxy), numTiles);
     }
 
     @Override
@@ -151,4 +178,9 @@ public final class GpuCovtBatch implements AutoCloseable {
     private static native long bboxBytes(long plan);
     private static native long[] bboxColumns(long plan);
     private static native long[] geometryBbox(long plan, ByteBuffer tiles, ByteBuffer out);
+    // (names of their own: an overloaded native method would need the signature-mangled symbol names)
+    private static native long[] geometryWkbProjected(long plan, ByteBuffer tiles, ByteBuffer out, int crs,
+                                                      long[] tileZxy, int numTiles);
+    private static native long[] geometryBboxProjected(long plan, ByteBuffer tiles, ByteBuffer out, int crs,
+                                                       long[] tileZxy, int numTiles);
 }

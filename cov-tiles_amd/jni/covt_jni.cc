@@ -318,3 +318,59 @@ JNIEXPORT jlongArray JNICALL BFN(geometryBbox)(JNIEnv* env, jclass, jlong h, job
 }
 
 }  // extern "C"
+
+namespace {
+
+// z, x, y of the batch's n_tiles tiles from the long[] the Java overloads pass (their int[] widened); false
+// with an IllegalArgumentException pending when the length is not 3 * n_tiles or a value is no int32 (the
+// address itself is checked by the library)
+bool tile_addresses(JNIEnv* env, jlongArray zxy, jint n_tiles, std::vector<int32_t>& out) {
+    if (!zxy || n_tiles < 0 || env->GetArrayLength(zxy) != 3 * (jsize)n_tiles) return check(env, COVT_ERR_INVALID_ARG);
+    std::vector<jlong> v(3 * (size_t)n_tiles);
+    env->GetLongArrayRegion(zxy, 0, (jsize)v.size(), v.data());
+    out.resize(v.size());
+    for (size_t i = 0; i < v.size(); ++i) {
+        if (v[i] < INT32_MIN || v[i] > INT32_MAX) return check(env, COVT_ERR_INVALID_ARG);
+        out[i] = (int32_t)v[i];
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Georeferenced geometry (include/covt.h "Georeferenced geometry"): geometryWkb / geometryBbox in a CRS, the
+// tiles' z, x, y supplied by the caller
+JNIEXPORT jlongArray JNICALL BFN(geometryWkbProjected)(JNIEnv* env, jclass, jlong h, jobject tiles, jobject out,
+                                                       jint crs, jlongArray zxy, jint n_tiles) {
+    const int64_t n = covt_plan_num_geometry_columns(plan_of(h));
+    uint8_t* dst = direct_out(env, out, covt_plan_wkb_bytes(plan_of(h)));
+    std::vector<int32_t> addr;
+    if (!dst || !tile_addresses(env, zxy, n_tiles, addr)) return nullptr;
+    std::vector<covt_wkb_result> res((size_t)n);
+    if (!check(env, covt_plan_wkb_projected_host(plan_of(h), direct(env, tiles),
+                                                 (uint64_t)env->GetDirectBufferCapacity(tiles), crs, addr.data(), dst,
+                                                 res.data())))
+        return nullptr;
+    return long_rows<2>(env, res, [](const covt_wkb_result& r) -> std::array<jlong, 2> { return {r.status, r.n_bytes}; });
+}
+JNIEXPORT jlongArray JNICALL BFN(geometryBboxProjected)(JNIEnv* env, jclass, jlong h, jobject tiles, jobject out,
+                                                        jint crs, jlongArray zxy, jint n_tiles) {
+    const int64_t n = covt_plan_num_geometry_columns(plan_of(h));
+    uint8_t* dst = direct_out(env, out, covt_plan_bbox_bytes(plan_of(h)));
+    std::vector<int32_t> addr;
+    if (!dst || !tile_addresses(env, zxy, n_tiles, addr)) return nullptr;
+    std::vector<covt_bbox_result> res((size_t)n);
+    if (!check(env, covt_plan_bbox_projected_host(plan_of(h), direct(env, tiles),
+                                                  (uint64_t)env->GetDirectBufferCapacity(tiles), crs, addr.data(), dst,
+                                                  res.data())))
+        return nullptr;
+    return long_rows<6>(env, res, [](const covt_bbox_result& r) {
+        std::array<jlong, 6> row{r.status, r.n_empty};
+        std::memcpy(&row[2], r.extent, 32);
+        return row;
+    });
+}
+
+}  // extern "C"

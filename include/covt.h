@@ -460,7 +460,8 @@ int covt_plan_wkb_host(const covt_plan* plan, const uint8_t* bytes, uint64_t n_b
  * ring_offsets[part_offsets[geometry_offsets[f + 1]]]), the ring-closing vertex included, whatever the
  * geometry type.  A feature with no coordinate (a MULTI* of 0 parts, a line of 0 vertices, a polygon whose
  * rings are all empty) gets the quiet NaN 0x7FF8000000000000 in all four arrays, as shapely.bounds reports
- * an empty geometry.  Coordinates are tile-local, the space of coords and of the WKB values.
+ * an empty geometry.  Coordinates are tile-local, the space of coords and of the WKB values (both in a CRS:
+ * "Georeferenced geometry" below).
  * Per column a covt_bbox_result: extent = xmin, ymin, xmax, ymax over all the column's coordinates (the
  * layer's bbox in GeoParquet file metadata, row-group statistics; all NaN without a coordinate), n_empty
  * the number of NaN rows.
@@ -506,6 +507,88 @@ int covt_geometry_bbox_device(const covt_geom_desc* d_gdesc, const uint8_t* d_as
  * host_bbox: covt_plan_bbox_bytes bytes; host_bres: one result per column in tile order. */
 int covt_plan_bbox_host(const covt_plan* plan, const uint8_t* bytes, uint64_t n_bytes, uint8_t* host_bbox,
                         covt_bbox_result* host_bres);
+
+/* ---------------------------------------------------------------------------
+ * Georeferenced geometry: the WKB values and the bounding boxes in a coordinate reference system instead of
+ * tile pixels, so the columns of many tiles share one table, the bbox column prunes across tiles and a
+ * GeoParquet writer can name a CRS.  A column's transform maps its assembled int32 pixel (px, py), converted
+ * exactly to float64, where the plain passes convert it:
+ *
+ *   COVT_GEO_IDENTITY    X = px, Y = py                                   (the plain passes' output)
+ *   COVT_GEO_AFFINE      X = ox + sx*px, Y = oy + sy*py
+ *   COVT_GEO_AFFINE_LAT  X = ox + sx*px, t = oy + sy*py, Y = atan(sinh(t)) * (180/PI)
+ *
+ * The container does not hold a tile's address, so the caller supplies z/x/y; the layer's extent E comes
+ * from its header (covt_plan_geometry_extents).  With W = 20037508.342789244 (pi * 6378137), PI the float64
+ * nearest pi and n = 2^z as a double, covt_geo_transform gives
+ *
+ *   crs                     kind        sx               ox                   sy                oy
+ *   COVT_CRS_TILE           IDENTITY    0                0                    0                 0
+ *   COVT_CRS_WEB_MERCATOR   AFFINE      (2*W) / (n*E)    (2*W) * (x/n) - W    -sx               W - (2*W) * (y/n)
+ *   COVT_CRS_CRS84          AFFINE_LAT  360.0 / (n*E)    360.0 * (x/n) - 180  -(2*PI) / (n*E)   PI - (2*PI) * (y/n)
+ *
+ * (EPSG:3857 metres; OGC:CRS84 longitude / latitude degrees, GeoParquet's default CRS.)  Everything is
+ * evaluated in float64 in the order written, one rounding per operation and no fused multiply-add, on the
+ * host and on the device.  So the table, every AFFINE coordinate and every longitude are bit-exact against
+ * the same expressions in any IEEE-754 float64 arithmetic (numpy, Java); only the latitude goes through the
+ * device's sinh and atan and agrees with another libm to a few ulp (tests hold it to 1e-9 degrees).
+ * Valid input: 0 <= z <= 30, 0 <= x, y < 2^z, extent >= 1, a known crs; anything else is
+ * COVT_ERR_INVALID_ARG.
+ *
+ * A projected WKB value has the byte count and offsets of the plain one (no SRID is written); only its
+ * coordinate doubles differ.  A projected box is, per axis, fmin / fmax of the transformed ends of the int32
+ * box (sy < 0 flips y, no sign test), the column extent likewise; a feature or column without a coordinate
+ * stays the quiet NaN 0x7FF8000000000000.
+ * Statuses of the projected passes: those of the plain passes, and a column whose kind is above
+ * COVT_GEO_AFFINE_LAT or whose bit is missing from `kinds` gets COVT_ERR_INVALID_ARG (n_bytes 0 / n_empty 0,
+ * extent NaN, slice untouched).  `kinds` with a bit above bit 2 makes the call return COVT_ERR_INVALID_ARG.
+ * ------------------------------------------------------------------------- */
+#define COVT_CRS_TILE 0         /* identity: tile-local, the plain passes' output */
+#define COVT_CRS_WEB_MERCATOR 1 /* EPSG:3857, metres */
+#define COVT_CRS_CRS84 2        /* OGC:CRS84 lon/lat degrees, GeoParquet's default CRS */
+
+#define COVT_GEO_IDENTITY 0
+#define COVT_GEO_AFFINE 1     /* X = ox + sx*px, Y = oy + sy*py */
+#define COVT_GEO_AFFINE_LAT 2 /* X as AFFINE; t = oy + sy*py; Y = atan(sinh(t)) * (180/pi) */
+
+/* One column's transform (40 bytes); a table of them is parallel to covt_geom_desc (launch order). */
+typedef struct covt_geo_xform {
+    double sx, ox, sy, oy;
+    int32_t kind, reserved;
+} covt_geo_xform;
+
+/* The transform of tile z/x/y for a layer of `extent` pixels a side (pure host arithmetic). */
+int covt_geo_transform(int32_t crs, int32_t z, int32_t x, int32_t y, int32_t extent, covt_geo_xform* out);
+
+/* The extent of every geometry column's layer as its header states it, in tile order
+ * (num_geometry_columns values; -1 where the header's value does not fit int32). */
+int covt_plan_geometry_extents(const covt_plan* plan, int32_t* out);
+
+/* The transform table of a plan for `crs`: tile_zxy holds z, x, y of every tile of the plan (3 per tile);
+ * out gets num_geometry_columns entries in launch order (column c's at its covt_geom_info.desc_index), *kinds
+ * the OR of 1u << kind over them.  An invalid address of a tile with a geometry column, or an extent < 1 on
+ * one, is COVT_ERR_INVALID_ARG. */
+int covt_plan_geo_transforms(const covt_plan* plan, int32_t crs, const int32_t* tile_zxy, covt_geo_xform* out,
+                             uint32_t* kinds);
+
+/* covt_geometry_wkb_device / covt_geometry_bbox_device with a transform per column: d_xf has n_columns
+ * entries in d_gdesc order, `kinds` is the caller's promise of the kinds in it (the OR of 1u << kind), which
+ * lets the launch leave the latitude code out when bit 2 is clear.  Asynchronous, no scratch, capturable. */
+int covt_geometry_wkb_projected_device(const uint8_t* d_decoded, const covt_geom_desc* d_gdesc, const uint8_t* d_asm,
+                                       const covt_geom_result* d_gres, const covt_wkb_desc* d_wdesc,
+                                       int64_t n_columns, uint8_t* d_wkb, covt_wkb_result* d_wres,
+                                       const covt_geo_xform* d_xf, uint32_t kinds, void* hip_stream);
+int covt_geometry_bbox_projected_device(const covt_geom_desc* d_gdesc, const uint8_t* d_asm,
+                                        const covt_geom_result* d_gres, const covt_bbox_desc* d_bdesc,
+                                        int64_t n_columns, uint8_t* d_bbox, covt_bbox_result* d_bres,
+                                        const covt_geo_xform* d_xf, uint32_t kinds, void* hip_stream);
+
+/* covt_plan_wkb_host / covt_plan_bbox_host in `crs` (tile_zxy as covt_plan_geo_transforms; it may be null
+ * for COVT_CRS_TILE).  Buffers and records are those of the plain entry points. */
+int covt_plan_wkb_projected_host(const covt_plan* plan, const uint8_t* bytes, uint64_t n_bytes, int32_t crs,
+                                 const int32_t* tile_zxy, uint8_t* host_wkb, covt_wkb_result* host_wres);
+int covt_plan_bbox_projected_host(const covt_plan* plan, const uint8_t* bytes, uint64_t n_bytes, int32_t crs,
+                                  const int32_t* tile_zxy, uint8_t* host_bbox, covt_bbox_result* host_bres);
 
 /* ---------------------------------------------------------------------------
  * Property columns: the GPU replacement for
