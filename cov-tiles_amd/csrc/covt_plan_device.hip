@@ -19,6 +19,8 @@
 //                   scatter instead measured slower: the scatter's rounds expose the gather's latency)
 // The split rule is the host plan's (split plans: split_mark .. fpf_states_walk below); property columns
 // (COVT_PLAN_PROPERTIES) add a property walk per tile and their stream entries after the tile's own.
+// On the host the plan is built by PlanBuild, one member function per stage; every arena (tile, property,
+// stream, descriptor, geometry) is declared once with ArenaLayout (covt_arena.h) and bound after its allocation.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -30,6 +32,7 @@
 
 #include "covt.h"
 #include "covt_internal.h"
+#include "covt_arena.h"
 #include "covt_walk.h"
 #include "covt_props_plan.h"
 #include "covt_wkb_plan.h"
@@ -2790,42 +2793,463 @@ __global__ void product_records(const covt_geom_info* __restrict__ ginfo, int64_
     desc[g.desc_index] = d;
 }
 
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+// a HIP (or hipcub) call of a function that returns a plan status
+#define HIP_TRY(x) do { if ((x) != hipSuccess) return COVT_ERR_DEVICE; } while (0)
+
+// hipFreeAsync(q, s) at scope exit: stream-ordered, after the work on s that uses q (q = nullptr: keep it)
+struct StreamFree {
+    void* q = nullptr;
+    hipStream_t s = nullptr;
+    ~StreamFree() { if (q) (void)hipFreeAsync(q, s); }
+};
+
+// the calling thread on device dev until scope exit (ok: it is there)
+struct DeviceGuard {
+    int cur = 0, dev;
+    bool ok;
+    explicit DeviceGuard(int d) : dev(d) {
+        ok = hipGetDevice(&cur) == hipSuccess && (cur == dev || hipSetDevice(dev) == hipSuccess);
+    }
+    ~DeviceGuard() { if (ok && cur != dev) (void)hipSetDevice(cur); }
+};
 
 // One product of covt_device_plan_geometry.  Its slice of the geometry arena: records | descriptors | column
 // bytes | column offsets.  Over the nc finished geometry records (tile order): the bytes kernel, their scan, the
 // records kernel and the copy of the total to *total, which holds after the caller's synchronize.
 template <class P>
-size_t product_arena_bytes(size_t m) {
-    return up256(m * sizeof(typename P::Info)) + up256(m * sizeof(typename P::Desc)) + 2 * up256((m + 1) * 8);
-}
+struct ProductSlice {
+    ArenaSlot<typename P::Info> info;
+    ArenaSlot<typename P::Desc> desc;
+    ArenaSlot<int64_t> bytes, off;
+    ProductSlice(ArenaLayout& a, size_t m)
+        : info(a.take<typename P::Info>(m)), desc(a.take<typename P::Desc>(m)), bytes(a.take<int64_t>(m + 1)),
+          off(a.take<int64_t>(m + 1)) {}
+};
 template <class P>
-int plan_product(uint8_t* slice, size_t m, int64_t nc, const covt_geom_info* ginfo, void* scan_mem, size_t scan_tmp,
-                 hipStream_t s, typename P::Info*& info, typename P::Desc*& desc, int64_t* total) {
-    info = (typename P::Info*)slice;
-    desc = (typename P::Desc*)(slice + up256(m * sizeof(typename P::Info)));
-    int64_t* bytes = (int64_t*)((uint8_t*)desc + up256(m * sizeof(typename P::Desc)));
-    int64_t* off = (int64_t*)((uint8_t*)bytes + up256((m + 1) * 8));
-    if (hipMemsetAsync(bytes, 0, (m + 1) * 8, s) != hipSuccess) return COVT_ERR_DEVICE;
+int plan_product(const ProductSlice<P>& slice, void* arena, size_t m, int64_t nc, const covt_geom_info* ginfo,
+                 void* scan_mem, size_t scan_tmp, hipStream_t s, typename P::Info*& info, typename P::Desc*& desc,
+                 int64_t* total) {
+    info = slice.info.at(arena);
+    desc = slice.desc.at(arena);
+    int64_t *bytes = slice.bytes.at(arena), *off = slice.off.at(arena);
+    HIP_TRY(hipMemsetAsync(bytes, 0, (m + 1) * 8, s));
     if (nc <= 0) return COVT_OK;
     const int cb = (int)((nc + 255) / 256);
     product_col_bytes<P><<<cb, 256, 0, s>>>(ginfo, nc, bytes);
-    if (hipGetLastError() != hipSuccess) return COVT_ERR_DEVICE;
-    if (hipcub::DeviceScan::ExclusiveSum(scan_mem, scan_tmp, bytes, off, (int)(nc + 1), s) != hipSuccess)
-        return COVT_ERR_DEVICE;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_mem, scan_tmp, bytes, off, (int)(nc + 1), s));
     product_records<P><<<cb, 256, 0, s>>>(ginfo, nc, off, info, desc);
-    if (hipGetLastError() != hipSuccess) return COVT_ERR_DEVICE;
-    return hipMemcpyAsync(total, off + nc, 8, hipMemcpyDeviceToHost, s) == hipSuccess ? COVT_OK : COVT_ERR_DEVICE;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(total, off + nc, 8, hipMemcpyDeviceToHost, s));
+    return COVT_OK;
 }
 
 // the *_copy entry points: n records and n descriptors of a built plan to the host (either may be null)
 template <class Info, class Desc>
 int copy_to_host(int64_t n, Info* infos, const Info* d_infos, Desc* descs, const Desc* d_descs) {
     if (n <= 0) return COVT_OK;
-    if (infos && hipMemcpy(infos, d_infos, (size_t)n * sizeof(Info), hipMemcpyDeviceToHost) != hipSuccess)
-        return COVT_ERR_DEVICE;
-    if (descs && hipMemcpy(descs, d_descs, (size_t)n * sizeof(Desc), hipMemcpyDeviceToHost) != hipSuccess)
-        return COVT_ERR_DEVICE;
+    if (infos) HIP_TRY(hipMemcpy(infos, d_infos, (size_t)n * sizeof(Info), hipMemcpyDeviceToHost));
+    if (descs) HIP_TRY(hipMemcpy(descs, d_descs, (size_t)n * sizeof(Desc), hipMemcpyDeviceToHost));
+    return COVT_OK;
+}
+
+// The build of one plan (covt_device_plan_create_opts) in stages, run() in order; each returns a status and the
+// caller destroys the plan when one fails.  The members: the arguments, the resolved options, and what later
+// stages use of the tile and property arenas.
+struct PlanBuild {
+    covt_device_plan* p;
+    hipStream_t s;
+    const covt_plan_options& o;
+    const uint8_t* d_bytes;
+    uint64_t n_bytes;
+    const uint64_t *d_tile_offsets, *d_tile_sizes;
+    int32_t n_tiles, format, id_mode;
+    const bool props = (o.flags & COVT_PLAN_PROPERTIES) != 0;
+    // device_walk 0: a wave per tile with per-tile slots; 1: the same walk twice; k >= 2: k lanes per workgroup
+    const int wl = o.device_walk >= 2 ? o.device_walk : 0;
+    const size_t nt1 = (size_t)n_tiles + 1;
+    const int32_t lane_max = lane_limits(o.lane_max_bytes, o.lane_max_values);
+    StreamFree order_mem{nullptr, s};  // the largest-first tile order (freed after the walks that read it)
+    // The rest is zero until its stage sets it (a PlanBuild is brace-initialized with the arguments alone).
+    // tile arena (tile_walk): null where the plan has no such member
+    size_t scan_tmp;
+    uint8_t* tscan;
+    int64_t *cnt, *ob, *cb, *obb, *head, *tcost, *pcnt, *pcb, *tcn, *ton;
+    unsigned long long *totals, *pacc;
+    long long* tsum;
+    RawStream* slots;
+    const uint32_t* order;
+    // property arena (prop_records)
+    int64_t n_rec, *rsb, *rob, *pin, *psz, *poff;
+    size_t pscan_tmp, psort_tmp;
+    PropRaw* recs;
+    int32_t* rtile;
+    uint16_t* pflags;
+    uint64_t *pk0, *pk1;
+    uint32_t *pv0, *pv1;
+    uint8_t *psort, *pscan;
+    // the stream count, output bytes, cost sum and largest cost (plan_head), and the bound-sized build
+    int64_t hd[4], spec_cap;
+    bool spec;
+    int tile_walk(), prop_records(), tile_prefixes(), stream_part(bool sp), prop_layout_order(), finish();
+    int emit_entries(int32_t* nvals, uint32_t* ekeys, int64_t ecap);
+    int run() {
+        int st = tile_walk();
+        if (!st && props) st = prop_records();
+        if (!st) st = tile_prefixes();
+        if (!st) st = stream_part(spec);
+        if (!st && props) st = prop_layout_order();
+        return st ? st : finish();
+    }
+    bool splits(int64_t ns, int64_t& smin) const {  // the split threshold (covt_plan_create_ex step 3)
+        smin = o.split_min;
+        if (smin >= 0 && o.split_ratio > 0) smin = std::max<int64_t>(smin, hd[2] / o.split_ratio);
+        return smin >= 0 && ns > 0 && hd[3] > smin && (o.split_max_streams <= 0 || ns <= o.split_max_streams);
+    }
+};
+
+// The tile arena and the counting walk (0: a wave per tile, its lanes in lockstep; k > 0: k lanes per
+// workgroup, a lane per tile).
+int PlanBuild::tile_walk() {
+    HIP_TRY(hipGetDevice(&p->dev));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tmp, (int64_t*)nullptr, (int64_t*)nullptr, (int)nt1, s));
+    const bool use_slots = o.device_walk == 0;
+    // tile arena: status | cnt | ob | cnt_base | ob_base | totals | head | per-tile sums | per-tile costs |
+    // scan scratch [| properties: per-tile record counts | their prefix | streams and output bytes per tile |
+    // totals] | slots
+    ArenaLayout L;
+    const auto a_status = L.take<int32_t>(nt1);
+    const auto a_cnt = L.take<int64_t>(nt1), a_ob = L.take<int64_t>(nt1), a_cb = L.take<int64_t>(nt1),
+               a_obb = L.take<int64_t>(nt1);
+    const auto a_tot = L.take<unsigned long long>(T_N);
+    const auto a_head = L.take<int64_t>(32);  // (256 bytes)
+    const auto a_ts = L.take<long long>(nt1 * 4);
+    const auto a_tc = L.take<int64_t>(nt1 * 2);
+    const auto a_tmp = L.take<uint8_t>(scan_tmp);
+    const auto a_pc = L.take<int64_t>(nt1, props), a_pcb = L.take<int64_t>(nt1, props),
+               a_ttc = L.take<int64_t>(nt1, props), a_tto = L.take<int64_t>(nt1, props);
+    const auto a_pacc = L.take<unsigned long long>(32, props);  // (256 bytes)
+    const auto a_slots = L.take<RawStream>((size_t)n_tiles * kSlots, use_slots);
+    HIP_TRY(plan_malloc(&p->tile_arena, L.bytes(), p->dev, s));
+    void* ta = p->tile_arena;
+    p->d_status = a_status.at(ta);
+    cnt = a_cnt.at(ta), ob = a_ob.at(ta), cb = a_cb.at(ta), obb = a_obb.at(ta);
+    totals = a_tot.at(ta), head = a_head.at(ta), tsum = a_ts.at(ta), tcost = a_tc.at(ta), tscan = a_tmp.at(ta);
+    if (props) pcnt = a_pc.at(ta), pcb = a_pcb.at(ta), tcn = a_ttc.at(ta), ton = a_tto.at(ta), pacc = a_pacc.at(ta);
+    if (use_slots) slots = a_slots.at(ta);
+    HIP_TRY(hipMemsetAsync(totals, 0, T_N * 8, s));
+    HIP_TRY(hipMemsetAsync(tsum, 0, nt1 * 32, s));  // failed tiles leave zeros
+    // property plans of more than 256 tiles: both walks largest tiles first (a stable descending sort of
+    // the sizes)
+    if (props && n_tiles > 256) {
+        size_t otmp = 0;
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, otmp, (const uint64_t*)nullptr,
+                                                             (uint64_t*)nullptr, (const uint32_t*)nullptr,
+                                                             (uint32_t*)nullptr, n_tiles, 0, 40, s));
+        const size_t nt = (size_t)n_tiles;
+        ArenaLayout O;  // order scratch: sorted sizes | tile indices | the order | sort scratch
+        const auto a_keys = O.take<uint64_t>(nt);
+        const auto a_iota = O.take<uint32_t>(nt), a_order = O.take<uint32_t>(nt);
+        const auto a_otmp = O.take<uint8_t>(otmp);
+        void*& om = order_mem.q;
+        HIP_TRY(plan_malloc(&om, O.bytes(), p->dev, s));
+        tile_iota<<<(n_tiles + 255) / 256, 256, 0, s>>>(a_iota.at(om), n_tiles);
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(a_otmp.at(om), otmp, d_tile_sizes, a_keys.at(om),
+                                                             a_iota.at(om), a_order.at(om), n_tiles, 0, 40, s));
+        order = a_order.at(om);
+    }
+    if (wl == 0)
+        walk_count<true><<<(int)nt1, 64, kWalkLds, s>>>(d_bytes, n_bytes, d_tile_offsets, d_tile_sizes, n_tiles, format,
+                                                        id_mode, p->d_status, cnt, ob, slots, o.fpf_split_weight, tcost,
+                                                        order);
+    else
+        walk_count<false><<<(int)((nt1 + wl - 1) / wl), wl, (size_t)wl * 64 + 16, s>>>(
+            d_bytes, n_bytes, d_tile_offsets, d_tile_sizes, n_tiles, format, id_mode, p->d_status, cnt, ob, nullptr,
+            o.fpf_split_weight, tcost, order);
+    HIP_TRY(hipGetLastError());
+    return COVT_OK;
+}
+
+// Property columns: their records (a count walk, one D2H for the record count, the emitting walk), each
+// record's streams and output bytes, and each tile's totals = Id / Geometry + property.
+int PlanBuild::prop_records() {
+    HIP_TRY(hipMemsetAsync(pacc, 0, 256, s));
+    // one walk counting the records and keeping up to kPropSlots per tile (batches whose slots would
+    // take more than kPropSlotBytes walk twice: count, then emit)
+    const size_t slot_bytes = (size_t)n_tiles * kPropSlots * sizeof(PropRaw);
+    if (slot_bytes <= kPropSlotBytes && n_tiles > 0) HIP_TRY(plan_malloc(&p->scratch, slot_bytes, p->dev, s));
+    // the property walk's per-tile record slots: the plan's scratch (a failure on the way frees it with
+    // the plan) until they are copied
+    PropRaw* prop_slots = (PropRaw*)p->scratch;
+    prop_walk<false><<<(int)nt1, 64, kPropWalkLds, s>>>(d_bytes, n_bytes, d_tile_offsets, d_tile_sizes, n_tiles, format,
+                                                       p->d_status, pcnt, nullptr, prop_slots, nullptr, order,
+                                                       pacc + PA_DIVERGED, prop_slots != nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tscan, scan_tmp, pcnt, pcb, (int)nt1, s));
+    unsigned long long walked[2] = {0, 0};  // record count, walk divergence
+    HIP_TRY(hipMemcpyAsync(&walked[0], pcb + n_tiles, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&walked[1], pacc + PA_DIVERGED, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    n_rec = (int64_t)walked[0];
+    if (walked[1]) return COVT_ERR_BAD_HEADER;  // the property walk failed a tile the Id walk accepted
+    if (n_rec > 0x7fffffff) return COVT_ERR_INVALID_ARG;
+    const size_t nr = (size_t)(n_rec > 0 ? n_rec : 1), nr1 = nr + 1;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, pscan_tmp, (int64_t*)nullptr, (int64_t*)nullptr, (int)nr1, s));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, psort_tmp, (uint64_t*)nullptr, (uint64_t*)nullptr,
+                                               (uint32_t*)nullptr, (uint32_t*)nullptr, (int)nr, 0, 41, s));
+    // property arena: records | their tiles | stream counts | output bytes | both prefixes | infos | flags |
+    // in-place input offsets | layout sizes | layout offsets | order keys / values in, out | descriptors |
+    // sort scratch | scan scratch
+    ArenaLayout L;
+    const auto a_recs = L.take<PropRaw>(nr);
+    const auto a_rt = L.take<int32_t>(nr);
+    const auto a_rc = L.take<int64_t>(nr1), a_ro = L.take<int64_t>(nr1), a_rsb = L.take<int64_t>(nr1),
+               a_rob = L.take<int64_t>(nr1);
+    const auto a_pi = L.take<covt_prop_info>(nr);
+    const auto a_pf = L.take<uint16_t>(nr);
+    const auto a_pin = L.take<int64_t>(nr * 2), a_psz = L.take<int64_t>(nr1), a_poff = L.take<int64_t>(nr1);
+    const auto a_k0 = L.take<uint64_t>(nr), a_k1 = L.take<uint64_t>(nr);
+    const auto a_v0 = L.take<uint32_t>(nr), a_v1 = L.take<uint32_t>(nr);
+    const auto a_pd = L.take<covt_prop_desc>(nr);
+    const auto a_st = L.take<uint8_t>(psort_tmp), a_sc = L.take<uint8_t>(pscan_tmp);
+    HIP_TRY(plan_malloc(&p->prop_arena, L.bytes(), p->dev, s));
+    void* pa = p->prop_arena;
+    recs = a_recs.at(pa), rtile = a_rt.at(pa), rsb = a_rsb.at(pa), rob = a_rob.at(pa);
+    int64_t *rs_cnt = a_rc.at(pa), *rs_ob = a_ro.at(pa);
+    pflags = a_pf.at(pa), pin = a_pin.at(pa), psz = a_psz.at(pa), poff = a_poff.at(pa);
+    pk0 = a_k0.at(pa), pk1 = a_k1.at(pa), pv0 = a_v0.at(pa), pv1 = a_v1.at(pa);
+    psort = a_st.at(pa), pscan = a_sc.at(pa);
+    p->n_props = n_rec;
+    p->d_pinfo = a_pi.at(pa);
+    p->d_pdesc = a_pd.at(pa);
+    if (n_rec > 0) {
+        if (prop_slots) {  // from the slots; the tiles with more records walk again
+            prop_compact<<<n_tiles, 64, 0, s>>>(prop_slots, pcnt, pcb, n_tiles, recs, rtile);
+            HIP_TRY(hipGetLastError());
+        }
+        prop_walk<true><<<n_tiles, 64, kPropWalkLds, s>>>(d_bytes, n_bytes, d_tile_offsets, d_tile_sizes, n_tiles,
+                                                         format, p->d_status, pcnt, pcb, recs, rtile, nullptr,
+                                                         pacc + PA_DIVERGED, prop_slots != nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    if (prop_slots) {
+        p->scratch = nullptr;
+        HIP_TRY(hipFreeAsync(prop_slots, s));  // (stream-ordered: after the copy)
+    }
+    prop_sizes<<<(int)((nr1 + 255) / 256), 256, 0, s>>>(recs, n_rec, id_mode, lane_max, rs_cnt, rs_ob, pacc);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(pscan, pscan_tmp, rs_cnt, rsb, (int)(n_rec + 1), s));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(pscan, pscan_tmp, rs_ob, rob, (int)(n_rec + 1), s));
+    tile_totals<<<(int)((nt1 + 255) / 256), 256, 0, s>>>(cnt, ob, pcb, rsb, rob, n_tiles, tcn, ton);
+    HIP_TRY(hipGetLastError());
+    return COVT_OK;
+}
+
+// Each tile's first stream and output offset, and the plan's counts (head).  Id / Geometry plans of many
+// tiles skip the host synchronisation between the walk and the stream entries (~57 us of the 10k-tile plan's
+// 0.62 ms, profiles/r05): the stream arena is sized to a bound, the kernels take the stream count from the
+// device (head[0]), and the count and the split decision are checked at the plan's final synchronisation --
+// a plan past the bound, or one that splits, runs the stream part again with the counted sizes.  (Property
+// plans synchronise for their record count anyway.)
+int PlanBuild::tile_prefixes() {
+    const int64_t *scan_cnt = props ? tcn : cnt, *scan_ob = props ? ton : ob;  // (property plans: the tiles' totals)
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tscan, scan_tmp, scan_cnt, cb, (int)nt1, s));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tscan, scan_tmp, scan_ob, obb, (int)nt1, s));
+    plan_head<<<1, 1024, 0, s>>>(cb, obb, tcost, n_tiles, head, pacc);
+    HIP_TRY(hipGetLastError());
+    spec_cap = std::min<int64_t>((int64_t)kSortFuseChunks * kSortChunk, (int64_t)n_tiles * kSpecCapPerTile);
+    spec = COVT_PLAN_SPEC && !props && wl == 0 && slots && o.split_max_streams > 0 &&
+           (int64_t)n_tiles * kSpecStreamsPerTile > o.split_max_streams;
+    if (!spec) {
+        HIP_TRY(hipMemcpyAsync(hd, head, sizeof(hd), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return COVT_OK;
+}
+
+// The stream entries, their launch order and descriptors; sp: sized to spec_cap, nothing split.
+int PlanBuild::stream_part(bool sp) {
+    const int64_t ns = sp ? spec_cap : hd[0];
+    const int64_t* dns = sp ? head : nullptr;
+    if (ns > 0x7fffffff) return COVT_ERR_INVALID_ARG;
+    // nothing splits unless the largest cost passes the threshold
+    int64_t smin = 0;
+    const bool splitting = !sp && splits(ns, smin);
+    const int64_t grow = split_grow_factor(hd[2], o.split_grow);
+    const int64_t schunk = o.split_chunk * grow, svalues = o.split_values * grow;
+    size_t dscan_tmp = 0;
+    if (splitting)
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, dscan_tmp, (int64_t*)nullptr, (int64_t*)nullptr,
+                                                 (int)(ns + 1), s));
+    const size_t n = (size_t)(ns > 0 ? ns : 1);
+    const int32_t nb = (int32_t)((n + kSortChunk - 1) / kSortChunk);  // counting-sort chunks
+    // more chunks than one scatter workgroup sums itself: their counts scanned by hipcub into bscan
+    const bool scanned = nb > kSortFuseChunks;
+    const size_t mh = (size_t)kSortBuckets * nb;
+    size_t hscan_tmp = 0;
+    if (scanned)
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, hscan_tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)mh, s));
+    // RLE chunk records: every candidate reserves (its cost / split_chunk + 2) <= the batch's
+    const int64_t chunk_cap = splitting ? hd[2] / o.split_chunk + 2 * ns + 2 : 0;
+    // stream arena: info | nvals | launch keys in, out | launch order in, out | bucket counts [| their scan |
+    // scan scratch] | descs [| split: family | desc counts | in launch order | their offsets | RLE list |
+    // FastPFOR list | RLE chunk bases | consumed | chunk records | scan scratch]
+    ArenaLayout L;
+    const auto a_info = L.take<covt_stream_info>(n);
+    const auto a_nv = L.take<int32_t>(n);
+    const auto a_k0 = L.take<uint32_t>(n), a_k1 = L.take<uint32_t>(n), a_v0 = L.take<uint32_t>(n),
+               a_v1 = L.take<uint32_t>(n), a_h = L.take<uint32_t>(mh), a_hs = L.take<uint32_t>(mh, scanned);
+    const auto a_ht = L.take<uint8_t>(hscan_tmp, scanned);
+    const auto a_d = L.take<covt_stream_desc>(n);
+    const auto a_sf = L.take<uint8_t>(n, splitting);
+    const auto a_sn = L.take<int64_t>(n, splitting), a_dn = L.take<int64_t>(n + 1, splitting),
+               a_dp = L.take<int64_t>(n + 1, splitting);
+    const auto a_rl = L.take<uint32_t>(n, splitting), a_fl = L.take<uint32_t>(n, splitting);
+    const auto a_rb = L.take<int64_t>(n, splitting);
+    const auto a_rc = L.take<int32_t>(n, splitting);
+    const auto a_ch = L.take<int4>((size_t)chunk_cap, splitting);
+    const auto a_ds = L.take<uint8_t>(dscan_tmp, splitting);
+    HIP_TRY(plan_malloc(&p->stream_arena, L.bytes(), p->dev, s));
+    void* sa = p->stream_arena;
+    p->d_info = a_info.at(sa);
+    int32_t* nvals = a_nv.at(sa);
+    uint32_t *q0 = a_k0.at(sa), *q1 = a_k1.at(sa), *v0 = a_v0.at(sa), *v1 = a_v1.at(sa), *bhist = a_h.at(sa);
+    uint32_t* bscan = scanned ? a_hs.at(sa) : bhist;
+    p->d_order = v1;
+    p->d_desc = a_d.at(sa);  // (split plans: the descriptor arena's, below)
+    // launch order: the stable radix sort of the launch keys q0 (low byte: -> q1, v0; high byte: -> q0, v1)
+    unsigned long long* fam_tot = splitting ? nullptr : totals + T_FAM;  // (split plans: stream_keys counts)
+    auto launch_order = [&]() -> int {
+        for (int pass = 0; pass < 2; ++pass) {
+            order_hist<<<nb, 256, 0, s>>>(pass ? q1 : q0, ns, nb, 8 * pass, bhist,
+                                          pass == 0 && !splitting ? p->d_info : nullptr, nvals, o.lane_min_streams, totals,
+                                          dns);
+            if (scanned) HIP_TRY(hipcub::DeviceScan::ExclusiveSum(a_ht.at(sa), hscan_tmp, bhist, bscan, (int)mh, s));
+            if (pass == 0) order_scatter<<<nb, 1024, 0, s>>>(q0, nullptr, ns, nb, 0, bscan, scanned, q1, v0, nullptr, dns);
+            else order_scatter<<<nb, 1024, 0, s>>>(q1, v0, ns, nb, 8, bscan, scanned, q0, v1, fam_tot, dns);
+        }
+        HIP_TRY(hipGetLastError());
+        return COVT_OK;
+    };
+    int st = emit_entries(nvals, splitting ? nullptr : q0, sp ? spec_cap : INT64_MAX);  // (split: stream_keys)
+    if (st) return st;
+    const int blocks_s = (int)((ns + 255) / 256);
+    if (ns > 0 && !splitting) {
+        if ((st = launch_order())) return st;
+        fill_descs<<<sp ? std::min(blocks_s, 2048) : blocks_s, 256, 0, s>>>(p->d_info, nvals, q0, v1, ns, p->d_desc, dns);
+        HIP_TRY(hipGetLastError());
+    } else if (splitting) {
+        uint8_t* sfam = a_sf.at(sa);
+        int64_t *sndesc = a_sn.at(sa), *dn = a_dn.at(sa), *dpos = a_dp.at(sa), *rle_base = a_rb.at(sa);
+        uint32_t *rle_list = a_rl.at(sa), *fpf_list = a_fl.at(sa);
+        int32_t* rle_cons = a_rc.at(sa);
+        int4* chunks = a_ch.at(sa);
+        const int walkers = (int)std::min<int64_t>(ns, 1024);
+        split_mark<<<blocks_s, 256, 0, s>>>(p->d_info, nvals, ns, lane_max, o.lane_min_streams, smin, schunk,
+                                            svalues, o.fpf_split_weight, totals, sfam, sndesc, rle_list, fpf_list);
+        HIP_TRY(hipGetLastError());
+        rle_chunks_walk<<<walkers, 64, kStreamRdLds, s>>>(d_bytes, p->d_info, nvals, totals, rle_list, schunk, sfam,
+                                                          sndesc, chunks, chunk_cap, rle_base, rle_cons);
+        HIP_TRY(hipGetLastError());
+        stream_keys<<<blocks_s, 256, 0, s>>>(p->d_info, nvals, ns, lane_max, o.lane_min_streams, totals, q0, sfam, sndesc);
+        HIP_TRY(hipGetLastError());
+        if ((st = launch_order())) return st;
+        gather_ndesc<<<(int)((ns + 256) / 256), 256, 0, s>>>(v1, sndesc, ns, dn);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(a_ds.at(sa), dscan_tmp, dn, dpos, (int)(ns + 1), s));
+        int64_t nd = 0;
+        HIP_TRY(hipMemcpyAsync(&nd, dpos + ns, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        ArenaLayout D;  // descriptor arena: descriptors | the stream of each
+        const auto a_desc = D.take<covt_stream_desc>((size_t)nd);
+        const auto a_dord = D.take<uint32_t>((size_t)nd);
+        HIP_TRY(plan_malloc(&p->desc_arena, D.bytes(), p->dev, s));
+        p->n_descs = nd;
+        p->d_desc = a_desc.at(p->desc_arena);
+        p->d_order = a_dord.at(p->desc_arena);
+        fill_split_descs<<<(int)((nd + 255) / 256), 256, 0, s>>>(p->d_info, nvals, v1, dpos, ns, nd, sfam, schunk,
+                                                                 svalues, chunks, rle_base, rle_cons, p->d_desc,
+                                                                 p->d_order);
+        HIP_TRY(hipGetLastError());
+        fpf_states_walk<<<walkers, 64, kStreamRdLds, s>>>(d_bytes, p->d_info, nvals, totals, fpf_list, svalues, p->d_desc);
+        HIP_TRY(hipGetLastError());
+    }
+    return COVT_OK;
+}
+
+// The stream entries of every tile, and their launch keys where ekeys is not null: unsplit plans write the
+// keys with the entries, taking every small RLE stream to the lane family (the sort's first pass redoes them
+// when the batch has fewer such streams than o.lane_min_streams: the count is known once the entries are written).
+int PlanBuild::emit_entries(int32_t* nvals, uint32_t* ekeys, int64_t ecap) {
+    if (!n_tiles) return COVT_OK;
+    if (slots) {
+        emit_slots<<<n_tiles, 64, 0, s>>>(d_tile_offsets, n_tiles, id_mode, p->d_status, cnt, cb, obb, slots,
+                                          lane_max, p->d_info, nvals, tsum, ekeys, lane_max, ecap);
+        HIP_TRY(hipGetLastError());
+    }
+    if (wl == 0)  // (with slots: only tiles with more than kSlots streams walk again)
+        walk_emit<true><<<n_tiles, 64, kWalkLds, s>>>(d_bytes, n_bytes, d_tile_offsets, d_tile_sizes, n_tiles, format,
+                                                      id_mode, p->d_status, cb, obb, lane_max, p->d_info, nvals, tsum,
+                                                      slots ? cnt : nullptr, ekeys, lane_max, ecap);
+    else
+        walk_emit<false><<<(n_tiles + wl - 1) / wl, wl, (size_t)wl * 64 + 16, s>>>(
+            d_bytes, n_bytes, d_tile_offsets, d_tile_sizes, n_tiles, format, id_mode, p->d_status, cb, obb,
+            lane_max, p->d_info, nvals, tsum, nullptr, ekeys, lane_max, ecap);
+    HIP_TRY(hipGetLastError());
+    reduce_tiles<<<1, 1024, 0, s>>>(tsum, n_tiles, totals, pacc);
+    HIP_TRY(hipGetLastError());
+    if (props && n_rec > 0) {  // the property streams after each tile's Id / Geometry ones
+        prop_fill<<<(int)((n_rec + 255) / 256), 256, 0, s>>>(recs, rtile, n_rec, id_mode, d_tile_offsets, cnt, ob, cb,
+                                                             obb, pcb, rsb, rob, p->d_info, nvals, p->d_pinfo, pflags,
+                                                             pin, ekeys, lane_max);
+        HIP_TRY(hipGetLastError());
+    }
+    return COVT_OK;
+}
+
+// Property output layout and the largest-first descriptor order (after the stream descriptors).
+int PlanBuild::prop_layout_order() {
+    const int pb = (int)((n_rec + 256) / 256);
+    prop_layout<<<pb, 256, 0, s>>>(p->d_pinfo, pflags, n_rec, psz);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(pscan, pscan_tmp, psz, poff, (int)(n_rec + 1), s));
+    HIP_TRY(hipMemcpyAsync(&p->prop_bytes, poff + n_rec, 8, hipMemcpyDeviceToHost, s));
+    if (n_rec <= 0) return COVT_OK;
+    prop_layout_fill<<<pb, 256, 0, s>>>(p->d_pinfo, pflags, n_rec, poff);
+    prop_order_keys<<<pb, 256, 0, s>>>(p->d_pinfo, n_rec, pk0, pv0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(psort, psort_tmp, pk0, pk1, pv0, pv1, (int)n_rec, 0, 41, s));
+    prop_rank<<<pb, 256, 0, s>>>(pv1, n_rec, pv0);  // (pv0, the sort's input values, is free)
+    prop_desc_fill<<<pb, 256, 0, s>>>(p->d_pinfo, pflags, pin, pv0, n_rec, p->d_info, p->d_pdesc);
+    HIP_TRY(hipGetLastError());
+    return COVT_OK;
+}
+
+// The totals to the host; a bound-sized plan past its bound, or one that splits, builds its stream part again
+// with the counted sizes.
+int PlanBuild::finish() {
+    unsigned long long tot[T_N];
+    HIP_TRY(hipMemcpyAsync(tot, totals, sizeof(tot), hipMemcpyDeviceToHost, s));
+    if (spec) HIP_TRY(hipMemcpyAsync(hd, head, sizeof(hd), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    int64_t smin = 0;
+    if (spec && (hd[0] > spec_cap || splits(hd[0], smin))) {
+        ++p->spec_redo;
+        HIP_TRY(hipFreeAsync(p->stream_arena, s));
+        p->stream_arena = nullptr;
+        HIP_TRY(hipMemsetAsync(totals + T_FAM, 0, COVT_NUM_FAMILIES * 8, s));
+        const int st = stream_part(false);
+        if (st) return st;
+        HIP_TRY(hipMemcpyAsync(tot, totals, sizeof(tot), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    p->n_streams = hd[0];
+    p->out_bytes = hd[1];
+    if (!p->desc_arena) p->n_descs = hd[0];  // (split plans: counted with their descriptor arena)
+    p->in_bytes = (int64_t)tot[T_IN];
+    p->out_payload = (int64_t)tot[T_PAYLOAD];
+    p->vertices = (int64_t)tot[T_VERTS];
+    for (int f = 0; f < COVT_NUM_FAMILIES; ++f) p->fam_counts[f] = (int64_t)tot[T_FAM + f];
     return COVT_OK;
 }
 
@@ -2850,7 +3274,6 @@ int covt_device_plan_create_opts(const uint8_t* d_bytes, uint64_t n_bytes, const
                                  const covt_plan_options* opts, void* hip_stream, covt_device_plan** out) {
     covt_plan_options o;
     if (!covt_resolve_options(opts, o) || (o.flags & ~COVT_PLAN_PROPERTIES)) return COVT_ERR_INVALID_ARG;
-    const bool props = (o.flags & COVT_PLAN_PROPERTIES) != 0;
     if (!out || n_tiles < 0 || (n_tiles && (!d_bytes || !d_tile_offsets || !d_tile_sizes))) return COVT_ERR_INVALID_ARG;
     if (format != COVT_FORMAT_GENC && format != COVT_FORMAT_GEND) return COVT_ERR_INVALID_ARG;
     if (id_mode != COVT_ID_FORMAT && id_mode != COVT_ID_JAVA) return COVT_ERR_INVALID_ARG;
@@ -2859,396 +3282,12 @@ int covt_device_plan_create_opts(const uint8_t* d_bytes, uint64_t n_bytes, const
     p->n_tiles = n_tiles;
     p->format = format;
     p->id_mode = id_mode;
-    hipStream_t s = (hipStream_t)hip_stream;
-    auto fail = [&](int st) {
-        covt_device_plan_destroy(p);
-        return st;
-    };
-#define DCHK(x)                                   \
-    do {                                          \
-        if ((x) != hipSuccess) return fail(COVT_ERR_DEVICE); \
-    } while (0)
-    DCHK(hipGetDevice(&p->dev));
-    const size_t nt1 = (size_t)n_tiles + 1;
-    // tile arena: status | cnt | ob | cnt_base | ob_base | totals | head | per-tile sums | per-tile costs |
-    // scan scratch | slots
-    size_t scan_tmp = 0;
-    DCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tmp, (int64_t*)nullptr, (int64_t*)nullptr, (int)nt1, s));
-    // [+ properties: per-tile record counts | their prefix | streams and output bytes per tile | totals]
-    const size_t o_cnt = up256(nt1 * 4), o_ob = o_cnt + up256(nt1 * 8), o_cb = o_ob + up256(nt1 * 8),
-                 o_obb = o_cb + up256(nt1 * 8), o_tot = o_obb + up256(nt1 * 8), o_head = o_tot + up256(T_N * 8),
-                 o_ts = o_head + 256, o_tc = o_ts + up256(nt1 * 32), o_tmp = o_tc + up256(nt1 * 16),
-                 o_pc = o_tmp + up256(scan_tmp), o_pcb = o_pc + (props ? up256(nt1 * 8) : 0),
-                 o_ttc = o_pcb + (props ? up256(nt1 * 8) : 0), o_tto = o_ttc + (props ? up256(nt1 * 8) : 0),
-                 o_pacc = o_tto + (props ? up256(nt1 * 8) : 0), o_slots = o_pacc + (props ? 256 : 0);
-    // device_walk 0: a wave per tile with per-tile slots; 1: the same walk twice; k >= 2: k lanes per workgroup
-    const int wl = o.device_walk >= 2 ? o.device_walk : 0;
-    const bool use_slots = o.device_walk == 0;
-    const size_t tile_bytes = o_slots + (use_slots ? up256((size_t)n_tiles * kSlots * sizeof(RawStream)) : 0);
-    DCHK(plan_malloc(&p->tile_arena, tile_bytes, p->dev, s));
-    uint8_t* ta = (uint8_t*)p->tile_arena;
-    p->d_status = (int32_t*)ta;
-    int64_t *cnt = (int64_t*)(ta + o_cnt), *ob = (int64_t*)(ta + o_ob), *cb = (int64_t*)(ta + o_cb),
-            *obb = (int64_t*)(ta + o_obb), *head = (int64_t*)(ta + o_head), *tcost = (int64_t*)(ta + o_tc);
-    auto* totals = (unsigned long long*)(ta + o_tot);
-    auto* tsum = (long long*)(ta + o_ts);
-    DCHK(hipMemsetAsync(totals, 0, T_N * 8, s));
-    DCHK(hipMemsetAsync(tsum, 0, nt1 * 32, s));  // failed tiles leave zeros
-    const int64_t fpf_w = o.fpf_split_weight;
-    const int32_t lane_max = lane_limits(o.lane_max_bytes, o.lane_max_values);
-    const int64_t lane_min = o.lane_min_streams;
-    // 0: a wave per tile, its lanes in lockstep; k > 0: k lanes per workgroup, a lane per tile
-    RawStream* slots = use_slots ? (RawStream*)(ta + o_slots) : nullptr;
-    // property plans of more than 256 tiles: both walks largest tiles first (a stable descending sort of
-    // the sizes)
-    uint32_t* order = nullptr;
-    void* order_mem = nullptr;
-    if (props && n_tiles > 256) {
-        size_t otmp = 0;
-        DCHK(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, otmp, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                                          (const uint32_t*)nullptr, (uint32_t*)nullptr, n_tiles, 0, 40, s));
-        const size_t nt = (size_t)n_tiles;
-        DCHK(plan_malloc(&order_mem, up256(nt * 8) + 2 * up256(nt * 4) + up256(otmp), p->dev, s));
-        uint8_t* om = (uint8_t*)order_mem;
-        uint32_t* iota = (uint32_t*)(om + up256(nt * 8));
-        order = (uint32_t*)(om + up256(nt * 8) + up256(nt * 4));
-        tile_iota<<<(n_tiles + 255) / 256, 256, 0, s>>>(iota, n_tiles);
-        const hipError_t e = hipcub::DeviceRadixSort::SortPairsDescending(
-            om + up256(nt * 8) + 2 * up256(nt * 4), otmp, d_tile_sizes, (uint64_t*)om, iota, order, n_tiles, 0, 40, s);
-        if (e != hipSuccess) {
-            (void)hipFreeAsync(order_mem, s);
-            return fail(COVT_ERR_DEVICE);
-        }
-    }
-    struct OrderFree {  // (stream-ordered: after the walks that read it)
-        void* m;
-        hipStream_t q;
-        ~OrderFree() { if (m) (void)hipFreeAsync(m, q); }
-    } order_free{order_mem, s};
-    const uint32_t* id_order = order;
-    const uint32_t* prop_order = order;
-    if (wl == 0)
-        walk_count<true><<<(int)nt1, 64, kWalkLds, s>>>(d_bytes, n_bytes, d_tile_offsets, d_tile_sizes, n_tiles, format,
-                                                        id_mode, p->d_status, cnt, ob, slots, fpf_w, tcost, id_order);
-    else
-        walk_count<false><<<(int)((nt1 + wl - 1) / wl), wl, (size_t)wl * 64 + 16, s>>>(
-            d_bytes, n_bytes, d_tile_offsets, d_tile_sizes, n_tiles, format, id_mode, p->d_status, cnt, ob, nullptr,
-            fpf_w, tcost, id_order);
-    DCHK(hipGetLastError());
-    // property columns: their records (a count walk, one D2H for the record count, the emitting walk), each
-    // record's streams and output bytes, and each tile's totals = Id / Geometry + property
-    int64_t *pcnt = nullptr, *pcb = nullptr, *rs_cnt = nullptr, *rs_ob = nullptr, *rsb = nullptr, *rob = nullptr;
-    unsigned long long* pacc = nullptr;
-    PropRaw* recs = nullptr;
-    PropRaw* prop_slots = nullptr;  // the property walk's per-tile record slots (freed once copied)
-    int32_t* rtile = nullptr;
-    int64_t n_rec = 0;
-    size_t pscan_tmp = 0, psort_tmp = 0;
-    size_t po_rt = 0, po_rc = 0, po_ro = 0, po_rsb = 0, po_rob = 0, po_pi = 0, po_pf = 0, po_pin = 0, po_psz = 0,
-           po_poff = 0, po_k0 = 0, po_k1 = 0, po_v0 = 0, po_v1 = 0, po_pd = 0, po_st = 0, po_sc = 0, prop_total = 0;
-    const int64_t* scan_cnt = cnt;
-    const int64_t* scan_ob = ob;
-    if (props) {
-        pcnt = (int64_t*)(ta + o_pc);
-        pcb = (int64_t*)(ta + o_pcb);
-        pacc = (unsigned long long*)(ta + o_pacc);
-        DCHK(hipMemsetAsync(pacc, 0, 256, s));
-        // one walk counting the records and keeping up to kPropSlots per tile (batches whose slots would
-        // take more than kPropSlotBytes walk twice: count, then emit)
-        void* pslots = nullptr;
-        const size_t slot_bytes = (size_t)n_tiles * kPropSlots * sizeof(PropRaw);
-        if (slot_bytes <= kPropSlotBytes && n_tiles > 0) DCHK(plan_malloc(&pslots, slot_bytes, p->dev, s));
-        prop_slots = (PropRaw*)pslots;
-        p->scratch = pslots;  // (a failure on the way frees it with the plan)
-        prop_walk<false><<<(int)nt1, 64, kPropWalkLds, s>>>(d_bytes, n_bytes, d_tile_offsets, d_tile_sizes, n_tiles, format,
-                                                           p->d_status, pcnt, nullptr, prop_slots, nullptr, prop_order,
-                                                           pacc + PA_DIVERGED, prop_slots != nullptr);
-        DCHK(hipGetLastError());
-        DCHK(hipcub::DeviceScan::ExclusiveSum(ta + o_tmp, scan_tmp, pcnt, pcb, (int)nt1, s));
-        unsigned long long head[2] = {0, 0};  // record count, walk divergence
-        DCHK(hipMemcpyAsync(&head[0], pcb + n_tiles, 8, hipMemcpyDeviceToHost, s));
-        DCHK(hipMemcpyAsync(&head[1], pacc + PA_DIVERGED, 8, hipMemcpyDeviceToHost, s));
-        DCHK(hipStreamSynchronize(s));
-        n_rec = (int64_t)head[0];
-        if (head[1]) return fail(COVT_ERR_BAD_HEADER);  // the property walk failed a tile the Id walk accepted
-        if (n_rec > 0x7fffffff) return fail(COVT_ERR_INVALID_ARG);
-        const size_t nr = (size_t)(n_rec > 0 ? n_rec : 1), nr1 = nr + 1;
-        DCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, pscan_tmp, (int64_t*)nullptr, (int64_t*)nullptr, (int)nr1, s));
-        DCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, psort_tmp, (uint64_t*)nullptr, (uint64_t*)nullptr,
-                                                (uint32_t*)nullptr, (uint32_t*)nullptr, (int)nr, 0, 41, s));
-        // property arena: records | their tiles | stream counts | output bytes | both prefixes | infos | flags |
-        // in-place input offsets | layout sizes | layout offsets | order keys / values in, out | descriptors |
-        // sort scratch | scan scratch
-        po_rt = up256(nr * sizeof(PropRaw));
-        po_rc = po_rt + up256(nr * 4);
-        po_ro = po_rc + up256(nr1 * 8);
-        po_rsb = po_ro + up256(nr1 * 8);
-        po_rob = po_rsb + up256(nr1 * 8);
-        po_pi = po_rob + up256(nr1 * 8);
-        po_pf = po_pi + up256(nr * sizeof(covt_prop_info));
-        po_pin = po_pf + up256(nr * 2);
-        po_psz = po_pin + up256(nr * 16);
-        po_poff = po_psz + up256(nr1 * 8);
-        po_k0 = po_poff + up256(nr1 * 8);
-        po_k1 = po_k0 + up256(nr * 8);
-        po_v0 = po_k1 + up256(nr * 8);
-        po_v1 = po_v0 + up256(nr * 4);
-        po_pd = po_v1 + up256(nr * 4);
-        po_st = po_pd + up256(nr * sizeof(covt_prop_desc));
-        po_sc = po_st + up256(psort_tmp);
-        prop_total = po_sc + up256(pscan_tmp);
-        DCHK(plan_malloc(&p->prop_arena, prop_total, p->dev, s));
-        uint8_t* pa = (uint8_t*)p->prop_arena;
-        recs = (PropRaw*)pa;
-        rtile = (int32_t*)(pa + po_rt);
-        rs_cnt = (int64_t*)(pa + po_rc);
-        rs_ob = (int64_t*)(pa + po_ro);
-        rsb = (int64_t*)(pa + po_rsb);
-        rob = (int64_t*)(pa + po_rob);
-        p->n_props = n_rec;
-        p->d_pinfo = (covt_prop_info*)(pa + po_pi);
-        p->d_pdesc = (covt_prop_desc*)(pa + po_pd);
-        if (n_rec > 0) {
-            if (prop_slots) {  // from the slots; the tiles with more records walk again
-                prop_compact<<<n_tiles, 64, 0, s>>>(prop_slots, pcnt, pcb, n_tiles, recs, rtile);
-                DCHK(hipGetLastError());
-            }
-            prop_walk<true><<<n_tiles, 64, kPropWalkLds, s>>>(d_bytes, n_bytes, d_tile_offsets, d_tile_sizes, n_tiles,
-                                                             format, p->d_status, pcnt, pcb, recs, rtile, nullptr,
-                                                             pacc + PA_DIVERGED, prop_slots != nullptr);
-            DCHK(hipGetLastError());
-        }
-        if (prop_slots) {
-            p->scratch = nullptr;
-            DCHK(hipFreeAsync(prop_slots, s));  // (stream-ordered: after the copy)
-            prop_slots = nullptr;
-        }
-        const int32_t lane_max0 = lane_limits(o.lane_max_bytes, o.lane_max_values);
-        prop_sizes<<<(int)((nr1 + 255) / 256), 256, 0, s>>>(recs, n_rec, id_mode, lane_max0, rs_cnt, rs_ob, pacc);
-        DCHK(hipGetLastError());
-        DCHK(hipcub::DeviceScan::ExclusiveSum(pa + po_sc, pscan_tmp, rs_cnt, rsb, (int)(n_rec + 1), s));
-        DCHK(hipcub::DeviceScan::ExclusiveSum(pa + po_sc, pscan_tmp, rs_ob, rob, (int)(n_rec + 1), s));
-        int64_t *tcn = (int64_t*)(ta + o_ttc), *ton = (int64_t*)(ta + o_tto);
-        tile_totals<<<(int)((nt1 + 255) / 256), 256, 0, s>>>(cnt, ob, pcb, rsb, rob, n_tiles, tcn, ton);
-        DCHK(hipGetLastError());
-        scan_cnt = tcn;
-        scan_ob = ton;
-    }
-    DCHK(hipcub::DeviceScan::ExclusiveSum(ta + o_tmp, scan_tmp, scan_cnt, cb, (int)nt1, s));
-    DCHK(hipcub::DeviceScan::ExclusiveSum(ta + o_tmp, scan_tmp, scan_ob, obb, (int)nt1, s));
-    plan_head<<<1, 1024, 0, s>>>(cb, obb, tcost, n_tiles, head, pacc);
-    DCHK(hipGetLastError());
-    // Id / Geometry plans of many tiles skip the host synchronisation between the walk and the stream entries
-    // (~57 us of the 10k-tile plan's 0.62 ms, profiles/r05): the stream arena is sized to a bound, the kernels
-    // take the stream count from the device (head[0]), and the count and the split decision are checked at the
-    // plan's final synchronisation -- a plan past the bound, or one that splits, runs this part again with the
-    // counted sizes.  (Property plans synchronise for their record count anyway.)
-    int64_t hd[4] = {0, 0, 0, 0};
-    const int64_t spec_cap = std::min<int64_t>((int64_t)kSortFuseChunks * kSortChunk, (int64_t)n_tiles * kSpecCapPerTile);
-    const bool spec = COVT_PLAN_SPEC && !props && wl == 0 && slots && o.split_max_streams > 0 &&
-                      (int64_t)n_tiles * kSpecStreamsPerTile > o.split_max_streams;
-    if (!spec) {
-        DCHK(hipMemcpyAsync(hd, head, sizeof(hd), hipMemcpyDeviceToHost, s));
-        DCHK(hipStreamSynchronize(s));
-    }
-    auto splits = [&](int64_t ns, int64_t& smin) {  // the split threshold (covt_plan_create_ex step 3)
-        smin = o.split_min;
-        if (smin >= 0 && o.split_ratio > 0) smin = std::max<int64_t>(smin, hd[2] / o.split_ratio);
-        return smin >= 0 && ns > 0 && hd[3] > smin && (o.split_max_streams <= 0 || ns <= o.split_max_streams);
-    };
-    // the stream entries, their launch order and descriptors; sp: sized to spec_cap, nothing split
-    auto stream_part = [&](bool sp) -> int {
-    const int64_t ns = sp ? spec_cap : hd[0];
-    const int64_t* dns = sp ? head : nullptr;
-    const int64_t ecap = sp ? spec_cap : INT64_MAX;
-    if (!sp) {
-        p->n_streams = ns;
-        p->n_descs = ns;
-        p->out_bytes = hd[1];
-    }
-    if (ns > 0x7fffffff) return fail(COVT_ERR_INVALID_ARG);
-    // nothing splits unless the largest cost passes the threshold
-    int64_t smin = 0;
-    const bool splitting = !sp && splits(ns, smin);
-    const int64_t grow = split_grow_factor(hd[2], o.split_grow);
-    const int64_t schunk = o.split_chunk * grow, svalues = o.split_values * grow;
-    // stream arena: info | nvals | launch buckets | sorted buckets | launch order | bucket counts | descs [|
-    // split: family | desc counts | offsets | RLE list | FastPFOR list | scan scratch]
-    size_t dscan_tmp = 0;
-    if (splitting)
-        DCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, dscan_tmp, (int64_t*)nullptr, (int64_t*)nullptr, (int)(ns + 1), s));
-    const size_t n = (size_t)(ns > 0 ? ns : 1);
-    const int32_t nb = (int32_t)((n + kSortChunk - 1) / kSortChunk);  // counting-sort chunks
-    // more chunks than one scatter workgroup sums itself: their counts scanned by hipcub into bscan
-    const bool scanned = nb > kSortFuseChunks;
-    const size_t mh = (size_t)kSortBuckets * nb;
-    size_t hscan_tmp = 0;
-    if (scanned)
-        DCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, hscan_tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)mh, s));
-    // RLE chunk records: every candidate reserves (its cost / split_chunk + 2) <= the batch's
-    const int64_t chunk_cap = splitting ? hd[2] / o.split_chunk + 2 * ns + 2 : 0;
-    const size_t o_nv = up256(n * sizeof(covt_stream_info)), o_k0 = o_nv + up256(n * 4), o_k1 = o_k0 + up256(n * 4),
-                 o_v0 = o_k1 + up256(n * 4), o_v1 = o_v0 + up256(n * 4), o_h = o_v1 + up256(n * 4),
-                 o_hs = o_h + up256(mh * 4), o_ht = o_hs + (scanned ? up256(mh * 4) : 0),
-                 o_d = o_ht + (scanned ? up256(hscan_tmp) : 0),
-                 o_sf = o_d + up256(n * sizeof(covt_stream_desc)),
-                 o_sn = o_sf + up256(n), o_dn = o_sn + up256(n * 8), o_dp = o_dn + up256((n + 1) * 8),
-                 o_rl = o_dp + up256((n + 1) * 8), o_fl = o_rl + up256(n * 4), o_rb = o_fl + up256(n * 4),
-                 o_rc = o_rb + up256(n * 8), o_ch = o_rc + up256(n * 4), o_ds = o_ch + up256((size_t)chunk_cap * 16),
-                 stream_bytes = splitting ? o_ds + up256(dscan_tmp) : o_sf;
-    DCHK(plan_malloc(&p->stream_arena, stream_bytes, p->dev, s));
-    uint8_t* sa = (uint8_t*)p->stream_arena;
-    p->d_info = (covt_stream_info*)sa;
-    int32_t* nvals = (int32_t*)(sa + o_nv);
-    uint32_t *q0 = (uint32_t*)(sa + o_k0), *q1 = (uint32_t*)(sa + o_k1), *v0 = (uint32_t*)(sa + o_v0),
-             *v1 = (uint32_t*)(sa + o_v1);
-    uint32_t* bhist = (uint32_t*)(sa + o_h);
-    uint32_t* bscan = scanned ? (uint32_t*)(sa + o_hs) : bhist;
-    p->d_order = v1;
-    p->d_desc = (covt_stream_desc*)(sa + o_d);
-    // launch order: the stable radix sort of the launch keys q0 (low byte: -> q1, v0; high byte: -> q0, v1)
-    unsigned long long* fam_tot = splitting ? nullptr : totals + T_FAM;  // (split plans: stream_keys counts)
-    auto launch_order = [&]() {
-        for (int pass = 0; pass < 2; ++pass) {
-            order_hist<<<nb, 256, 0, s>>>(pass ? q1 : q0, ns, nb, 8 * pass, bhist,
-                                          pass == 0 && !splitting ? p->d_info : nullptr, nvals, lane_min, totals, dns);
-            if (scanned) {
-                const hipError_t e = hipcub::DeviceScan::ExclusiveSum(sa + o_ht, hscan_tmp, bhist, bscan, (int)mh, s);
-                if (e != hipSuccess) return e;
-            }
-            if (pass == 0) order_scatter<<<nb, 1024, 0, s>>>(q0, nullptr, ns, nb, 0, bscan, scanned, q1, v0, nullptr, dns);
-            else order_scatter<<<nb, 1024, 0, s>>>(q1, v0, ns, nb, 8, bscan, scanned, q0, v1, fam_tot, dns);
-        }
-        return hipGetLastError();
-    };
-    // unsplit plans: the launch keys written with the stream entries, taking every small RLE stream to the
-    // lane family (the sort's first pass redoes them when the batch has fewer such streams than lane_min:
-    // the count is known once the entries are written); split plans: stream_keys after split_mark
-    uint32_t* ekeys = splitting ? nullptr : q0;
-    const int32_t lm = lane_max;
-    if (n_tiles) {
-        if (slots) {
-            emit_slots<<<n_tiles, 64, 0, s>>>(d_tile_offsets, n_tiles, id_mode, p->d_status, cnt, cb, obb, slots,
-                                              lane_max, p->d_info, nvals, tsum, ekeys, lm, ecap);
-            DCHK(hipGetLastError());
-        }
-        if (wl == 0)  // (with slots: only tiles with more than kSlots streams walk again)
-            walk_emit<true><<<n_tiles, 64, kWalkLds, s>>>(d_bytes, n_bytes, d_tile_offsets, d_tile_sizes, n_tiles, format,
-                                                          id_mode, p->d_status, cb, obb, lane_max, p->d_info, nvals, tsum,
-                                                          slots ? cnt : nullptr, ekeys, lm, ecap);
-        else
-            walk_emit<false><<<(n_tiles + wl - 1) / wl, wl, (size_t)wl * 64 + 16, s>>>(
-                d_bytes, n_bytes, d_tile_offsets, d_tile_sizes, n_tiles, format, id_mode, p->d_status, cb, obb,
-                lane_max, p->d_info, nvals, tsum, nullptr, ekeys, lm, ecap);
-        DCHK(hipGetLastError());
-        reduce_tiles<<<1, 1024, 0, s>>>(tsum, n_tiles, totals, pacc);
-        DCHK(hipGetLastError());
-        if (props && n_rec > 0) {  // the property streams after each tile's Id / Geometry ones
-            uint8_t* pa = (uint8_t*)p->prop_arena;
-            prop_fill<<<(int)((n_rec + 255) / 256), 256, 0, s>>>(recs, rtile, n_rec, id_mode, d_tile_offsets, cnt, ob, cb,
-                                                                 obb, pcb, rsb, rob, p->d_info, nvals, p->d_pinfo,
-                                                                 (uint16_t*)(pa + po_pf), (int64_t*)(pa + po_pin), ekeys,
-                                                                 lm);
-            DCHK(hipGetLastError());
-        }
-    }
-    const int blocks_s = (int)((ns + 255) / 256);
-    if (ns > 0 && !splitting) {
-        DCHK(launch_order());
-        fill_descs<<<sp ? std::min(blocks_s, 2048) : blocks_s, 256, 0, s>>>(p->d_info, nvals, q0, v1, ns, p->d_desc, dns);
-        DCHK(hipGetLastError());
-    } else if (splitting) {
-        auto* sfam = (uint8_t*)(sa + o_sf);
-        auto *sndesc = (int64_t*)(sa + o_sn), *dn = (int64_t*)(sa + o_dn), *dpos = (int64_t*)(sa + o_dp);
-        auto *rle_list = (uint32_t*)(sa + o_rl), *fpf_list = (uint32_t*)(sa + o_fl);
-        const int walkers = (int)std::min<int64_t>(ns, 1024);
-        split_mark<<<blocks_s, 256, 0, s>>>(p->d_info, nvals, ns, lane_max, lane_min, smin, schunk,
-                                            svalues, fpf_w, totals, sfam, sndesc, rle_list, fpf_list);
-        DCHK(hipGetLastError());
-        auto* chunks = (int4*)(sa + o_ch);
-        auto* rle_base = (int64_t*)(sa + o_rb);
-        auto* rle_cons = (int32_t*)(sa + o_rc);
-        rle_chunks_walk<<<walkers, 64, kStreamRdLds, s>>>(d_bytes, p->d_info, nvals, totals, rle_list, schunk, sfam,
-                                                 sndesc, chunks, chunk_cap, rle_base, rle_cons);
-        DCHK(hipGetLastError());
-        stream_keys<<<blocks_s, 256, 0, s>>>(p->d_info, nvals, ns, lane_max, lane_min, totals, q0, sfam, sndesc);
-        DCHK(hipGetLastError());
-        DCHK(launch_order());
-        gather_ndesc<<<(int)((ns + 256) / 256), 256, 0, s>>>(v1, sndesc, ns, dn);
-        DCHK(hipGetLastError());
-        DCHK(hipcub::DeviceScan::ExclusiveSum(sa + o_ds, dscan_tmp, dn, dpos, (int)(ns + 1), s));
-        int64_t nd = 0;
-        DCHK(hipMemcpyAsync(&nd, dpos + ns, 8, hipMemcpyDeviceToHost, s));
-        DCHK(hipStreamSynchronize(s));
-        // descriptor arena: descriptors | the stream of each
-        DCHK(plan_malloc(&p->desc_arena, up256((size_t)nd * sizeof(covt_stream_desc)) + up256((size_t)nd * 4), p->dev, s));
-        p->n_descs = nd;
-        p->d_desc = (covt_stream_desc*)p->desc_arena;
-        p->d_order = (uint32_t*)((uint8_t*)p->desc_arena + up256((size_t)nd * sizeof(covt_stream_desc)));
-        fill_split_descs<<<(int)((nd + 255) / 256), 256, 0, s>>>(p->d_info, nvals, v1, dpos, ns, nd, sfam, schunk,
-                                                                 svalues, chunks, rle_base, rle_cons, p->d_desc,
-                                                                 p->d_order);
-        DCHK(hipGetLastError());
-        fpf_states_walk<<<walkers, 64, kStreamRdLds, s>>>(d_bytes, p->d_info, nvals, totals, fpf_list, svalues, p->d_desc);
-        DCHK(hipGetLastError());
-    }
-    return COVT_OK;
-    };
-    {
-        const int st = stream_part(spec);
-        if (st) return st;  // (fail() has destroyed the plan)
-    }
-
-    if (props) {  // property output layout and the largest-first descriptor order (after the stream descriptors)
-        uint8_t* pa = (uint8_t*)p->prop_arena;
-        auto* pflags = (uint16_t*)(pa + po_pf);
-        auto *psz = (int64_t*)(pa + po_psz), *poff = (int64_t*)(pa + po_poff);
-        const int pb = (int)((n_rec + 256) / 256);
-        prop_layout<<<pb, 256, 0, s>>>(p->d_pinfo, pflags, n_rec, psz);
-        DCHK(hipGetLastError());
-        DCHK(hipcub::DeviceScan::ExclusiveSum(pa + po_sc, pscan_tmp, psz, poff, (int)(n_rec + 1), s));
-        DCHK(hipMemcpyAsync(&p->prop_bytes, poff + n_rec, 8, hipMemcpyDeviceToHost, s));
-        if (n_rec > 0) {
-            prop_layout_fill<<<pb, 256, 0, s>>>(p->d_pinfo, pflags, n_rec, poff);
-            auto *pk0 = (uint64_t*)(pa + po_k0), *pk1 = (uint64_t*)(pa + po_k1);
-            auto *pv0 = (uint32_t*)(pa + po_v0), *pv1 = (uint32_t*)(pa + po_v1);
-            prop_order_keys<<<pb, 256, 0, s>>>(p->d_pinfo, n_rec, pk0, pv0);
-            DCHK(hipGetLastError());
-            DCHK(hipcub::DeviceRadixSort::SortPairs(pa + po_st, psort_tmp, pk0, pk1, pv0, pv1, (int)n_rec, 0, 41, s));
-            prop_rank<<<pb, 256, 0, s>>>(pv1, n_rec, pv0);  // (pv0, the sort's input values, is free)
-            prop_desc_fill<<<pb, 256, 0, s>>>(p->d_pinfo, pflags, (const int64_t*)(pa + po_pin), pv0, n_rec, p->d_info,
-                                              p->d_pdesc);
-            DCHK(hipGetLastError());
-        }
-    }
-    unsigned long long tot[T_N];
-    DCHK(hipMemcpyAsync(tot, totals, sizeof(tot), hipMemcpyDeviceToHost, s));
-    if (spec) DCHK(hipMemcpyAsync(hd, head, sizeof(hd), hipMemcpyDeviceToHost, s));
-    DCHK(hipStreamSynchronize(s));
-    if (spec) {
-        int64_t smin = 0;
-        if (hd[0] > spec_cap || splits(hd[0], smin)) {  // past the bound, or a split plan: with the counted sizes
-            ++p->spec_redo;
-            DCHK(hipFreeAsync(p->stream_arena, s));
-            p->stream_arena = nullptr;
-            DCHK(hipMemsetAsync(totals + T_FAM, 0, COVT_NUM_FAMILIES * 8, s));
-            const int st = stream_part(false);
-            if (st) return st;
-            DCHK(hipMemcpyAsync(tot, totals, sizeof(tot), hipMemcpyDeviceToHost, s));
-            DCHK(hipStreamSynchronize(s));
-        } else {
-            p->n_streams = hd[0];
-            p->n_descs = hd[0];
-            p->out_bytes = hd[1];
-        }
-    }
-#undef DCHK
-    p->in_bytes = (int64_t)tot[T_IN];
-    p->out_payload = (int64_t)tot[T_PAYLOAD];
-    p->vertices = (int64_t)tot[T_VERTS];
-    for (int f = 0; f < COVT_NUM_FAMILIES; ++f) p->fam_counts[f] = (int64_t)tot[T_FAM + f];
-    *out = p;
-    return COVT_OK;
+    PlanBuild build{p, (hipStream_t)hip_stream, o, d_bytes, n_bytes, d_tile_offsets, d_tile_sizes, n_tiles,
+                    format, id_mode};
+    const int st = build.run();
+    if (st) covt_device_plan_destroy(p);  // (the one place: every stage returns its failure here)
+    else *out = p;
+    return st;
 }
 
 int covt_device_plan_pool_trim(int device, uint64_t keep_bytes) {
@@ -3256,24 +3295,20 @@ int covt_device_plan_pool_trim(int device, uint64_t keep_bytes) {
     if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return COVT_ERR_INVALID_ARG;
     hipMemPool_t mp = plan_pool(device);
     if (!mp) return COVT_ERR_DEVICE;
-    int cur = 0;
-    const bool sw = hipGetDevice(&cur) == hipSuccess && cur != device && hipSetDevice(device) == hipSuccess;
+    DeviceGuard on_device(device);
     (void)hipDeviceSynchronize();  // (freed arenas return to the pool in stream order)
-    const hipError_t e = hipMemPoolTrimTo(mp, (size_t)keep_bytes);
-    if (sw) (void)hipSetDevice(cur);
-    return e == hipSuccess ? COVT_OK : COVT_ERR_DEVICE;
+    HIP_TRY(hipMemPoolTrimTo(mp, (size_t)keep_bytes));
+    return COVT_OK;
 }
 
 void covt_device_plan_destroy(covt_device_plan* p) {
     if (!p) return;
-    int cur = 0;
-    const bool sw = hipGetDevice(&cur) == hipSuccess && cur != p->dev && hipSetDevice(p->dev) == hipSuccess;
+    DeviceGuard on_device(p->dev);
     // (hipFree's implicit device synchronization, then the arenas back to the pool)
     (void)hipDeviceSynchronize();
     for (void* q : {p->tile_arena, p->stream_arena, p->desc_arena, p->geo_arena, p->prop_arena, p->scratch})
         if (q) (void)hipFreeAsync(q, nullptr);
     (void)hipStreamSynchronize(nullptr);
-    if (sw) (void)hipSetDevice(cur);
     delete p;
 }
 
@@ -3304,99 +3339,87 @@ int covt_device_plan_copy(const covt_device_plan* p, covt_stream_info* streams, 
                           int32_t* tile_status) {
     if (!p) return COVT_ERR_INVALID_ARG;
     const size_t ns = (size_t)p->n_streams, nd = (size_t)p->n_descs;
-    if (streams && ns && hipMemcpy(streams, p->d_info, ns * sizeof(covt_stream_info), hipMemcpyDeviceToHost) != hipSuccess)
-        return COVT_ERR_DEVICE;
-    if (descs && nd && hipMemcpy(descs, p->d_desc, nd * sizeof(covt_stream_desc), hipMemcpyDeviceToHost) != hipSuccess)
-        return COVT_ERR_DEVICE;
-    if (tile_status && p->n_tiles &&
-        hipMemcpy(tile_status, p->d_status, (size_t)p->n_tiles * 4, hipMemcpyDeviceToHost) != hipSuccess)
-        return COVT_ERR_DEVICE;
+    if (streams && ns) HIP_TRY(hipMemcpy(streams, p->d_info, ns * sizeof(covt_stream_info), hipMemcpyDeviceToHost));
+    if (descs && nd) HIP_TRY(hipMemcpy(descs, p->d_desc, nd * sizeof(covt_stream_desc), hipMemcpyDeviceToHost));
+    if (tile_status && p->n_tiles)
+        HIP_TRY(hipMemcpy(tile_status, p->d_status, (size_t)p->n_tiles * 4, hipMemcpyDeviceToHost));
     return COVT_OK;
 }
 
 int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     if (!p) return COVT_ERR_INVALID_ARG;
     if (p->geo_built) return COVT_OK;
-    int cur = 0;
-    if (hipGetDevice(&cur) != hipSuccess || (cur != p->dev && hipSetDevice(p->dev) != hipSuccess)) return COVT_ERR_DEVICE;
-    struct Restore {
-        int cur, dev;
-        ~Restore() { if (cur != dev) (void)hipSetDevice(cur); }
-    } restore{cur, p->dev};
+    DeviceGuard on_device(p->dev);
+    if (!on_device.ok) return COVT_ERR_DEVICE;
     hipStream_t s = (hipStream_t)hip_stream;
     const int64_t ns = p->n_streams;
     const size_t n1 = (size_t)ns + 1;
     size_t scan_tmp = 0;
-    if (hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tmp, (int64_t*)nullptr, (int64_t*)nullptr, (int)n1, s) != hipSuccess)
-        return COVT_ERR_DEVICE;
-    // stage 1 arena: column starts | their indices | scan scratch
-    void* tmp = nullptr;
-    const size_t o_gp = up256(n1 * 8), o_t = o_gp + up256(n1 * 8);
-    if (plan_malloc(&tmp, o_t + up256(scan_tmp), p->dev, s) != hipSuccess) return COVT_ERR_DEVICE;
-    struct Free {  // stream-ordered: after the work on s that uses it
-        void* q;
-        hipStream_t s;
-        ~Free() { if (q) (void)hipFreeAsync(q, s); }
-    } free_tmp{tmp, s};
-    int64_t *gst = (int64_t*)tmp, *gpos = (int64_t*)((uint8_t*)tmp + o_gp);
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tmp, (int64_t*)nullptr, (int64_t*)nullptr, (int)n1, s));
+    ArenaLayout T;  // stage 1 arena: column starts | their indices | scan scratch
+    const auto a_gst = T.take<int64_t>(n1), a_gpos = T.take<int64_t>(n1);
+    const auto a_tscan = T.take<uint8_t>(scan_tmp);
+    StreamFree tmp{nullptr, s};
+    HIP_TRY(plan_malloc(&tmp.q, T.bytes(), p->dev, s));
+    int64_t *gst = a_gst.at(tmp.q), *gpos = a_gpos.at(tmp.q);
     const int blocks = (int)((n1 + 255) / 256);
     geom_mark<<<blocks, 256, 0, s>>>(p->d_info, ns, gst);
-    if (hipGetLastError() != hipSuccess) return COVT_ERR_DEVICE;
-    if (hipcub::DeviceScan::ExclusiveSum((uint8_t*)tmp + o_t, scan_tmp, gst, gpos, (int)n1, s) != hipSuccess)
-        return COVT_ERR_DEVICE;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(a_tscan.at(tmp.q), scan_tmp, gst, gpos, (int)n1, s));
     int64_t nc = 0;
-    if (hipMemcpyAsync(&nc, gpos + ns, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return COVT_ERR_DEVICE;
-    // geometry arena: records | descriptors | column bytes | column offsets | keys in/out | vals in/out | scratch
+    HIP_TRY(hipMemcpyAsync(&nc, gpos + ns, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     const size_t m = (size_t)(nc > 0 ? nc : 1);
     size_t sort_tmp = 0, cscan_tmp = 0;
-    if (hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr,
-                                           (uint32_t*)nullptr, (int)nc, 0, 41, s) != hipSuccess ||
-        hipcub::DeviceScan::ExclusiveSum(nullptr, cscan_tmp, (int64_t*)nullptr, (int64_t*)nullptr, (int)(nc + 1), s) != hipSuccess)
-        return COVT_ERR_DEVICE;
-    const size_t o_gd = up256(m * sizeof(covt_geom_info)), o_cb = o_gd + up256(m * sizeof(covt_geom_desc)),
-                 o_co = o_cb + up256((m + 1) * 8), o_k0 = o_co + up256((m + 1) * 8), o_k1 = o_k0 + up256(m * 8),
-                 o_v0 = o_k1 + up256(m * 8), o_v1 = o_v0 + up256(m * 4), o_st = o_v1 + up256(m * 4),
-                 o_cs = o_st + up256(sort_tmp), o_wkb = o_cs + up256(cscan_tmp),
-                 o_bbox = o_wkb + product_arena_bytes<WkbProduct>(m), total = o_bbox + product_arena_bytes<BboxProduct>(m);
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp, (uint64_t*)nullptr, (uint64_t*)nullptr,
+                                               (uint32_t*)nullptr, (uint32_t*)nullptr, (int)nc, 0, 41, s));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, cscan_tmp, (int64_t*)nullptr, (int64_t*)nullptr, (int)(nc + 1), s));
+    // geometry arena: records | descriptors | column bytes | column offsets | keys in/out | vals in/out | sort
+    // scratch | scan scratch | the products' slices
+    ArenaLayout L;
+    const auto a_gi = L.take<covt_geom_info>(m);
+    const auto a_gd = L.take<covt_geom_desc>(m);
+    const auto a_cb = L.take<int64_t>(m + 1), a_co = L.take<int64_t>(m + 1);
+    const auto a_k0 = L.take<uint64_t>(m), a_k1 = L.take<uint64_t>(m);
+    const auto a_v0 = L.take<uint32_t>(m), a_v1 = L.take<uint32_t>(m);
+    const auto a_st = L.take<uint8_t>(sort_tmp), a_cs = L.take<uint8_t>(cscan_tmp);
+    const ProductSlice<WkbProduct> a_wkb(L, m);
+    const ProductSlice<BboxProduct> a_bbox(L, m);
     // the arena is the plan's only on success: a failed build frees it (a retry allocates afresh)
-    void* arena = nullptr;
-    if (plan_malloc(&arena, total, p->dev, s) != hipSuccess) return COVT_ERR_DEVICE;
-    Free free_arena{arena, s};
-    uint8_t* g = (uint8_t*)arena;
-    p->d_ginfo = (covt_geom_info*)g;
-    p->d_gdesc = (covt_geom_desc*)(g + o_gd);
-    int64_t *colbytes = (int64_t*)(g + o_cb), *coloff = (int64_t*)(g + o_co);
-    uint64_t *k0 = (uint64_t*)(g + o_k0), *k1 = (uint64_t*)(g + o_k1);
-    uint32_t *v0 = (uint32_t*)(g + o_v0), *v1 = (uint32_t*)(g + o_v1);
-    if (hipMemsetAsync(colbytes, 0, (m + 1) * 8, s) != hipSuccess) return COVT_ERR_DEVICE;
+    StreamFree arena{nullptr, s};
+    HIP_TRY(plan_malloc(&arena.q, L.bytes(), p->dev, s));
+    void* g = arena.q;
+    p->d_ginfo = a_gi.at(g);
+    p->d_gdesc = a_gd.at(g);
+    int64_t *colbytes = a_cb.at(g), *coloff = a_co.at(g);
+    uint32_t* v1 = a_v1.at(g);
+    uint8_t* cscan = a_cs.at(g);
+    HIP_TRY(hipMemsetAsync(colbytes, 0, (m + 1) * 8, s));
     int64_t asm_bytes = 0, wkb_bytes = 0, bbox_bytes = 0;
     if (nc > 0) {
         geom_columns<<<(int)((ns + 255) / 256), 256, 0, s>>>(p->d_info, ns, p->format, gst, gpos, p->d_ginfo, colbytes);
-        if (hipGetLastError() != hipSuccess) return COVT_ERR_DEVICE;
-        if (hipcub::DeviceScan::ExclusiveSum(g + o_cs, cscan_tmp, colbytes, coloff, (int)(nc + 1), s) != hipSuccess)
-            return COVT_ERR_DEVICE;
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(cscan, cscan_tmp, colbytes, coloff, (int)(nc + 1), s));
         const int cb = (int)((nc + 255) / 256);
-        geom_keys<<<cb, 256, 0, s>>>(p->d_ginfo, nc, coloff, k0, v0);
-        if (hipGetLastError() != hipSuccess) return COVT_ERR_DEVICE;
-        if (hipcub::DeviceRadixSort::SortPairs(g + o_st, sort_tmp, k0, k1, v0, v1, (int)nc, 0, 41, s) != hipSuccess)
-            return COVT_ERR_DEVICE;
+        geom_keys<<<cb, 256, 0, s>>>(p->d_ginfo, nc, coloff, a_k0.at(g), a_v0.at(g));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(a_st.at(g), sort_tmp, a_k0.at(g), a_k1.at(g), a_v0.at(g), v1, (int)nc, 0,
+                                                   41, s));
         geom_descs<<<cb, 256, 0, s>>>(p->d_info, p->d_ginfo, v1, nc, p->d_gdesc);
-        if (hipGetLastError() != hipSuccess) return COVT_ERR_DEVICE;
+        HIP_TRY(hipGetLastError());
     }
     // the products' layouts over the finished records, descriptors at the geometry descriptors' rows
-    int st = plan_product<WkbProduct>(g + o_wkb, m, nc, p->d_ginfo, g + o_cs, cscan_tmp, s, p->d_winfo, p->d_wdesc,
-                                      &wkb_bytes);
+    int st = plan_product(a_wkb, g, m, nc, p->d_ginfo, cscan, cscan_tmp, s, p->d_winfo, p->d_wdesc, &wkb_bytes);
     if (st == COVT_OK)
-        st = plan_product<BboxProduct>(g + o_bbox, m, nc, p->d_ginfo, g + o_cs, cscan_tmp, s, p->d_binfo, p->d_bdesc,
-                                       &bbox_bytes);
+        st = plan_product(a_bbox, g, m, nc, p->d_ginfo, cscan, cscan_tmp, s, p->d_binfo, p->d_bdesc, &bbox_bytes);
     if (st) return st;
-    if (nc > 0 && (hipMemcpyAsync(&asm_bytes, coloff + nc, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                   hipStreamSynchronize(s) != hipSuccess))
-        return COVT_ERR_DEVICE;
+    if (nc > 0) {
+        HIP_TRY(hipMemcpyAsync(&asm_bytes, coloff + nc, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
     if (p->geo_arena) (void)hipFreeAsync(p->geo_arena, s);
-    p->geo_arena = arena;
-    free_arena.q = nullptr;
+    p->geo_arena = arena.q;
+    arena.q = nullptr;
     p->n_geo = nc;
     p->asm_bytes = asm_bytes;
     p->wkb_bytes = wkb_bytes;
