@@ -32,9 +32,7 @@ namespace covt {
 
 constexpr int kWin = 1024;  // window bytes (64 lanes x 16 B)
 // kWavesPerBlock (covt_internal.h): independent waves (streams) per workgroup
-constexpr int kFpfBlock = 256;
-constexpr int kFpfPage = 65536;
-constexpr int kFpfBcCap = 3 * kFpfPage / kFpfBlock + kFpfPage;  // JavaFastPFOR byteContainer size
+// kFpfBlock, kFpfPage, kFpfBcCap (covt_split_plan.h): the FastPFOR framing's constants
 
 #ifndef COVT_LONG_STREAM
 #define COVT_LONG_STREAM 16384
@@ -2653,17 +2651,13 @@ __device__ __forceinline__ void run_fastpfor_chunk(Ctx& c, int32_t v0, int32_t v
     Carry carry{0u, 0u};
     int32_t err = 0;
     FpfSkip skip;
-    {  // the plan's walk of the headers before the chunk (pads [2..7], covt_host.cpp fpf_chunk_states)
-        auto slot = [&](int i) -> const int32_t* {
-            return (const int32_t*)((const uint8_t*)(cd + 2 + i / 7) + covt_fpf_state_byte(i % 7));
-        };
-        if (uni(*slot(0)) == 1) {
-            const int l = lane_id();
-            skip.done = uni(*slot(1));
-            skip.cur0 = uni(*slot(2));
-            skip.pk = uni(*slot(3));
-            skip.xc = l <= 32 ? *slot(4 + l) : 0;
-        }
+    // the plan's walk of the headers before the chunk (covt_split_plan.h: the state slots)
+    if (uni(*fpf_state_slot(cd, kFpfStPresent)) == 1) {
+        const int l = lane_id();
+        skip.done = uni(*fpf_state_slot(cd, kFpfStPage));
+        skip.cur0 = uni(*fpf_state_slot(cd, kFpfStHeader));
+        skip.pk = uni(*fpf_state_slot(cd, kFpfStWord));
+        skip.xc = l <= 32 ? *fpf_state_slot(cd, kFpfStCursor + l) : 0;
     }
     // The delta ops are linear in the carry: one decode stores the chunk's values with its own running
     // sums (from 0), publishes them, and after the look-back adds the predecessors' sums in place (an
@@ -2714,21 +2708,20 @@ __device__ __forceinline__ void run_fastpfor_chunk(Ctx& c, int32_t v0, int32_t v
     }
 }
 
-// One chunk of a split ORC RLE stream: whole groups, located by the plan's host walk (pads: [1] the
-// chunk's bytes [s, e), [2] its values [v0, v0 + nv), [3] the stream's consumed bytes).  Groups carry
+// One chunk of a split ORC RLE stream: whole groups, located by the plan's walk (covt_split_plan.h: the
+// chunk's bytes [s, e), its values [v0, v0 + nv) and the stream's consumed bytes).  Groups carry
 // no state across, so a chunk needs no look-back: it decodes like a stream of its own into its slice
 // of the stream's output.  The stream's result entry (zeroed before the launch) takes the first chunk's
 // consumed count and the lowest failing status (the plan splits only streams whose group structure it
 // walked: what remains is the GeometryType range check, BAD_HEADER from any chunk).
 __device__ __forceinline__ void run_rle_chunk(Ctx& c, const covt_stream_desc* __restrict__ cd, int32_t chunk, covt_stream_result* res,
                               int64_t t) {
-    const int32_t s = (int32_t)cd[1].in_off, e = (int32_t)cd[1].out_off;
-    const int32_t v0 = (int32_t)cd[2].in_off, nv = (int32_t)cd[2].out_off;
-    c.sb += s;
-    c.avail = c.byte_length = e - s;
-    c.n = v0 + nv;
-    if (c.op == COVT_OP_BYTE_RLE_U8 || c.op == COVT_OP_BYTE_RLE_RAW) run_rle_byte(c, v0, true);
-    else run_rle_int(c, v0);
+    const SplitChunk ch = split_rle_chunk(cd);
+    c.sb += ch.s;
+    c.avail = c.byte_length = ch.e - ch.s;
+    c.n = ch.v0 + ch.nv;
+    if (c.op == COVT_OP_BYTE_RLE_U8 || c.op == COVT_OP_BYTE_RLE_RAW) run_rle_byte(c, ch.v0, true);
+    else run_rle_int(c, ch.v0);
     if (lane_id() == 0) {
         // (status, consumed) as one 64-bit word (status in the low half): consumed stays 0 once any chunk
         // failed, whichever of that chunk and chunk 0 comes first
@@ -2742,7 +2735,7 @@ __device__ __forceinline__ void run_rle_chunk(Ctx& c, const covt_stream_desc* __
                 old = atomicCAS(w, seen, (unsigned long long)(uint32_t)(st < c.err ? st : c.err));
             } while (old != seen);
         } else if (chunk == 0) {
-            atomicCAS(w, 0ull, (unsigned long long)(uint32_t)cd[3].in_off << 32);
+            atomicCAS(w, 0ull, (unsigned long long)split_rle_consumed(cd) << 32);
         }
     }
 }
@@ -2761,8 +2754,9 @@ __device__ __forceinline__ int64_t decode_split_chunk(WaveSmem* sm, const uint8_
     if (t >= n_chunks) return -1;
     // chunks are pieces of the launch's longest streams: the same raised priority as a long stream's wave
     __builtin_amdgcn_s_setprio(COVT_CHUNK_PRIO);
-    const covt_stream_desc d = descs[kSplitSlots * t];
-    const covt_stream_desc rg = descs[kSplitSlots * t + 1];  // the chunk's byte range
+    const covt_stream_desc* group = descs + kSplitSlots * t;
+    const covt_stream_desc d = group[0];
+    const covt_stream_desc rg = group[kSplitPadRange];
     Ctx c;
     c.sm = sm;
     c.sb = in + d.in_off;
@@ -2786,18 +2780,19 @@ __device__ __forceinline__ int64_t decode_split_chunk(WaveSmem* sm, const uint8_
                 for (int k = 0; k < kPhases - 2; ++k) r[2 + k] = c.ph[k];
             }
         }
-    } phase_out{c, descs + kSplitSlots * t};
+    } phase_out{c, group};
 #endif
-    const int32_t chunk = d.avail, s = (int32_t)rg.in_off, e = (int32_t)rg.out_off;
+    const SplitChunk ch = split_range(rg);  // bytes, or values for FastPFOR
+    const int32_t chunk = split_chunk_index(d), s = ch.s, e = ch.e;
     if constexpr (K == kSplitRle) {
-        run_rle_chunk(c, descs + kSplitSlots * t, chunk, res, t);
+        run_rle_chunk(c, group, chunk, res, t);
         return t;
     }
     if constexpr (FPF) {
         switch (d.op) {
-        case COVT_OP_FPF_ZZ_DELTA_I32: run_fastpfor_chunk<COVT_OP_FPF_ZZ_DELTA_I32>(c, s, e, chunk, res, t, descs + kSplitSlots * t); break;
-        case COVT_OP_FPF_ZZ_DELTA_XY: run_fastpfor_chunk<COVT_OP_FPF_ZZ_DELTA_XY>(c, s, e, chunk, res, t, descs + kSplitSlots * t); break;
-        default: run_fastpfor_chunk<COVT_OP_FPF_DELTA_MORTON>(c, s, e, chunk, res, t, descs + kSplitSlots * t); break;
+        case COVT_OP_FPF_ZZ_DELTA_I32: run_fastpfor_chunk<COVT_OP_FPF_ZZ_DELTA_I32>(c, s, e, chunk, res, t, group); break;
+        case COVT_OP_FPF_ZZ_DELTA_XY: run_fastpfor_chunk<COVT_OP_FPF_ZZ_DELTA_XY>(c, s, e, chunk, res, t, group); break;
+        default: run_fastpfor_chunk<COVT_OP_FPF_DELTA_MORTON>(c, s, e, chunk, res, t, group); break;
         }
         return t;
     }

@@ -1196,11 +1196,6 @@ int covt_decode_fastpfor_delta_morton_codes(const uint8_t* buf, size_t buf_len, 
                     2 * (size_t)std::max(n_vertices, 0));
 }
 
-// Test hook (not in covt.h): the plan's FastPFOR chunk start states for one stream, nch x 42 int32
-// (the slots of pads [2..7], covt_internal.h kFpfStateSlots), as fpf_chunk_states computes them.
-int covt_debug_fpf_chunk_states(const uint8_t* stream, int32_t byte_length, int32_t num_values, int64_t unit,
-                                int64_t nch, int32_t* out);
-
 int covt_plan_create(const uint8_t* bytes, const uint64_t* tile_offsets, const uint64_t* tile_sizes,
                      int32_t n_tiles, int32_t format, int32_t id_mode, covt_plan** out) {
     return covt_plan_create_ex(bytes, tile_offsets, tile_sizes, n_tiles, format, id_mode, 0u, out);
@@ -1215,13 +1210,10 @@ namespace {
 // output bytes / 4).  Each chunk: {first byte, end byte, first value, values}; `consumed` = the bytes
 // the one-wave decode reads (through the group that reaches num_values).  Empty when the stream does
 // not frame num_values values in byte_length bytes: its one-wave decode then reports the error.
-struct RleChunk {
-    int32_t s, e, v0, nv;
-};
-std::vector<RleChunk> rle_chunks(const uint8_t* b, int32_t len, int op, int32_t n, int32_t elem, int64_t unit,
-                                 int32_t& consumed) {
+std::vector<SplitChunk> rle_chunks(const uint8_t* b, int32_t len, int op, int32_t n, int32_t elem, int64_t unit,
+                                   int32_t& consumed) {
     const bool byte_rle = op == COVT_OP_BYTE_RLE_U8 || op == COVT_OP_BYTE_RLE_RAW;
-    std::vector<RleChunk> ch;
+    std::vector<SplitChunk> ch;
     int32_t pos = 0, v = 0, cs = 0, cv = 0;
     auto varint = [&]() {
         do {
@@ -1232,7 +1224,7 @@ std::vector<RleChunk> rle_chunks(const uint8_t* b, int32_t len, int op, int32_t 
     while (v < n) {
         if (pos >= len) return {};
         if ((int64_t)(pos - cs) + (int64_t)(v - cv) * elem / 4 >= unit) {  // cut before this group
-            ch.push_back(RleChunk{cs, pos, cv, v - cv});
+            ch.push_back(SplitChunk{cs, pos, cv, v - cv});
             cs = pos;
             cv = v;
         }
@@ -1259,86 +1251,59 @@ std::vector<RleChunk> rle_chunks(const uint8_t* b, int32_t len, int op, int32_t 
             v += cnt;
         }
     }
-    ch.push_back(RleChunk{cs, pos, cv, n - cv});
+    ch.push_back(SplitChunk{cs, pos, cv, n - cv});
     consumed = pos;
     if (ch.size() < 2) ch.clear();
     return ch;
 }
 
 // FastPFOR split chunks: each chunk's state at its first block, from a host walk of the page directories
-// and block headers (JavaFastPFOR FastPFOR.decodePage framing, read exactly as run_fastpfor's pre-walk
-// does): the container offset of the block's header, its packed-word index and the exception cursor of
-// every dataTobePacked array.  The chunk then skips walking up to 255 headers before its range (the
-// critical path of BASELINE config 3).  Stored in the chunk's pads [2..7], seven int32 slots each (all
-// fields but op / num_bits / flags; covt_fpf_state_slot): [0] 1 = present, [1] the page's first value,
-// [2] header offset, [3] packed word, [4 + k] cursor of array k (k = 0..32).  Where the walk cannot
-// follow the framing it stops: later chunks get no state and walk (and report the error) on the device.
+// and block headers (covt_split_plan.h: the framing, shared with the device plan's fpf_states_walk): the
+// container offset of the block's header, its packed-word index and the exception cursor of every
+// dataTobePacked array.  The chunk then skips walking up to 255 headers before its range (the critical
+// path of BASELINE config 3).  kFpfStateSlots int32 per chunk, by the kFpfSt* slots; step 4 copies them into
+// the chunk's pads.  Where the walk cannot follow the framing it stops: later chunks get no state and walk
+// (and report the error) on the device.
+struct FpfBytes {  // the framing's reader over host bytes
+    const uint8_t* b;
+    uint32_t word(int64_t i) const {
+        return ((uint32_t)b[4 * i] << 24) | ((uint32_t)b[4 * i + 1] << 16) | ((uint32_t)b[4 * i + 2] << 8) | b[4 * i + 3];
+    }
+    uint64_t bytes8(int64_t i) const {
+        return (uint64_t)__builtin_bswap32(word(i)) | ((uint64_t)__builtin_bswap32(word(i + 1)) << 32);
+    }
+};
 void fpf_chunk_states(const uint8_t* b, int32_t byte_length, int32_t n, int64_t unit, int64_t nch,
                       std::vector<int32_t>& st) {
     st.assign((size_t)nch * kFpfStateSlots, 0);
     const int64_t nw = byte_length / 4;
-    if (nw <= 0 || unit % 256) return;
-    auto W = [&](int64_t i) -> uint32_t {
-        return ((uint32_t)b[4 * i] << 24) | ((uint32_t)b[4 * i + 1] << 16) | ((uint32_t)b[4 * i + 2] << 8) | b[4 * i + 3];
-    };
-    int32_t L = (int32_t)W(0);
-    if (L < 0) return;
-    L -= L % 256;
-    if (L > n) return;
+    FpfBytes rd{b};
+    const int32_t L = fpf_paged_values(rd, nw, n, unit);
     int64_t p = 1;
     int32_t done = 0;
-    while (done < L) {
-        const int32_t thissize = std::min<int32_t>(L - done, 65536);
-        const int64_t p0 = p;
-        if (p0 >= nw) return;
-        int64_t ie = p0 + (int32_t)W(p0);
-        if (ie < 0 || ie >= nw) return;
-        const int32_t bytesize = (int32_t)W(ie++);
-        if (bytesize < 0 || bytesize > 3 * 65536 / 256 + 65536) return;
-        const int64_t bcw = (bytesize + 3) / 4, bc = ie;
-        if (bc + bcw >= nw) return;
-        ie += bcw;
-        uint32_t bm = W(ie++) & ~1u;  // (bc + bcw < nw)
-        while (bm) {
-            const int32_t k = __builtin_ctz(bm) + 1;
-            bm &= bm - 1;
-            if (ie >= nw) return;
-            const int32_t size = (int32_t)W(ie++);
-            if (size < 0) return;
-            const int64_t groups = ((int64_t)size + 31) / 32;
-            ie += groups * k - ((groups * 32 - size) * k) / 32;
-        }
-        const int32_t bclen = (int32_t)(bcw * 4), nblk = thissize / 256;
-        auto cb = [&](int32_t q) -> uint32_t { return b[4 * bc + (q ^ 3)]; };  // container byte q
-        int32_t cur = 0, xc[33] = {};
-        int64_t pk = p0 + 1;
-        for (int32_t j = 0; j < nblk; ++j) {
-            const int64_t v = (int64_t)done + (int64_t)j * 256;
+    FpfPage pg;
+    while (done < L && fpf_page_dir(rd, nw, p, pg)) {
+        const int32_t thissize = std::min<int32_t>(L - done, kFpfPage);
+        int32_t cur = 0, xc[33] = {}, arr, cnt;
+        int64_t pk = pg.pk;
+        for (int32_t j = 0; j < thissize / kFpfBlock; ++j) {
+            const int64_t v = (int64_t)done + (int64_t)j * kFpfBlock;
             if (j > 0 && v % unit == 0 && v / unit < nch) {  // chunk v / unit starts at block j of this page
                 int32_t* s = st.data() + (size_t)(v / unit) * kFpfStateSlots;
-                s[0] = 1;
-                s[1] = done;
-                s[2] = cur;
-                s[3] = (int32_t)pk;
-                for (int k = 0; k <= 32; ++k) s[4 + k] = xc[k];
+                s[kFpfStPresent] = 1;
+                s[kFpfStPage] = done;
+                s[kFpfStHeader] = cur;
+                s[kFpfStWord] = (int32_t)pk;
+                for (int k = 0; k <= 32; ++k) s[kFpfStCursor + k] = xc[k];
             }
-            if (cur + 3 > bclen + 1) return;  // (the device reads the header word through its window)
-            const int32_t hb = (int32_t)(int8_t)cb(cur), ce = (int32_t)cb(cur + 1);
-            const int32_t idx = ce > 0 && cur + 2 < bclen ? (int32_t)(int8_t)cb(cur + 2) - hb : 0;
-            pk += 8 * hb;
-            if (ce > 0 && idx >= 2 && idx <= 32) xc[idx] += ce;
-            cur += ce > 0 ? 3 + ce : 2;
-            if (cur > bclen) return;
+            if (!fpf_block_step(rd, pg, cur, pk, arr, cnt)) return;
+            xc[arr] += cnt;
         }
         done += thissize;
-        p = ie;
+        p = pg.next;
     }
 }
 }  // namespace
-
-extern "C" {
-
-}  // extern "C"
 
 bool covt_resolve_options(const covt_plan_options* in, covt_plan_options& o) {
     covt_plan_options d;
@@ -1538,14 +1503,11 @@ int covt_plan_create_opts(const uint8_t* bytes, const uint64_t* tile_offsets, co
     const size_t ns = p->info.size();
     std::vector<SortKey> keys(ns);
     // split a stream only where one wave decoding it would outlast the launch.  A stream's cost is its
-    // bytes + output bytes / 4 (the launch-order key below; FastPFOR and RLE time follows the values as
-    // much as the bytes): split above COVT_SPLIT_MIN and above the batch's total cost /
+    // bytes + output bytes / 4 (stream_cost, covt_split_plan.h; the launch-order key below too): split
+    // above COVT_SPLIT_MIN and above the batch's total cost /
     // COVT_SPLIT_RATIO (a wave decodes ~0.35 GB/s, the launch ~500 GB/s: a stream over ~1/1400 of the
     // batch is a long pole).  Big batches are throughput-bound and split nothing; single tiles and
     // small batches split their long streams.
-    auto stream_cost = [](const covt_stream_info& s) {
-        return (int64_t)s.byte_length + s.out_elems * s.elem_bytes / 4;
-    };
     int64_t split_min = o.split_min;
     const int64_t split_ratio = o.split_ratio;
     int32_t lane_max = lane_limits(o.lane_max_bytes, o.lane_max_values);
@@ -1571,21 +1533,18 @@ int covt_plan_create_opts(const uint8_t* bytes, const uint64_t* tile_offsets, co
         if (n_lane < o.lane_min_streams) lane_max = -1;
         grow = split_grow_factor(total, o.split_grow);
     }
-    const int64_t split_chunk = o.split_chunk * grow;
-    const int64_t split_values = o.split_values * grow;  // FastPFOR: whole blocks
+    // chunks of split_chunk bytes (varint, RLE) or split_values values (FastPFOR: whole blocks)
+    const SplitRule rule{split_min, o.split_chunk * grow, o.split_values * grow, o.fpf_split_weight};
     // long RLE streams: chunk boundaries from the host walk (stream index -> chunks, consumed)
-    std::unordered_map<size_t, std::pair<std::vector<RleChunk>, int32_t>> rle_split;
-    if (split_min >= 0) {
-        for (size_t i = 0; i < ns; ++i) {
-            const auto& s = p->info[i];
-            if (!split_rle_op(s.op) || stream_cost(s) <= split_min || s.desc_index <= 0) continue;
-            int32_t consumed = 0;
-            auto ch = rle_chunks(bytes + s.in_off, s.byte_length, s.op, s.desc_index, s.elem_bytes, split_chunk,
-                                 consumed);
-            if (!ch.empty()) rle_split.emplace(i, std::make_pair(std::move(ch), consumed));
-        }
+    std::unordered_map<size_t, std::pair<std::vector<SplitChunk>, int32_t>> rle_split;
+    for (size_t i = 0; split_min >= 0 && i < ns; ++i) {
+        const auto& s = p->info[i];
+        if (!split_rle_candidate(s.op, s.desc_index, stream_cost(s), split_min)) continue;
+        int32_t consumed = 0;
+        auto ch = rle_chunks(bytes + s.in_off, s.byte_length, s.op, s.desc_index, s.elem_bytes, rule.chunk_bytes,
+                             consumed);
+        if (!ch.empty()) rle_split.emplace(i, std::make_pair(std::move(ch), consumed));
     }
-    const int64_t fpf_w = o.fpf_split_weight;
     // descriptors per stream: 1, or COVT_SPLIT_SLOTS per chunk of a split stream
     std::vector<int32_t> ndesc(ns);
     par_for(n_thr, (int64_t)ns, [&](int64_t i0, int64_t i1) {
@@ -1594,15 +1553,10 @@ int covt_plan_create_opts(const uint8_t* bytes, const uint64_t* tile_offsets, co
             const auto& s = p->info[i];
             const bool lane = lane_stream(s.op, s.desc_index, s.byte_length, lane_max);
             const auto rs = rle_split.empty() ? rle_split.end() : rle_split.find(i);
-            const bool rsplit = rs != rle_split.end();
-            // (FastPFOR: a wave's time follows the blocks, i.e. the values: their output counts fpf_w times)
-            const int64_t scost = split_fpf_op(s.op) ? stream_cost(s) + (fpf_w - 1) * (s.out_elems * s.elem_bytes / 4)
-                                                     : stream_cost(s);
-            const bool split = split_stream(s.op, s.desc_index, scost, split_min, split_values) || rsplit;
-            const uint64_t fam = split ? (uint64_t)(split_fpf_op(s.op) ? COVT_FAMILY_SPLIT_FPF
-                                                    : rsplit           ? COVT_FAMILY_SPLIT_RLE
-                                                                       : COVT_FAMILY_SPLIT)
-                                 : lane ? (uint64_t)COVT_FAMILY_LANE : (uint64_t)covt_op_family_of(s.op);
+            SplitChoice sc = split_choice(s, s.desc_index, lane ? COVT_FAMILY_LANE : covt_op_family_of(s.op), rule);
+            if (rs != rle_split.end())  // the walk framed it in chunks
+                sc = SplitChoice{COVT_FAMILY_SPLIT_RLE, (int64_t)rs->second.first.size() * COVT_SPLIT_SLOTS};
+            const uint64_t fam = (uint64_t)sc.fam;
 #ifdef COVT_EXACT_ORDER  // (A/B: the exact cost-descending order of rounds 1-4)
             const uint64_t cost = std::min<uint64_t>((uint64_t)stream_cost(s), (1ull << 48) - 1);
             keys[i] = SortKey{(fam << 60) | ((lane ? (uint64_t)s.op : 0ull) << 52) | ((1ull << 48) - 1 - cost),
@@ -1610,15 +1564,7 @@ int covt_plan_create_opts(const uint8_t* bytes, const uint64_t* tile_offsets, co
 #else
             keys[i] = SortKey{launch_key((uint32_t)fam, fam == COVT_FAMILY_LANE, s.op, stream_cost(s)), (uint32_t)i};
 #endif
-            int64_t nd = 1;
-            if (rsplit) {
-                nd = (int64_t)rs->second.first.size() * COVT_SPLIT_SLOTS;
-            } else if (split) {
-                const bool fpf = fam == COVT_FAMILY_SPLIT_FPF;
-                const int64_t unit = fpf ? split_values : split_chunk, tot = fpf ? s.desc_index : s.byte_length;
-                nd = (tot + unit - 1) / unit * COVT_SPLIT_SLOTS;
-            }
-            ndesc[i] = (int32_t)nd;
+            ndesc[i] = (int32_t)sc.ndesc;
         }
     });
     radix_sort(keys);  // stable: ties in tile order
@@ -1649,56 +1595,25 @@ int covt_plan_create_opts(const uint8_t* bytes, const uint64_t* tile_offsets, co
             d.flags = fam == COVT_FAMILY_LANE ? COVT_DESC_LANE : 0;
             si.desc_index = (int32_t)o;
             for (int64_t q = 0; q < ndesc[i]; ++q) p->desc_stream[o + (size_t)q] = (int64_t)i;
-            if (fam != COVT_FAMILY_SPLIT && fam != COVT_FAMILY_SPLIT_FPF && fam != COVT_FAMILY_SPLIT_RLE) {
+            if (!split_family(fam)) {
                 p->descs[o] = d;
                 continue;
             }
-            // RLE: the host walk's chunks
-            auto rs = rle_split.find(i);
-            if (rs != rle_split.end()) {
-                const auto& ch = rs->second.first;
-                for (size_t c = 0; c < ch.size(); ++c) {
-                    covt_stream_desc cd = d;
-                    cd.flags = COVT_DESC_SPLIT | COVT_DESC_SPLIT_RLE;
-                    cd.avail = (int32_t)c;
-                    p->descs[o++] = cd;
-                    for (int q = 1; q < COVT_SPLIT_SLOTS; ++q) {
-                        covt_stream_desc pd{};
-                        pd.flags = COVT_DESC_SPLIT_PAD | COVT_DESC_SPLIT_RLE;
-                        if (q == 1) pd.in_off = (uint64_t)ch[c].s, pd.out_off = (uint64_t)ch[c].e;
-                        if (q == 2) pd.in_off = (uint64_t)ch[c].v0, pd.out_off = (uint64_t)ch[c].nv;
-                        if (q == 3) pd.in_off = (uint64_t)rs->second.second;
-                        p->descs[o++] = pd;
-                    }
-                }
-                continue;
-            }
-            // chunk c: bytes [c * split_chunk, min((c + 1) * split_chunk, byte_length)) of a varint stream,
-            // values [c * split_values, min((c + 1) * split_values, num_values)) of a FastPFOR stream
-            const bool fpf = fam == COVT_FAMILY_SPLIT_FPF;
-            const uint16_t fflag = fpf ? COVT_DESC_SPLIT_FPF : 0;
-            const int64_t unit = fpf ? split_values : split_chunk, total = fpf ? d.num_values : d.byte_length;
-            const int64_t nch = (total + unit - 1) / unit;
+            // the chunk groups (covt_split_plan.h).  RLE: the host walk's chunks; chunk c of a varint stream:
+            // bytes [c * unit, min((c + 1) * unit, byte_length)); of a FastPFOR stream: values likewise, and
+            // the walked start states in its pads
+            const bool fpf = fam == COVT_FAMILY_SPLIT_FPF, rle = fam == COVT_FAMILY_SPLIT_RLE;
+            const auto rs = rle_split.find(i);
+            const int64_t unit = fpf ? rule.chunk_values : rule.chunk_bytes, total = fpf ? d.num_values : d.byte_length;
+            const int64_t nch = ndesc[i] / COVT_SPLIT_SLOTS;
             std::vector<int32_t> fst;
             if (fpf) fpf_chunk_states(bytes + si.in_off, si.byte_length, d.num_values, unit, nch, fst);
-            for (int64_t c = 0; c < nch; ++c) {
-                covt_stream_desc cd = d;
-                cd.flags = COVT_DESC_SPLIT | fflag;
-                cd.avail = (int32_t)c;
-                p->descs[o++] = cd;
-                for (int q = 1; q < COVT_SPLIT_SLOTS; ++q) {
-                    covt_stream_desc pd{};
-                    pd.flags = COVT_DESC_SPLIT_PAD | fflag;
-                    if (q == 1) {
-                        pd.in_off = (uint64_t)(c * unit);
-                        pd.out_off = (uint64_t)std::min<int64_t>((c + 1) * unit, total);
-                    }
-                    if (fpf && q >= 2)
-                        for (int k = 0; k < 7; ++k)
-                            std::memcpy((uint8_t*)&pd + covt_fpf_state_byte(k), &fst[(size_t)c * kFpfStateSlots + (size_t)(q - 2) * 7 + (size_t)k],
-                                        4);
-                    p->descs[o++] = pd;
-                }
+            for (int64_t c = 0; c < nch; ++c, o += COVT_SPLIT_SLOTS) {
+                const SplitChunk ch = rle ? rs->second.first[(size_t)c] : split_unit_chunk(c, unit, total);
+                for (int q = 0; q < COVT_SPLIT_SLOTS; ++q)
+                    p->descs[o + (size_t)q] = split_slot_desc(d, fam, c, q, ch, rle ? rs->second.second : 0);
+                for (int m = 0; fpf && m < kFpfStateSlots; ++m)
+                    std::memcpy(fpf_state_slot(&p->descs[o], m), &fst[(size_t)c * kFpfStateSlots + (size_t)m], 4);
             }
         }
     });
@@ -1853,7 +1768,7 @@ void build_shards(const covt_plan* p, const std::vector<int32_t>& devs, std::vec
         const covt_stream_info& si = p->info[(size_t)i];
         HostShard& h = *out[(size_t)shard_of_tile[(size_t)si.tile]];
         covt_stream_desc d = p->descs[k];
-        if (!(d.flags & COVT_DESC_SPLIT_PAD)) {  // pads carry stream-relative chunk ranges
+        if (!split_is_pad(d)) {  // pads carry stream-relative chunk ranges
             d.in_off -= h.in_lo;
             d.out_off -= (uint64_t)h.out_lo;
         }
@@ -2203,6 +2118,8 @@ int covt_plan_properties_host(const covt_plan* p, const uint8_t* bytes, uint64_t
 
 }  // extern "C"
 
+// Test hook (not in covt.h): the plan's FastPFOR chunk start states for one stream, nch x 42 int32
+// (the slots of pads [2..7], covt_split_plan.h kFpfStateSlots), as fpf_chunk_states computes them.
 extern "C" int covt_debug_fpf_chunk_states(const uint8_t* stream, int32_t byte_length, int32_t num_values, int64_t unit,
                                            int64_t nch, int32_t* out) {
     if (!out || nch < 0 || byte_length < 0 || (!stream && byte_length)) return COVT_ERR_INVALID_ARG;

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "covt.h"
+#include "covt_split_plan.h"  // split chunks: descriptor layout, split rules, FastPFOR framing
 
 extern "C" {
 // Enqueues the decode kernel of one family (covt_decode.hip) on `stream` over descriptors
@@ -103,45 +104,5 @@ inline int desc_family(const covt_stream_desc& d) {
                                                  : COVT_FAMILY_SPLIT;
     return (d.flags & COVT_DESC_LANE) ? COVT_FAMILY_LANE : covt_op_family_of(d.op);
 }
-// Plan rule for split streams: the Java-capped int32 varint ops (value ends are local: every byte
-// with bit 7 clear ends a value, DecodingUtils.java:157-186), longer than split_min bytes.
-__host__ __device__ inline bool split_op(int op) {
-    return op == COVT_OP_VARINT_I32 || op == COVT_OP_VARINT_ZZ_I32 || op == COVT_OP_VARINT_ZZ_DELTA_I32 ||
-           op == COVT_OP_VARINT_ZZ_DELTA_XY || op == COVT_OP_VARINT_DELTA_MORTON || op == COVT_OP_VARINT_I32_AS_I64 ||
-           op == COVT_OP_VARINT_ZZ_I32_AS_I64 || op == COVT_OP_VARINT_ZZ_DELTA_I64 || op == COVT_OP_VARINT_U64 ||
-           op == COVT_OP_VARINT_ZZ_S64;
-}
-// FastPFOR ops whose long streams split into value chunks.  The chunk kernel (covt_decode.hip
-// run_fastpfor_chunk) adds a chunk's carry in place for the linear int32 ops (ZZ_DELTA_I32, ZZ_DELTA_XY) and
-// decodes Morton twice; an op added here needs a carry rule there (static_asserts guard it).
-__host__ __device__ inline bool split_fpf_op(int op) {
-    return op == COVT_OP_FPF_ZZ_DELTA_I32 || op == COVT_OP_FPF_ZZ_DELTA_XY || op == COVT_OP_FPF_DELTA_MORTON;
-}
-__host__ __device__ inline bool split_rle_op(int op) {
-    return op == COVT_OP_RLE_U64 || op == COVT_OP_RLE_I32 || op == COVT_OP_RLE_S64 || op == COVT_OP_BYTE_RLE_U8 ||
-           op == COVT_OP_BYTE_RLE_RAW;
-}
-// FastPFOR streams split by values into chunks of whole blocks (their own headers and page directories
-// locate every block), at least two chunks
-// cost: the stream's bytes + output bytes / 4 (covt_plan_create's launch-order key)
-__host__ __device__ inline bool split_stream(int op, int32_t num_values, int64_t cost, int64_t split_min, int64_t split_values) {
-    if (split_min < 0 || num_values <= 0 || cost <= split_min) return false;
-    if (split_fpf_op(op)) return num_values > split_values && !(op == COVT_OP_FPF_ZZ_DELTA_XY && (num_values & 1));
-    return split_op(op) && !(op == COVT_OP_VARINT_ZZ_DELTA_XY && (num_values & 1));
-}
-
-// covt_plan_options.split_grow: chunks (split_chunk bytes, split_values values) doubled for plans of >= 4 MiB of
-// cost and quadrupled from 48 MiB.  In a plan whose streams fill the chip a chunk wave shares its SIMD with
-// the crowd, and its fixed costs (start state, look-back) weigh more than a longer body
-// (profiles/r05/shard_sizes.txt: 2 KiB chunks best for one tile, 4 KiB for 8-30 MiB plans, 8 KiB above)
-__host__ __device__ inline int64_t split_grow_factor(int64_t total_cost, int32_t grow) {
-    if (!grow) return 1;
-    return total_cost >= (48ll << 20) ? 4 : total_cost >= (4ll << 20) ? 2 : 1;
-}
-
-// FastPFOR split chunks: the host-walked start state in pads [2..7] of the chunk (covt_host.cpp
-// fpf_chunk_states): seven int32 slots per pad, every field but op / num_bits / flags
-constexpr int kFpfStateSlots = 42;
-__host__ __device__ constexpr int covt_fpf_state_byte(int k) { return k < 6 ? 4 * k : 28; }
 
 #endif

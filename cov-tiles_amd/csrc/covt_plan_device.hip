@@ -542,7 +542,7 @@ __device__ __forceinline__ uint32_t entry_key(int32_t op, int32_t nv, int32_t bl
                                               int32_t lm) {
     const bool lane = lane_stream(op, nv, bl, lm);
     const uint32_t fam = lane ? (uint32_t)COVT_FAMILY_LANE : (uint32_t)covt_op_family(op);
-    return launch_key(fam, lane, op, (int64_t)bl + out_elems * elem / 4);
+    return launch_key(fam, lane, op, stream_cost(bl, out_elems, elem));
 }
 
 // ---- speculative Gen C walk (one wave per tile) -------------------------------------------------------
@@ -977,11 +977,10 @@ struct CountEmit {
         choose_op(s, id_mode, op, nvals, elem, oe);
         if (slots && writer && n < kSlots) slots[n] = s;
         ++n;
-        const int64_t ob = (op == COVT_OP_NONE ? 0 : oe) * elem;
-        out = align_out(out + ob);
-        const int64_t c = (int64_t)s.bl + ob / 4;  // covt_plan_create's stream_cost
-        cost += c;
-        const int64_t sc = split_fpf_op(op) ? c + (fpf_w - 1) * (ob / 4) : c;
+        const int64_t no = op == COVT_OP_NONE ? 0 : oe;  // the elements it outputs
+        out = align_out(out + no * elem);
+        cost += stream_cost(s.bl, no, elem);
+        const int64_t sc = split_cost(op, s.bl, no, elem, fpf_w);
         cmax = sc > cmax ? sc : cmax;
     }
     // the slotted records' sums (defer), one lane per record: output bytes (each stream's slice aligned, so
@@ -997,11 +996,10 @@ struct CountEmit {
             int64_t nvals, oe;
             const RawStream r = slots[j];
             choose_op(r, id_mode, op, nvals, elem, oe);
-            const int64_t ob = (op == COVT_OP_NONE ? 0 : oe) * elem;
-            so += align_out(ob);
-            const int64_t c = (int64_t)r.bl + ob / 4;
-            sc += c;
-            const int64_t x = split_fpf_op(op) ? c + (fpf_w - 1) * (ob / 4) : c;
+            const int64_t no = op == COVT_OP_NONE ? 0 : oe;
+            so += align_out(no * elem);
+            sc += stream_cost(r.bl, no, elem);
+            const int64_t x = split_cost(op, r.bl, no, elem, fpf_w);
             sm = x > sm ? x : sm;
         }
 #pragma unroll
@@ -1311,8 +1309,7 @@ __global__ void stream_keys(const covt_stream_info* info, const int32_t* nvals, 
         const int32_t lm = (int64_t)totals[T_LANE] < lane_min ? -1 : lane_max;
         const bool lane = lane_stream(s.op, nvals[i], s.byte_length, lm);
         fam = sfam ? (uint32_t)sfam[i] : lane ? (uint32_t)COVT_FAMILY_LANE : (uint32_t)covt_op_family(s.op);
-        const int64_t c = (int64_t)s.byte_length + s.out_elems * s.elem_bytes / 4;
-        keys[i] = launch_key(fam, fam == COVT_FAMILY_LANE, s.op, c);
+        keys[i] = launch_key(fam, fam == COVT_FAMILY_LANE, s.op, stream_cost(s));
         if (sndesc) atomicAdd(&fam_n[fam], (unsigned long long)sndesc[i]);
     }
     if (!sndesc) {  // one descriptor per stream: a ballot per family (same-address LDS atomics serialized)
@@ -1504,30 +1501,20 @@ __global__ void fill_descs(covt_stream_info* info, const int32_t* nvals, const u
 enum { T_NRLE = 6, T_NFPF = 7 };  // list lengths (totals slots)
 
 __global__ void split_mark(const covt_stream_info* __restrict__ info, const int32_t* __restrict__ nvals, int64_t n,
-                           int32_t lane_max, int64_t lane_min, int64_t smin, int64_t split_chunk, int64_t split_values,
-                           int64_t fpf_w, unsigned long long* __restrict__ totals, uint8_t* __restrict__ sfam,
-                           int64_t* __restrict__ sndesc, uint32_t* __restrict__ rle_list, uint32_t* __restrict__ fpf_list) {
+                           int32_t lane_max, int64_t lane_min, SplitRule rule, unsigned long long* __restrict__ totals,
+                           uint8_t* __restrict__ sfam, int64_t* __restrict__ sndesc, uint32_t* __restrict__ rle_list,
+                           uint32_t* __restrict__ fpf_list) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const covt_stream_info& s = info[i];
     const int32_t nv = nvals[i];
     const int32_t lm = (int64_t)totals[T_LANE] < lane_min ? -1 : lane_max;
     const bool lane = lane_stream(s.op, nv, s.byte_length, lm);
-    const int64_t ob4 = s.out_elems * s.elem_bytes / 4, cost = (int64_t)s.byte_length + ob4;
-    const bool fpf = split_fpf_op(s.op);
-    const int64_t scost = fpf ? cost + (fpf_w - 1) * ob4 : cost;
-    const bool split = split_stream(s.op, nv, scost, smin, split_values);
-    int fam = split ? (fpf ? COVT_FAMILY_SPLIT_FPF : COVT_FAMILY_SPLIT) : lane ? COVT_FAMILY_LANE : covt_op_family(s.op);
-    int64_t nd = 1;
-    if (split) {
-        const int64_t unit = fpf ? split_values : split_chunk, tot = fpf ? nv : s.byte_length;
-        nd = (tot + unit - 1) / unit * COVT_SPLIT_SLOTS;
-        if (fpf) fpf_list[atomicAdd(&totals[T_NFPF], 1ull)] = (uint32_t)i;
-    } else if (split_rle_op(s.op) && cost > smin && nv > 0) {
-        rle_list[atomicAdd(&totals[T_NRLE], 1ull)] = (uint32_t)i;
-    }
-    sfam[i] = (uint8_t)fam;
-    sndesc[i] = nd;
+    const SplitChoice sc = split_choice(s, nv, lane ? COVT_FAMILY_LANE : covt_op_family(s.op), rule);
+    if (sc.fam == COVT_FAMILY_SPLIT_FPF) fpf_list[atomicAdd(&totals[T_NFPF], 1ull)] = (uint32_t)i;
+    else if (split_rle_candidate(s.op, nv, stream_cost(s), rule.split_min)) rle_list[atomicAdd(&totals[T_NRLE], 1ull)] = (uint32_t)i;
+    sfam[i] = (uint8_t)sc.fam;
+    sndesc[i] = sc.ndesc;
 }
 
 // One stream's bytes for the split walkers (a wave each, lanes in lockstep): a 4 KiB LDS window refilled
@@ -1561,6 +1548,9 @@ struct StreamRd {
         return win_bytes8(reinterpret_cast<const uint32_t*>(covt_walk_win), ensure(i, 8));
     }
     __device__ __forceinline__ int at(int32_t i) { return (int)(peek8(i) & 0xff); }
+    // the FastPFOR framing's reader (covt_split_plan.h): big-endian word i; the bytes of words i, i + 1
+    __device__ __forceinline__ uint32_t word(int64_t i) { return __builtin_bswap32((uint32_t)peek8((int32_t)(4 * i))); }
+    __device__ __forceinline__ uint64_t bytes8(int64_t i) { return peek8((int32_t)(4 * i)); }
 };
 constexpr size_t kStreamRdLds = StreamRd::kWin + 16;
 
@@ -1686,8 +1676,8 @@ __global__ void gather_ndesc(const uint32_t* __restrict__ order, const int64_t* 
 // streams: rle_chunks_walk<true>).  The first descriptor of a stream sets its desc_index.
 __global__ void fill_split_descs(covt_stream_info* __restrict__ info, const int32_t* __restrict__ nvals,
                                  const uint32_t* __restrict__ order, const int64_t* __restrict__ dpos, int64_t ns,
-                                 int64_t n_desc, const uint8_t* __restrict__ sfam, int64_t split_chunk,
-                                 int64_t split_values, const int4* __restrict__ chunks, const int64_t* __restrict__ rle_base,
+                                 int64_t n_desc, const uint8_t* __restrict__ sfam, SplitRule rule,
+                                 const int4* __restrict__ chunks, const int64_t* __restrict__ rle_base,
                                  const int32_t* __restrict__ rle_cons, covt_stream_desc* __restrict__ desc,
                                  uint32_t* __restrict__ dorder) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1713,48 +1703,28 @@ __global__ void fill_split_descs(covt_stream_info* __restrict__ info, const int3
     d.num_bits = (uint8_t)si.num_bits;
     d.flags = fam == COVT_FAMILY_LANE ? COVT_DESC_LANE : 0;
     d.byte_length = si.byte_length;
-    if (fam != COVT_FAMILY_SPLIT && fam != COVT_FAMILY_SPLIT_FPF && fam != COVT_FAMILY_SPLIT_RLE) {
+    if (!split_family(fam)) {
         desc[j] = d;
         return;
     }
-    const int64_t c = q / COVT_SPLIT_SLOTS, slot = q % COVT_SPLIT_SLOTS;
-    if (fam == COVT_FAMILY_SPLIT_RLE) {  // the chunk records of rle_chunks_walk
-        covt_stream_desc x{};
-        if (slot == 0) {
-            x = d;
-            x.flags = COVT_DESC_SPLIT | COVT_DESC_SPLIT_RLE;
-            x.avail = (int32_t)c;
-        } else {
-            x.flags = COVT_DESC_SPLIT_PAD | COVT_DESC_SPLIT_RLE;
-            const int4 r = chunks[rle_base[i] + c];
-            if (slot == 1) x.in_off = (uint64_t)r.x, x.out_off = (uint64_t)r.y;
-            if (slot == 2) x.in_off = (uint64_t)r.z, x.out_off = (uint64_t)r.w;
-            if (slot == 3) x.in_off = (uint64_t)rle_cons[i];
-        }
-        desc[j] = x;
-        return;
+    // slot q % COVT_SPLIT_SLOTS of chunk c (covt_split_plan.h): RLE chunks from rle_chunks_walk's records
+    const int64_t c = q / COVT_SPLIT_SLOTS;
+    SplitChunk ch;
+    int32_t consumed = 0;
+    if (fam == COVT_FAMILY_SPLIT_RLE) {
+        const int4 r = chunks[rle_base[i] + c];
+        ch = SplitChunk{r.x, r.y, r.z, r.w};
+        consumed = rle_cons[i];
+    } else {
+        const bool fpf = fam == COVT_FAMILY_SPLIT_FPF;
+        ch = split_unit_chunk(c, fpf ? rule.chunk_values : rule.chunk_bytes, fpf ? (int64_t)d.num_values : (int64_t)d.byte_length);
     }
-    const bool fpf = fam == COVT_FAMILY_SPLIT_FPF;
-    const uint16_t fflag = fpf ? COVT_DESC_SPLIT_FPF : 0;
-    if (slot == 0) {
-        d.flags = COVT_DESC_SPLIT | fflag;
-        d.avail = (int32_t)c;
-        desc[j] = d;
-        return;
-    }
-    covt_stream_desc pd{};
-    pd.flags = COVT_DESC_SPLIT_PAD | fflag;
-    if (slot == 1) {
-        const int64_t unit = fpf ? split_values : split_chunk, total = fpf ? (int64_t)d.num_values : (int64_t)d.byte_length;
-        pd.in_off = (uint64_t)(c * unit);
-        pd.out_off = (uint64_t)((c + 1) * unit < total ? (c + 1) * unit : total);
-    }
-    desc[j] = pd;
+    desc[j] = split_slot_desc(d, fam, c, (int)(q % COVT_SPLIT_SLOTS), ch, consumed);
 }
 
 // fpf_chunk_states (covt_host.cpp) for each split FastPFOR stream, one wave each (lanes in lockstep; lane
 // k <= 32 holds the exception cursor of array k): the start state of every chunk the page / block header
-// walk reaches, in the chunk's pads [2..7] (state slot m: pad 2 + m / 7, field m % 7)
+// walk (covt_split_plan.h: the framing, shared with the host) reaches, in the chunk's state slots
 __global__ void fpf_states_walk(const uint8_t* __restrict__ bytes, const covt_stream_info* __restrict__ info,
                                 const int32_t* __restrict__ nvals, const unsigned long long* __restrict__ totals,
                                 const uint32_t* __restrict__ fpf_list, int64_t unit, covt_stream_desc* __restrict__ desc) {
@@ -1770,83 +1740,35 @@ __global__ void fpf_states_walk(const uint8_t* __restrict__ bytes, const covt_st
         r.t = bytes + si.in_off;
         r.len = byte_length;
         r.wo = -0x40000000;
-        auto W = [&](int64_t w) -> uint32_t { return __builtin_bswap32((uint32_t)r.peek8((int32_t)(4 * w))); };
         const int64_t nw = byte_length / 4;
-        if (nw <= 0 || unit % 256) continue;
-        int32_t L = (int32_t)W(0);
-        if (L < 0) continue;
-        L -= L % 256;
-        if (L > n) continue;
+        const int32_t L = fpf_paged_values(r, nw, n, unit);
         int64_t p = 1;
         int32_t done = 0;
+        FpfPage pg;
         bool stop = false;
-        while (done < L && !stop) {
-            const int32_t thissize = L - done < 65536 ? L - done : 65536;
-            const int64_t p0 = p;
-            if (p0 >= nw) break;
-            int64_t ie = p0 + (int32_t)W(p0);
-            if (ie < 0 || ie >= nw) break;
-            const int32_t bytesize = (int32_t)W(ie++);
-            if (bytesize < 0 || bytesize > 3 * 65536 / 256 + 65536) break;
-            const int64_t bcw = (bytesize + 3) / 4, bc = ie;
-            if (bc + bcw >= nw) break;
-            ie += bcw;
-            uint32_t bm = W(ie++) & ~1u;
-            while (bm) {
-                const int32_t k = __builtin_ctz(bm) + 1;
-                bm &= bm - 1;
-                if (ie >= nw) {
-                    stop = true;
-                    break;
-                }
-                const int32_t size = (int32_t)W(ie++);
-                if (size < 0) {
-                    stop = true;
-                    break;
-                }
-                const int64_t groups = ((int64_t)size + 31) / 32;
-                ie += groups * k - ((groups * 32 - size) * k) / 32;
-            }
-            if (stop) break;
-            const int32_t bclen = (int32_t)(bcw * 4), nblk = thissize / 256;
-            // container bytes cur, cur + 1, cur + 2 (byte q at stream byte 4 bc + (q ^ 3)): one 8-byte read
-            // of the two words holding them
-            const int32_t cbase = (int32_t)(4 * bc);
-            int32_t cur = 0, xc = 0;  // xc: this lane's array cursor (lane k <= 32)
-            int64_t pk = p0 + 1;
+        while (done < L && !stop && fpf_page_dir(r, nw, p, pg)) {
+            const int32_t thissize = L - done < kFpfPage ? L - done : kFpfPage, nblk = thissize / kFpfBlock;
+            int32_t cur = 0, xc = 0, arr, cnt;  // xc: this lane's array cursor (lane k <= 32)
+            int64_t pk = pg.pk;
             // the next chunk start past the page's first block (a multiple of unit; no 64-bit division per block)
-            int64_t ci = ((int64_t)done + 256 + unit - 1) / unit, cut = ci * unit;
-            for (int32_t j = 0; j < nblk; ++j) {
-                const int64_t v = (int64_t)done + (int64_t)j * 256;
+            int64_t ci = ((int64_t)done + kFpfBlock + unit - 1) / unit, cut = ci * unit;
+            for (int32_t j = 0; j < nblk && !stop; ++j) {
+                const int64_t v = (int64_t)done + (int64_t)j * kFpfBlock;
                 if (v == cut) {  // chunk ci starts at block j (> 0) of this page
                     const bool own = ci < nch;
                     covt_stream_desc* o = out + (size_t)ci * COVT_SPLIT_SLOTS;
                     ++ci;
                     cut += unit;
-                    const int32_t xv = __shfl(xc, lane >= 4 ? lane - 4 : 0, 64);
-                    const int32_t val = lane == 0 ? 1 : lane == 1 ? done : lane == 2 ? cur : lane == 3 ? (int32_t)pk : xv;
-                    if (own && lane < 37) *(int32_t*)((uint8_t*)(o + 2 + lane / 7) + covt_fpf_state_byte(lane % 7)) = val;
+                    const int32_t xv = __shfl(xc, lane >= kFpfStCursor ? lane - kFpfStCursor : 0, 64);
+                    const int32_t val = lane == kFpfStPresent ? 1 : lane == kFpfStPage ? done : lane == kFpfStHeader ? cur
+                                        : lane == kFpfStWord  ? (int32_t)pk : xv;
+                    if (own && lane < kFpfStUsed) *fpf_state_slot(o, lane) = val;
                 }
-                if (cur + 3 > bclen + 1) {
-                    stop = true;
-                    break;
-                }
-                const uint64_t x = r.peek8(cbase + 4 * (cur >> 2));
-                auto cb = [&](int32_t q) -> uint32_t {
-                    return (uint32_t)(x >> (8 * (4 * ((q >> 2) - (cur >> 2)) + ((q & 3) ^ 3)))) & 0xffu;
-                };
-                const int32_t hb = (int32_t)(int8_t)cb(cur), ce = (int32_t)cb(cur + 1);
-                const int32_t idx = ce > 0 && cur + 2 < bclen ? (int32_t)(int8_t)cb(cur + 2) - hb : 0;
-                pk += 8 * hb;
-                if (ce > 0 && idx >= 2 && idx <= 32 && lane == idx) xc += ce;
-                cur += ce > 0 ? 3 + ce : 2;
-                if (cur > bclen) {
-                    stop = true;
-                    break;
-                }
+                stop = !fpf_block_step(r, pg, cur, pk, arr, cnt);
+                if (lane == arr) xc += cnt;
             }
             done += thissize;
-            p = ie;
+            p = pg.next;
         }
     }
 }
@@ -2473,7 +2395,7 @@ __global__ void __launch_bounds__(256) prop_sizes(const PropRaw* __restrict__ re
             ob = align_out(ob + bytes);
             a[PA_PAYLOAD] += (unsigned long long)bytes;
             a[PA_LANE] += lane_stream(ps.op[k], (int32_t)ps.count[k], bl, lane_max) ? 1ull : 0ull;
-            const unsigned long long c = (unsigned long long)((int64_t)bl + bytes / 4);
+            const unsigned long long c = (unsigned long long)stream_cost(bl, ps.count[k], ps.elem[k]);
             a[PA_COST] += c;
             a[PA_CMAX] = c > a[PA_CMAX] ? c : a[PA_CMAX];
         }
@@ -3076,7 +2998,7 @@ int PlanBuild::stream_part(bool sp) {
     int64_t smin = 0;
     const bool splitting = !sp && splits(ns, smin);
     const int64_t grow = split_grow_factor(hd[2], o.split_grow);
-    const int64_t schunk = o.split_chunk * grow, svalues = o.split_values * grow;
+    const SplitRule rule{smin, o.split_chunk * grow, o.split_values * grow, o.fpf_split_weight};
     size_t dscan_tmp = 0;
     if (splitting)
         HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, dscan_tmp, (int64_t*)nullptr, (int64_t*)nullptr,
@@ -3145,10 +3067,10 @@ int PlanBuild::stream_part(bool sp) {
         int32_t* rle_cons = a_rc.at(sa);
         int4* chunks = a_ch.at(sa);
         const int walkers = (int)std::min<int64_t>(ns, 1024);
-        split_mark<<<blocks_s, 256, 0, s>>>(p->d_info, nvals, ns, lane_max, o.lane_min_streams, smin, schunk,
-                                            svalues, o.fpf_split_weight, totals, sfam, sndesc, rle_list, fpf_list);
+        split_mark<<<blocks_s, 256, 0, s>>>(p->d_info, nvals, ns, lane_max, o.lane_min_streams, rule, totals, sfam, sndesc,
+                                            rle_list, fpf_list);
         HIP_TRY(hipGetLastError());
-        rle_chunks_walk<<<walkers, 64, kStreamRdLds, s>>>(d_bytes, p->d_info, nvals, totals, rle_list, schunk, sfam,
+        rle_chunks_walk<<<walkers, 64, kStreamRdLds, s>>>(d_bytes, p->d_info, nvals, totals, rle_list, rule.chunk_bytes, sfam,
                                                           sndesc, chunks, chunk_cap, rle_base, rle_cons);
         HIP_TRY(hipGetLastError());
         stream_keys<<<blocks_s, 256, 0, s>>>(p->d_info, nvals, ns, lane_max, o.lane_min_streams, totals, q0, sfam, sndesc);
@@ -3167,11 +3089,10 @@ int PlanBuild::stream_part(bool sp) {
         p->n_descs = nd;
         p->d_desc = a_desc.at(p->desc_arena);
         p->d_order = a_dord.at(p->desc_arena);
-        fill_split_descs<<<(int)((nd + 255) / 256), 256, 0, s>>>(p->d_info, nvals, v1, dpos, ns, nd, sfam, schunk,
-                                                                 svalues, chunks, rle_base, rle_cons, p->d_desc,
-                                                                 p->d_order);
+        fill_split_descs<<<(int)((nd + 255) / 256), 256, 0, s>>>(p->d_info, nvals, v1, dpos, ns, nd, sfam, rule, chunks,
+                                                                 rle_base, rle_cons, p->d_desc, p->d_order);
         HIP_TRY(hipGetLastError());
-        fpf_states_walk<<<walkers, 64, kStreamRdLds, s>>>(d_bytes, p->d_info, nvals, totals, fpf_list, svalues, p->d_desc);
+        fpf_states_walk<<<walkers, 64, kStreamRdLds, s>>>(d_bytes, p->d_info, nvals, totals, fpf_list, rule.chunk_values, p->d_desc);
         HIP_TRY(hipGetLastError());
     }
     return COVT_OK;

@@ -152,7 +152,7 @@ enum covt_op {
 #define COVT_DESC_SPLIT 0x2u
 #define COVT_DESC_SPLIT_PAD 0x4u
 #define COVT_DESC_SPLIT_FPF 0x8u /* with SPLIT / SPLIT_PAD: a FastPFOR stream's chunk (pads [2..7]: the plan's
-                                  * host walk of the headers before it -- int32 slots in every field but
+                                  * walk of the headers before it -- int32 slots in every field but
                                   * op / num_bits / flags; all zero = none, the chunk walks them itself) */
 #define COVT_DESC_SPLIT_RLE 0x10u /* with SPLIT / SPLIT_PAD: an ORC RLE stream's chunk (whole groups, located by the
                                    * plan; pads [1] bytes [s, e), [2] values (first, count), [3] consumed) */
@@ -197,7 +197,7 @@ typedef struct covt_plan_options {
                                   every wave slot busy, and there the chunks' header re-walks and look-back cost
                                   more than the long poles they shorten */
     int32_t split_grow;        /* 1 (default): split_chunk / split_values doubled for plans of >= 4 MiB of cost and
-                                  quadrupled from 48 MiB (covt_internal.h split_grow_factor); 0: fixed */
+                                  quadrupled from 48 MiB (covt_split_plan.h split_grow_factor); 0: fixed */
 } covt_plan_options;
 void covt_plan_options_init(covt_plan_options* opts);
 

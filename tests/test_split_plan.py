@@ -344,3 +344,24 @@ def test_split_grow_and_max_streams(covt):
     over = covt.Plan.from_tiles(tiles, options=covt.PlanOptions(**dict(base, split_max_streams=n - 1)))
     assert at.family_counts[covt.FAMILY_SPLIT:].sum() > 0
     assert over.family_counts[covt.FAMILY_SPLIT:].sum() == 0 and over.num_descs == n
+
+
+def test_split_contract_under_sanitizers(tmp_path):
+    """covt_split_plan.h is plain C++ (g++ compiles it without HIP): a stand-alone program built with
+    AddressSanitizer and UndefinedBehaviorSanitizer writes 60,000 chunk groups (varint, FastPFOR, RLE) with the
+    one writer and checks them against the layout include/covt.h documents, stated by position -- the head is
+    the stream's descriptor but for avail = chunk and the flags, every pad has exactly COVT_DESC_SPLIT_PAD | kind
+    and is zero outside its fields, the readers return what was written, the 42 FastPFOR state slots are 42
+    distinct aligned words of pads 2..7 -- and runs the shared FastPFOR page-directory parse and block-header
+    step over every prefix of 120 streams of 640 words (random, and framed as pages) through a reader that
+    aborts on a word outside the stream."""
+    import subprocess
+
+    exe = str(tmp_path / "split_plan_check")
+    subprocess.check_call([os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-Wall", "-Werror",
+                           "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "cov-tiles_amd", "csrc"),
+                           "-o", exe, os.path.join(ROOT, "tests", "split_plan", "split_plan_check.cc")])
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    out = p.stdout.split()
+    assert p.returncode == 0 and out[:3] == ["ok", "60000", "76920"] and int(out[3]) > 100000, (p.stdout, p.stderr[-2000:])
