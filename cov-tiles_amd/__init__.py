@@ -159,6 +159,16 @@ BBOX_INFO_DTYPE = np.dtype([("tile", np.int32), ("layer", np.int32), ("n_feature
                             ("reserved", np.int32)])
 BBOX_TOO_LARGE = 0x1
 assert BBOX_DESC_DTYPE.itemsize == 16 and BBOX_RESULT_DTYPE.itemsize == 40 and BBOX_INFO_DTYPE.itemsize == 32
+# geometry measures (include/covt.h "Geometry measures")
+MEASURES_DESC_DTYPE = np.dtype([("off", np.int64), ("n_features", np.int32), ("flags", np.int32),
+                                ("ring_cap", np.int32), ("reserved", np.int32)])
+MEASURES_RESULT_DTYPE = np.dtype([("status", np.int32), ("reserved", np.int32)])
+MEASURES_INFO_DTYPE = np.dtype([("tile", np.int32), ("layer", np.int32), ("n_features", np.int32),
+                                ("desc_index", np.int32), ("off", np.int64), ("flags", np.int32),
+                                ("ring_cap", np.int32)])
+MEASURES_TOO_LARGE = 0x1
+assert (MEASURES_DESC_DTYPE.itemsize == 24 and MEASURES_RESULT_DTYPE.itemsize == 8
+        and MEASURES_INFO_DTYPE.itemsize == 32)
 # georeferenced geometry (include/covt.h "Georeferenced geometry")
 CRS_TILE, CRS_WEB_MERCATOR, CRS_CRS84 = 0, 1, 2
 GEO_IDENTITY, GEO_AFFINE, GEO_AFFINE_LAT = 0, 1, 2
@@ -228,16 +238,17 @@ _SIGNATURES = {
     **_sig(None, [_vp], "covt_plan_options_init", "covt_plan_destroy", "covt_device_plan_destroy"),
     **_sig(_i64, [_vp], "covt_plan_num_streams", "covt_plan_output_bytes", "covt_plan_num_descs",
            "covt_plan_num_geometry_columns", "covt_plan_assembly_bytes", "covt_plan_wkb_bytes", "covt_plan_bbox_bytes",
+           "covt_plan_measures_bytes",
            "covt_plan_num_property_columns", "covt_plan_property_bytes"),
     **_sig(_int, [_vp, _i64p, _i64p, _i64p], "covt_plan_totals", "covt_device_plan_totals"),
     **_sig(_int, [_vp, _vp], "covt_plan_streams", "covt_plan_descs", "covt_plan_geometry_columns",
            "covt_plan_geometry_descs", "covt_plan_wkb_columns", "covt_plan_wkb_descs", "covt_plan_bbox_columns",
-           "covt_plan_bbox_descs", "covt_plan_property_columns", "covt_plan_property_descs"),
+           "covt_plan_bbox_descs", "covt_plan_measures_columns", "covt_plan_measures_descs", "covt_plan_property_columns", "covt_plan_property_descs"),
     **_sig(_int, [_vp, _i64p], "covt_plan_desc_streams", "covt_plan_family_counts", "covt_device_plan_family_counts"),
     "covt_plan_tile_status": (_int, [_vp, _i32p]),
     "covt_plan_release_device": (_int, [_vp]),
     **_sig(_int, [_vp, _u8p, _u64, _vp, _vp], "covt_plan_decode_host", "covt_plan_assemble_host", "covt_plan_wkb_host",
-           "covt_plan_bbox_host", "covt_plan_properties_host"),
+           "covt_plan_bbox_host", "covt_plan_measures_host", "covt_plan_properties_host"),
     "covt_plan_decode_host_multi": (_int, [_vp, _u8p, _u64, _i32, _vp, _vp]),
     "covt_plan_decode_host_shards": (_int, [_vp, _u8p, _u64, _i32, _i32p, _vp, _vp]),
     # launches over device buffers
@@ -248,6 +259,7 @@ _SIGNATURES = {
     "covt_materialize_properties_device": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "covt_geometry_wkb_device": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "covt_geometry_bbox_device": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "covt_geometry_measures_device": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     # georeferenced geometry
     "covt_geo_transform": (_int, [_i32, _i32, _i32, _i32, _i32, _vp]),
     "covt_plan_geometry_extents": (_int, [_vp, _vp]),
@@ -262,18 +274,19 @@ _SIGNATURES = {
     "covt_device_plan_pool_trim": (_int, [_int, _u64]),
     **_sig(_i64, [_vp], "covt_device_plan_num_streams", "covt_device_plan_num_descs", "covt_device_plan_output_bytes",
            "covt_device_plan_num_geometry_columns", "covt_device_plan_assembly_bytes", "covt_device_plan_wkb_bytes",
-           "covt_device_plan_bbox_bytes", "covt_device_plan_num_property_columns", "covt_device_plan_property_bytes"),
+           "covt_device_plan_bbox_bytes", "covt_device_plan_measures_bytes", "covt_device_plan_num_property_columns", "covt_device_plan_property_bytes"),
     **_sig(_vp, [_vp], "covt_device_plan_descs_device", "covt_device_plan_streams_device",
            "covt_device_plan_tile_status_device", "covt_device_plan_order_device",
            "covt_device_plan_geometry_descs_device", "covt_device_plan_wkb_descs_device",
-           "covt_device_plan_bbox_descs_device", "covt_device_plan_property_descs_device"),
+           "covt_device_plan_bbox_descs_device", "covt_device_plan_measures_descs_device",
+           "covt_device_plan_property_descs_device"),
     "covt_device_plan_copy": (_int, [_vp, _vp, _vp, _i32p]),
     **_sig(_int, [_vp, _vp, _vp], "covt_device_plan_geometry_copy", "covt_device_plan_wkb_copy",
-           "covt_device_plan_bbox_copy", "covt_device_plan_property_copy"),
+           "covt_device_plan_bbox_copy", "covt_device_plan_measures_copy", "covt_device_plan_property_copy"),
     "covt_device_plan_geometry": (_int, [_vp, _vp]),
     "covt_device_plan_decode": (_int, [_vp, _vp, _vp, _vp, _vp]),
     **_sig(_int, [_vp] * 6, "covt_device_plan_assemble", "covt_device_plan_bbox"),
-    "covt_device_plan_materialize": (_int, [_vp] * 7),
+    **_sig(_int, [_vp] * 7, "covt_device_plan_materialize", "covt_device_plan_measures"),
     "covt_device_plan_wkb": (_int, [_vp] * 8),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -569,6 +582,9 @@ _PRODUCTS = {
     "bbox": _Product("num_geometry_columns", "bbox_bytes", "bdescs", "bbox", BBOX_INFO_DTYPE, BBOX_DESC_DTYPE,
                      BBOX_DESC_DTYPE.itemsize, BBOX_RESULT_DTYPE, ("int64", 5), False, True,
                      ("d_bdesc", "d_bbox", "d_bres")),
+    "measures": _Product("num_geometry_columns", "measures_bytes", "mdescs", "measures", MEASURES_INFO_DTYPE,
+                         MEASURES_DESC_DTYPE, MEASURES_DESC_DTYPE.itemsize, MEASURES_RESULT_DTYPE, ("int32", 2), False,
+                         True, ("d_mdesc", "d_measures", "d_mres")),
     "property": _Product("num_property_columns", "property_bytes", "pdescs", "props", PROP_INFO_DTYPE, PROP_DESC_DTYPE,
                          PROP_DESC_DTYPE.itemsize, PROP_RESULT_DTYPE, ("int32", 2), True, False,
                          ("d_pdesc", "d_props", "d_pres")),
@@ -651,6 +667,13 @@ class Plan:
         if self.num_geometry_columns:
             L.covt_plan_bbox_columns(h, self.bbox.ctypes.data)
             L.covt_plan_bbox_descs(h, self.bdescs.ctypes.data)
+        # geometry measures (include/covt.h "Geometry measures"): one column per geometry column
+        self.measures_bytes = int(L.covt_plan_measures_bytes(h))
+        self.measures = np.zeros(self.num_geometry_columns, dtype=MEASURES_INFO_DTYPE)
+        self.mdescs = np.zeros(self.num_geometry_columns, dtype=MEASURES_DESC_DTYPE)
+        if self.num_geometry_columns:
+            L.covt_plan_measures_columns(h, self.measures.ctypes.data)
+            L.covt_plan_measures_descs(h, self.mdescs.ctypes.data)
         # property columns (include/covt.h "Property columns"; plans made with PLAN_PROPERTIES)
         self.num_property_columns = int(L.covt_plan_num_property_columns(h))
         self.property_bytes = int(L.covt_plan_property_bytes(h))
@@ -767,6 +790,19 @@ class Plan:
         a = buf[o:o + 32 * n].view(np.float64)
         return BboxColumn(a[:n], a[n:2 * n], a[2 * n:3 * n], a[3 * n:], np.array(r["extent"], dtype=np.float64),
                           int(r["n_empty"]))
+
+    def measures_host(self):
+        """H2D + decode + geometry assembly + measures + D2H (covt_plan_measures_host).
+        Returns (uint8 measures buffer, results[num_geometry_columns] in tile order); see measures_column."""
+        return self._product_host("measures", "covt_plan_measures_host")
+
+    def measures_column(self, buf: np.ndarray, mres: np.ndarray, c: int) -> "MeasuresColumn":
+        """Column c (tile order) of a measures buffer -> MeasuresColumn (raises on its status)."""
+        m, r = self.measures[c], mres[c]
+        _raise(int(r["status"]), "measures column %d (tile %d, layer %d)" % (c, m["tile"], m["layer"]))
+        o, n = int(m["off"]), int(m["n_features"])
+        return MeasuresColumn(buf[o:o + 8 * n].view(np.float64), buf[o + 8 * n:o + 16 * n].view(np.float64),
+                              buf[o + 16 * n:o + 20 * n].view(np.int32))
 
     def properties_host(self):
         """H2D + decode + property materialization + D2H (covt_plan_properties_host).
@@ -976,6 +1012,21 @@ class DeviceBatch:
         """(bounding-box bytes, results in tile order) copied to the host (after bbox())."""
         return self._results("bbox")
 
+    def measures(self, stream=None):
+        """Enqueue the measures (area, length, num_coords) of every assembled geometry column (after
+        assemble() on the same stream)."""
+        self._buffers("geometry")
+        self._buffers("measures")
+        _raise(lib().covt_geometry_measures_device(self.d_out.data_ptr(), self.d_gdesc.data_ptr(),
+                                                   self.d_asm.data_ptr(), self.d_gres.data_ptr(),
+                                                   self.d_mdesc.data_ptr(), self.plan.num_geometry_columns,
+                                                   self.d_measures.data_ptr(), self.d_mres.data_ptr(),
+                                                   _stream(stream, self.device)), "covt_geometry_measures_device")
+
+    def measures_results(self):
+        """(measures bytes, results in tile order) copied to the host (after measures())."""
+        return self._results("measures")
+
     def materialize_properties(self, stream=None):
         """Enqueue the property-column materialization (after decode() on the same stream)."""
         self._buffers("property")
@@ -1119,6 +1170,7 @@ class DevicePlan:
         self.assembly_bytes = lib().covt_device_plan_assembly_bytes(self._h)
         self.wkb_bytes = lib().covt_device_plan_wkb_bytes(self._h)
         self.bbox_bytes = lib().covt_device_plan_bbox_bytes(self._h)
+        self.measures_bytes = lib().covt_device_plan_measures_bytes(self._h)
         return self.num_geometry_columns
 
     def geometry_copy(self):
@@ -1184,6 +1236,23 @@ class DevicePlan:
             return
         _raise(lib().covt_device_plan_bbox(self._h, d_asm.data_ptr(), d_gres.data_ptr(), d_bbox.data_ptr(),
                                            d_bres.data_ptr(), _stream(stream, self.device)), "covt_device_plan_bbox")
+
+    def measures_copy(self):
+        """(measures records in tile order, descriptors in launch order) as host arrays (Plan.measures /
+        Plan.mdescs)."""
+        return self._copy("measures", "covt_device_plan_measures_copy")
+
+    def alloc_measures(self):
+        """(measures buffer, results) on the device, sized for this plan's geometry columns."""
+        return self._alloc("measures")
+
+    def measures(self, d_out, d_asm, d_gres, d_measures, d_mres, stream=None):
+        """Enqueue the measures over this plan's descriptors (after assemble() on the same stream); d_out is
+        the decode output, which holds the GeometryTypes."""
+        self.geometry(stream)
+        _raise(lib().covt_device_plan_measures(self._h, d_out.data_ptr(), d_asm.data_ptr(), d_gres.data_ptr(),
+                                               d_measures.data_ptr(), d_mres.data_ptr(),
+                                               _stream(stream, self.device)), "covt_device_plan_measures")
 
 
 class DeviceSubset:
@@ -1302,6 +1371,19 @@ class BboxColumn:
 
 
 @dataclass
+class MeasuresColumn:
+    """One geometry column's measures (include/covt.h "Geometry measures"), in tile pixels: per feature its
+    area (float64, shell minus holes; +0.0 unless a polygon type), its length (float64, line length or
+    polygon perimeter; +0.0 for point types) and num_coords (int32, the points of its WKB value)."""
+    area: np.ndarray
+    length: np.ndarray
+    num_coords: np.ndarray
+
+    def __len__(self) -> int:
+        return int(self.area.size)
+
+
+@dataclass
 class PropertyColumn:
     """One materialized property (sub)column (include/covt.h "Property columns"): Arrow-style validity
     bitmap (LSB first) + values at feature positions (BOOLEAN: bitmap; INT64: int64; FLOAT: float32;
@@ -1347,6 +1429,7 @@ class LayerColumns:
     wkb: Optional[WkbColumn] = None  # the layer's geometries, one WKB value per feature
     bbox: Optional[BboxColumn] = None  # their bounding boxes, the bbox covering column beside wkb
     crs: int = CRS_TILE  # the CRS of wkb and bbox (geometry.vertexBuffer stays in tile pixels)
+    measures: Optional["MeasuresColumn"] = None  # their area, length and num_coords, in tile pixels whatever the crs
 
 
 _GEOM_FIELD = {GEOMETRY_TYPES: "geometryTypes", GEOMETRY_OFFSETS: "geometryOffsets", PART_OFFSETS: "partOffsets",
@@ -1399,6 +1482,11 @@ class CovtParser:
                 lc = by_layer.get(int(plan.bbox["layer"][c]))
                 if lc is not None and int(bres["status"][c]) == OK:  # (a failed column keeps bbox = None)
                     lc.bbox = plan.bbox_column(bbuf, bres, c)
+            mbuf, mres = plan.measures_host()
+            for c in range(plan.num_geometry_columns):
+                lc = by_layer.get(int(plan.measures["layer"][c]))
+                if lc is not None and int(mres["status"][c]) == OK:  # (a failed column keeps measures = None)
+                    lc.measures = plan.measures_column(mbuf, mres, c)
         if properties and plan.num_property_columns:
             buf, pres = plan.properties_host()
             by_layer = {lc.layer: lc for lc in layers}
@@ -1420,10 +1508,10 @@ def version() -> str:
 # the files whose sha256 (in this order) the Makefile compiles into covt_version() as "src:<16 hex>"
 _BUILD_SOURCES = (  # the Makefile's SRC, then its HDR, one to one
     ("csrc/covt_decode.hip", "csrc/covt_assemble.hip", "csrc/covt_props.hip", "csrc/covt_plan_device.hip",
-     "csrc/covt_wkb.hip", "csrc/covt_bbox.hip", "csrc/covt_host.cpp")
+     "csrc/covt_wkb.hip", "csrc/covt_bbox.hip", "csrc/covt_measures.hip", "csrc/covt_host.cpp")
     + ("../include/covt.h", "csrc/covt_internal.h", "csrc/covt_wave.h", "csrc/covt_walk.h", "csrc/covt_props_plan.h",
        "csrc/covt_scratch.h", "csrc/covt_coop.h", "csrc/covt_wkb_plan.h", "csrc/covt_bbox_plan.h",
-       "csrc/covt_geo_plan.h", "csrc/covt_arena.h", "csrc/covt_split_plan.h"))
+       "csrc/covt_measures_plan.h", "csrc/covt_geo_plan.h", "csrc/covt_arena.h", "csrc/covt_split_plan.h"))
 
 
 def source_build_id() -> str:

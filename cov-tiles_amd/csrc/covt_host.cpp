@@ -25,6 +25,7 @@
 #include "covt_props_plan.h"
 #include "covt_wkb_plan.h"
 #include "covt_bbox_plan.h"
+#include "covt_measures_plan.h"
 #include "covt_geo_plan.h"
 
 namespace {
@@ -800,6 +801,9 @@ struct covt_plan {
     std::vector<covt_bbox_info> binfo;   // bounding-box columns, tile order (one per geometry column)
     std::vector<covt_bbox_desc> bdescs;  // launch order (that of gdescs)
     int64_t bbox_bytes = 0;
+    std::vector<covt_measures_info> minfo;   // measures columns, tile order (one per geometry column)
+    std::vector<covt_measures_desc> mdescs;  // launch order (that of gdescs)
+    int64_t measures_bytes = 0;
     std::vector<covt_prop_info> pinfo;   // property (sub)columns, tile order
     std::vector<uint16_t> pflags;        // their COVT_PROP_* flags
     std::vector<covt_prop_desc> pdescs;  // launch order: largest first
@@ -980,6 +984,20 @@ void plan_bbox(covt_plan* p) {
             return bbox_column_layout(g.n_features, (uint32_t)g.flags, off, d);
         },
         [](covt_bbox_info& b, const covt_bbox_desc& d) { b.off = d.off; });
+}
+
+// Measures columns (include/covt.h "Geometry measures"): slices in a buffer of their own, each with its
+// per-ring scratch (covt_measures_plan.h).
+void plan_measures(covt_plan* p) {
+    p->measures_bytes = plan_geometry_product(
+        p, p->minfo, p->mdescs,
+        [](const covt_geom_info& g, int64_t off, covt_measures_desc& d) {
+            return measures_column_layout(g.n_features, g.ring_cap, (uint32_t)g.flags, off, d);
+        },
+        [](covt_measures_info& m, const covt_measures_desc& d) {
+            m.off = d.off;
+            m.ring_cap = d.ring_cap;
+        });
 }
 
 // Property (sub)columns (include/covt.h "Property columns"; CovtParser.decodePropertyColumn
@@ -1630,6 +1648,7 @@ int covt_plan_create_opts(const uint8_t* bytes, const uint64_t* tile_offsets, co
     }
     plan_wkb(p);
     plan_bbox(p);
+    plan_measures(p);
     plan_property_layout(p);
     *out = p;
     return COVT_OK;
@@ -2013,6 +2032,22 @@ int covt_plan_bbox_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_byt
                              [](const PlanDev& d, const covt_bbox_desc* bdesc, int64_t n, uint8_t* buf,
                                 covt_bbox_result* bres, hipStream_t s) {
                                  return covt_geometry_bbox_device(d.gdesc, d.asm_buf, d.gres, bdesc, n, buf, bres, s);
+                             });
+}
+
+int64_t covt_plan_measures_bytes(const covt_plan* p) { return p ? p->measures_bytes : 0; }
+int covt_plan_measures_columns(const covt_plan* p, covt_measures_info* out) { return copy_records(p ? &p->minfo : nullptr, out); }
+int covt_plan_measures_descs(const covt_plan* p, covt_measures_desc* out) { return copy_records(p ? &p->mdescs : nullptr, out); }
+
+// decode, assembly, measures
+int covt_plan_measures_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, uint8_t* host_measures,
+                            covt_measures_result* host_mres) {
+    if (!p) return COVT_ERR_INVALID_ARG;
+    return plan_product_host(p, bytes, n_bytes, p->minfo, p->mdescs, p->measures_bytes, host_measures, host_mres, true,
+                             [](const PlanDev& d, const covt_measures_desc* mdesc, int64_t n, uint8_t* buf,
+                                covt_measures_result* mres, hipStream_t s) {
+                                 return covt_geometry_measures_device(d.out, d.gdesc, d.asm_buf, d.gres, mdesc, n, buf,
+                                                                      mres, s);
                              });
 }
 

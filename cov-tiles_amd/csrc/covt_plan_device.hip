@@ -37,6 +37,7 @@
 #include "covt_props_plan.h"
 #include "covt_wkb_plan.h"
 #include "covt_bbox_plan.h"
+#include "covt_measures_plan.h"
 
 struct covt_device_plan {
     int dev = 0;
@@ -58,6 +59,9 @@ struct covt_device_plan {
     int64_t bbox_bytes = 0;        // bounding-box columns (likewise)
     covt_bbox_info* d_binfo = nullptr;
     covt_bbox_desc* d_bdesc = nullptr;
+    int64_t measures_bytes = 0;    // measures columns (likewise)
+    covt_measures_info* d_minfo = nullptr;
+    covt_measures_desc* d_mdesc = nullptr;
     void* prop_arena = nullptr;    // property columns (COVT_PLAN_PROPERTIES): records, infos, descriptors
     void* scratch = nullptr;       // creation-time scratch (the property walk's record slots), freed on the way
     int64_t n_props = 0, prop_bytes = 0;
@@ -2689,6 +2693,17 @@ struct BboxProduct {  // covt_bbox_plan.h
     }
     static __device__ void fill(Info& b, const Desc& d) { b.off = d.off; }
 };
+struct MeasuresProduct {  // covt_measures_plan.h
+    using Info = covt_measures_info;
+    using Desc = covt_measures_desc;
+    static __device__ int64_t layout(const covt_geom_info& g, int64_t off, Desc& d) {
+        return measures_column_layout(g.n_features, g.ring_cap, (uint32_t)g.flags, off, d);
+    }
+    static __device__ void fill(Info& m, const Desc& d) {
+        m.off = d.off;
+        m.ring_cap = d.ring_cap;
+    }
+};
 template <class P>
 __global__ void product_col_bytes(const covt_geom_info* __restrict__ ginfo, int64_t nc, int64_t* __restrict__ bytes) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -3306,6 +3321,7 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     const auto a_st = L.take<uint8_t>(sort_tmp), a_cs = L.take<uint8_t>(cscan_tmp);
     const ProductSlice<WkbProduct> a_wkb(L, m);
     const ProductSlice<BboxProduct> a_bbox(L, m);
+    const ProductSlice<MeasuresProduct> a_measures(L, m);
     // the arena is the plan's only on success: a failed build frees it (a retry allocates afresh)
     StreamFree arena{nullptr, s};
     HIP_TRY(plan_malloc(&arena.q, L.bytes(), p->dev, s));
@@ -3316,7 +3332,7 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     uint32_t* v1 = a_v1.at(g);
     uint8_t* cscan = a_cs.at(g);
     HIP_TRY(hipMemsetAsync(colbytes, 0, (m + 1) * 8, s));
-    int64_t asm_bytes = 0, wkb_bytes = 0, bbox_bytes = 0;
+    int64_t asm_bytes = 0, wkb_bytes = 0, bbox_bytes = 0, measures_bytes = 0;
     if (nc > 0) {
         geom_columns<<<(int)((ns + 255) / 256), 256, 0, s>>>(p->d_info, ns, p->format, gst, gpos, p->d_ginfo, colbytes);
         HIP_TRY(hipGetLastError());
@@ -3333,6 +3349,8 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     int st = plan_product(a_wkb, g, m, nc, p->d_ginfo, cscan, cscan_tmp, s, p->d_winfo, p->d_wdesc, &wkb_bytes);
     if (st == COVT_OK)
         st = plan_product(a_bbox, g, m, nc, p->d_ginfo, cscan, cscan_tmp, s, p->d_binfo, p->d_bdesc, &bbox_bytes);
+    if (st == COVT_OK)
+        st = plan_product(a_measures, g, m, nc, p->d_ginfo, cscan, cscan_tmp, s, p->d_minfo, p->d_mdesc, &measures_bytes);
     if (st) return st;
     if (nc > 0) {
         HIP_TRY(hipMemcpyAsync(&asm_bytes, coloff + nc, 8, hipMemcpyDeviceToHost, s));
@@ -3345,6 +3363,7 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     p->asm_bytes = asm_bytes;
     p->wkb_bytes = wkb_bytes;
     p->bbox_bytes = bbox_bytes;
+    p->measures_bytes = measures_bytes;
     p->geo_built = true;
     return COVT_OK;
 }
@@ -3407,6 +3426,24 @@ int covt_device_plan_bbox(covt_device_plan* p, const uint8_t* d_asm, const covt_
     const int st = covt_device_plan_geometry(p, hip_stream);
     if (st) return st;
     return covt_geometry_bbox_device(p->d_gdesc, d_asm, d_gres, p->d_bdesc, p->n_geo, d_bbox, d_bres, hip_stream);
+}
+
+int64_t covt_device_plan_measures_bytes(const covt_device_plan* p) { return p && p->geo_built ? p->measures_bytes : 0; }
+const covt_measures_desc* covt_device_plan_measures_descs_device(const covt_device_plan* p) {
+    return p && p->geo_built ? p->d_mdesc : nullptr;
+}
+int covt_device_plan_measures_copy(const covt_device_plan* p, covt_measures_info* infos, covt_measures_desc* descs) {
+    if (!p || !p->geo_built) return COVT_ERR_INVALID_ARG;
+    return copy_to_host(p->n_geo, infos, p->d_minfo, descs, p->d_mdesc);
+}
+int covt_device_plan_measures(covt_device_plan* p, const uint8_t* d_decoded, const uint8_t* d_asm,
+                              const covt_geom_result* d_gres, uint8_t* d_measures, covt_measures_result* d_mres,
+                              void* hip_stream) {
+    if (!p) return COVT_ERR_INVALID_ARG;
+    const int st = covt_device_plan_geometry(p, hip_stream);
+    if (st) return st;
+    return covt_geometry_measures_device(d_decoded, p->d_gdesc, d_asm, d_gres, p->d_mdesc, p->n_geo, d_measures, d_mres,
+                                         hip_stream);
 }
 
 int covt_device_plan_assemble(covt_device_plan* p, const uint8_t* d_decoded, const covt_stream_result* d_res,

@@ -38,6 +38,9 @@ public final class GpuCovtBatch implements AutoCloseable {
     /** Fields per row of {@link #geometryBbox}: status, n_empty, then the column's extent xmin, ymin,
      * xmax, ymax as the bits of their doubles (Double.longBitsToDouble; NaN without a coordinate). */
     public static final int BBOX_RESULT_FIELDS = 6;
+    /** Fields per row of {@link #measuresColumns()}: covt_measures_info in order (tile, layer, n_features,
+     * desc_index, off); off indexes the buffer of {@link #geometryMeasures}. */
+    public static final int MEASURES_FIELDS = 5;
     /** Coordinate reference systems of the georeferenced overloads (include/covt.h "Georeferenced
      * geometry"): tile pixels (the plain methods' output), EPSG:3857 metres, OGC:CRS84 lon/lat degrees. */
     public static final int CRS_TILE = 0, CRS_WEB_MERCATOR = 1, CRS_CRS84 = 2;
@@ -150,6 +153,21 @@ public final class GpuCovtBatch implements AutoCloseable {
         return geometryBboxProjected(live(), tiles, out, crs, addresses(tileZxy), numTiles);
     }
 
+    /** Bytes {@link #geometryMeasures} writes. */
+    public long measuresBytes() { return measuresBytes(live()); }
+
+    /** One row of MEASURES_FIELDS values per geometry column, tile order. */
+    public long[] measuresColumns() { return measuresColumns(live()); }
+
+    /** Decode + geometry assembly + measures into {@code out} (direct, measuresBytes() long): per column, at
+     * off, little-endian area[n_features] and length[n_features] float64, then num_coords[n_features] int32 --
+     * what JTS getArea(), getLength() and getNumPoints() give for the feature of {@link #geometryWkb}, in tile
+     * pixels.  Returns one status per column, tile order. */
+    public long[] geometryMeasures(ByteBuffer out) {
+        if (!out.isDirect() || out.capacity() < measuresBytes()) throw new IllegalArgumentException("output buffer");
+        return geometryMeasures(live(), tiles, out);
+    }
+
     @Override
     public void close() {
         if (handle != 0) destroy(handle);
@@ -178,6 +196,9 @@ public final class GpuCovtBatch implements AutoCloseable {
     private static native long bboxBytes(long plan);
     private static native long[] bboxColumns(long plan);
     private static native long[] geometryBbox(long plan, ByteBuffer tiles, ByteBuffer out);
+    private static native long measuresBytes(long plan);
+    private static native long[] measuresColumns(long plan);
+    private static native long[] geometryMeasures(long plan, ByteBuffer tiles, ByteBuffer out);
     // (names of their own: an overloaded native method would need the signature-mangled symbol names)
     private static native long[] geometryWkbProjected(long plan, ByteBuffer tiles, ByteBuffer out, int crs,
                                                       long[] tileZxy, int numTiles);

@@ -317,6 +317,28 @@ JNIEXPORT jlongArray JNICALL BFN(geometryBbox)(JNIEnv* env, jclass, jlong h, job
     });
 }
 
+// Geometry measures (include/covt.h "Geometry measures"): area, length (float64) and num_coords (int32) per
+// feature of every geometry column
+JNIEXPORT jlong JNICALL BFN(measuresBytes)(JNIEnv*, jclass, jlong h) { return covt_plan_measures_bytes(plan_of(h)); }
+JNIEXPORT jlongArray JNICALL BFN(measuresColumns)(JNIEnv* env, jclass, jlong h) {
+    const int64_t n = covt_plan_num_geometry_columns(plan_of(h));
+    std::vector<covt_measures_info> info((size_t)n);
+    if (!check(env, covt_plan_measures_columns(plan_of(h), info.data()))) return nullptr;
+    return long_rows<5>(env, info, [](const covt_measures_info& m) -> std::array<jlong, 5> {
+        return {m.tile, m.layer, m.n_features, m.desc_index, m.off};
+    });
+}
+JNIEXPORT jlongArray JNICALL BFN(geometryMeasures)(JNIEnv* env, jclass, jlong h, jobject tiles, jobject out) {
+    const int64_t n = covt_plan_num_geometry_columns(plan_of(h));
+    uint8_t* dst = direct_out(env, out, covt_plan_measures_bytes(plan_of(h)));
+    if (!dst) return nullptr;
+    std::vector<covt_measures_result> res((size_t)n);
+    if (!check(env, covt_plan_measures_host(plan_of(h), direct(env, tiles),
+                                            (uint64_t)env->GetDirectBufferCapacity(tiles), dst, res.data())))
+        return nullptr;
+    return long_rows<1>(env, res, [](const covt_measures_result& r) -> std::array<jlong, 1> { return {r.status}; });
+}
+
 }  // extern "C"
 
 namespace {

@@ -509,6 +509,90 @@ int covt_plan_bbox_host(const covt_plan* plan, const uint8_t* bytes, uint64_t n_
                         covt_bbox_result* host_bres);
 
 /* ---------------------------------------------------------------------------
+ * Geometry measures: how big every feature of an assembled geometry column is, what JTS answers with
+ * Geometry.getArea(), getLength() and getNumPoints() and a tile server, a GeoParquet writer or a simplifier
+ * asks next (drop small features per zoom, store area / length beside bbox, size work by vertex count).
+ * Per column one slice (16-byte aligned start) in the measures output buffer:
+ *
+ *   area[n_features] float64 | length[n_features] float64 | num_coords[n_features] int32 (padded to 16 bytes)
+ *   | per-ring scratch, 16 * ring_cap bytes (contents unspecified)
+ *
+ * The scratch (a ring's doubled signed area and its length) lives in the same buffer, sized by the same
+ * layout rule from the column's ring_cap, so the pass allocates nothing.  All values are in tile pixels and
+ * are taken over the assembled column as the bounding boxes are: the ring-closing vertex is included and no
+ * implicit closing edge is added.  With ring r's coordinates (x_0, y_0) .. (x_{m-1}, y_{m-1}),
+ * m = ring_offsets[r + 1] - ring_offsets[r], and t the feature's GeometryTypes ordinal:
+ *
+ *   num_coords[f] = start(f + 1) - start(f), start(f) = ring_offsets[part_offsets[geometry_offsets[f]]]: the
+ *     number of points in the feature's WKB value.
+ *   area[f]: every ring has S_r = sum over i in 0 .. m - 2 of (x_i * y_{i+1} - x_{i+1} * y_i) in int64 (a
+ *     product of two int32 is exact; differences and sums are two's complement mod 2^64; 0 for m < 2).  For
+ *     POLYGON (2) and MULTIPOLYGON (5), T_f = sum over the parts p of f of (|S of p's first ring| - sum of |S_r|
+ *     over p's other rings), |.| the magnitude as uint64, the sum mod 2^64 and then read as int64, and
+ *     area[f] = (double)T_f * 0.5.  Every other type gets +0.0.  This is JTS Polygon.getArea: shell minus
+ *     holes, each by absolute value, whatever the winding.  Integer arithmetic, so the value does not depend
+ *     on evaluation order.  It is the true area whenever the sum of the |terms| is below 2^63 and
+ *     |T_f| < 2^54, which every real tile meets (coordinates lie within a few extents of 4096); outside that
+ *     bound the mod-2^64 arithmetic as written is the definition (a hole larger than its shell gives a
+ *     negative area).
+ *   length[f]: for types 1, 2, 4 and 5 (lines, and polygon perimeters as JTS getLength) the sum over all the
+ *     feature's rings and all i in 0 .. m - 2 of sqrt(dx * dx + dy * dy), dx and dy the exact coordinate
+ *     differences as float64 (a difference of two int32 is exact), one rounding per operation and no fused
+ *     multiply-add.  POINT and MULTIPOINT get +0.0.  The summation order is the kernel's; the value is within
+ *     (m_f + 4) * 2^-52 relative of the exactly rounded sum, m_f the feature's segment count: a few roundings
+ *     per term, well inside 2^-51, and at most m_f - 1 roundings in a sum of non-negative terms in any order.
+ *     No floating-point atomics are used, so the same input through the same entry point gives the same bytes
+ *     every time.
+ *
+ * A feature without coordinates gets 0.0, 0.0, 0.  Per column a covt_measures_result.
+ * Statuses: a column whose assembly result is not COVT_OK gets that status (slice untouched);
+ * COVT_GEOM_TOO_LARGE or COVT_MEASURES_TOO_LARGE -> COVT_ERR_INVALID_ARG, likewise.
+ * Out of scope: measures in a CRS (for Web Mercator multiply length by |sx| and area by sx * sx of the
+ * column's covt_geo_xform; degrees have no meaningful area), centroids, per-column totals.
+ * ------------------------------------------------------------------------- */
+#define COVT_MEASURES_TOO_LARGE 0x1 /* covt_measures_desc.flags: assembly refuses the column (COVT_GEOM_TOO_LARGE) */
+
+/* One device-resident measures column entry (24 bytes), parallel to covt_geom_desc (launch order). */
+typedef struct covt_measures_desc {
+    int64_t off; /* byte offset of the column's slice in the measures output buffer (16-byte aligned) */
+    int32_t n_features, flags;
+    int32_t ring_cap, reserved; /* ring_cap: the rings the slice's scratch holds (= covt_geom_desc.ring_cap) */
+} covt_measures_desc;
+
+/* Per-column measures result written by the kernels (8 bytes). */
+typedef struct covt_measures_result {
+    int32_t status, reserved;
+} covt_measures_result;
+
+/* Host-visible measures column record of a plan, in tile order (32 bytes); column c belongs to geometry
+ * column c (covt_geom_info). */
+typedef struct covt_measures_info {
+    int32_t tile, layer, n_features, desc_index; /* desc_index: row in the launch-ordered descriptors */
+    int64_t off;
+    int32_t flags, ring_cap;
+} covt_measures_info;
+
+int64_t covt_plan_measures_bytes(const covt_plan* plan); /* size of the measures output buffer */
+int covt_plan_measures_columns(const covt_plan* plan, covt_measures_info* out); /* tile order, num_geometry_columns */
+int covt_plan_measures_descs(const covt_plan* plan, covt_measures_desc* out);   /* launch order (= covt_plan_geometry_descs) */
+
+/* Measures of every assembled geometry column on `hip_stream`, after covt_assemble_geometry_device on the
+ * same stream: d_decoded the decode output (GeometryTypes are read from it at covt_geom_desc.in_off[0]),
+ * d_gdesc / d_asm / d_gres the assembly's descriptors, output and results, d_mdesc the measures descriptors
+ * (same order), d_measures an output buffer of covt_plan_measures_bytes bytes, d_mres n_columns results (same
+ * order).  Asynchronous; allocates nothing and writes every output element exactly once, so it can be
+ * captured in a HIP graph as it is and its result does not depend on scheduling. */
+int covt_geometry_measures_device(const uint8_t* d_decoded, const covt_geom_desc* d_gdesc, const uint8_t* d_asm,
+                                  const covt_geom_result* d_gres, const covt_measures_desc* d_mdesc,
+                                  int64_t n_columns, uint8_t* d_measures, covt_measures_result* d_mres,
+                                  void* hip_stream);
+
+/* Convenience: H2D + decode + assembly + measures + D2H of the whole plan on the current device.
+ * host_measures: covt_plan_measures_bytes bytes; host_mres: one result per column in tile order. */
+int covt_plan_measures_host(const covt_plan* plan, const uint8_t* bytes, uint64_t n_bytes, uint8_t* host_measures,
+                            covt_measures_result* host_mres);
+
+/* ---------------------------------------------------------------------------
  * Georeferenced geometry: the WKB values and the bounding boxes in a coordinate reference system instead of
  * tile pixels, so the columns of many tiles share one table, the bbox column prunes across tiles and a
  * GeoParquet writer can name a CRS.  A column's transform maps its assembled int32 pixel (px, py), converted
@@ -788,6 +872,18 @@ int covt_device_plan_bbox_copy(const covt_device_plan* plan, covt_bbox_info* inf
  * covt_bbox_info.desc_index). */
 int covt_device_plan_bbox(covt_device_plan* plan, const uint8_t* d_asm, const covt_geom_result* d_gres,
                           uint8_t* d_bbox, covt_bbox_result* d_bres, void* hip_stream);
+/* Measures columns from a device plan: the records and descriptors of covt_plan_measures_columns /
+ * covt_plan_measures_descs, built on the device next to the bounding-box records (covt_device_plan_geometry;
+ * the host plan's exactly); 0 / NULL before that call. */
+int64_t covt_device_plan_measures_bytes(const covt_device_plan* plan);
+const covt_measures_desc* covt_device_plan_measures_descs_device(const covt_device_plan* plan);
+int covt_device_plan_measures_copy(const covt_device_plan* plan, covt_measures_info* infos, covt_measures_desc* descs);
+/* covt_geometry_measures_device over the plan's descriptors, after covt_device_plan_assemble on the same
+ * stream: d_measures covt_device_plan_measures_bytes bytes, d_mres one result per column in launch order
+ * (column c's at its covt_measures_info.desc_index). */
+int covt_device_plan_measures(covt_device_plan* plan, const uint8_t* d_decoded, const uint8_t* d_asm,
+                              const covt_geom_result* d_gres, uint8_t* d_measures, covt_measures_result* d_mres,
+                              void* hip_stream);
 /* Property columns from a device plan made with COVT_PLAN_PROPERTIES in opts->flags: the records,
  * output layout and largest-first descriptors of covt_plan_property_columns / covt_plan_property_descs,
  * built on the device with the plan (the host plan's exactly); a plan without the flag has none. */
