@@ -126,7 +126,7 @@ def test_batch_properties_digests(covt, oracle, gpu_available):
 def test_corrupted_property_streams_status_parity(covt, oracle, gpu_available, n_tiles):
     """Bit flips / truncations inside property streams: the GPU reports exactly the oracle's status and,
     when that is OK, exactly its column.  20 tiles (2,900 columns) take the small-batch path, where the
-    tile's 35k-feature columns are materialized by whole workgroups (props_coop_kernel)."""
+    tile's 35k-feature columns are cut into 4,096-feature chunks, a workgroup each (prop_split_kernel)."""
     rng = np.random.default_rng(11 if n_tiles == 60 else 12)
     base = _tile("5_16_20")
     st, props = oracle.walk_properties(base)
