@@ -56,6 +56,27 @@ COVT_GEO_HD inline covt_geo_xform geo_identity_affine() {
     return t;
 }
 
+// The column's transform as a kernel holds it (uniform): nothing for a plain pass (GEO 0), the affine
+// coefficients for a launch without latitudes (GEO 1: a tile-local column maps by 0 + 1 * p), and with them
+// whether y goes on through the Gudermannian (GEO 2).
+template <int GEO>
+struct GeoHold {
+    covt_geo_xform t;
+    bool lat;
+};
+template <>
+struct GeoHold<0> {};
+template <int GEO>
+COVT_GEO_HD inline GeoHold<GEO> geo_hold(const covt_geo_xform* xf, int64_t col) {
+    GeoHold<GEO> g;
+    if constexpr (GEO != 0) {
+        g.t = xf[col];
+        g.lat = GEO == 2 && g.t.kind == COVT_GEO_AFFINE_LAT;
+        if (g.t.kind == COVT_GEO_IDENTITY) g.t = geo_identity_affine();
+    }
+    return g;
+}
+
 // The coefficient table of include/covt.h for tile z/x/y of a layer with `extent` pixels a side.
 COVT_GEO_HD inline int geo_transform(int32_t crs, int32_t z, int32_t x, int32_t y, int32_t extent, covt_geo_xform& out) {
     COVT_GEO_NO_CONTRACT

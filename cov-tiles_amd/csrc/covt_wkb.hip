@@ -35,6 +35,7 @@
 #include "covt.h"
 #include "covt_coop.h"
 #include "covt_geo_plan.h"
+#include "covt_segscan.h"
 #include "covt_wave.h"
 #include "covt_wkb_plan.h"
 
@@ -46,7 +47,6 @@ constexpr int kWkbIpl = 4;                 // items per thread and step
 constexpr int kWkbWriteWaves = 4;          // write: waves per workgroup
 constexpr int kWkbChunk = 64 * kWkbIpl;    // write: items per wave chunk (lane-major, kWkbIpl per lane)
 constexpr int kWkbWin = 384;               // write: offsets of a level staged in LDS per chunk (a multiple of 64)
-constexpr int kWkbSmallBlocks = 8192;      // write, small batches: workgroups over all columns (at most 64 each)
 
 typedef uint32_t u32u __attribute__((aligned(1)));
 typedef double f64x2u __attribute__((ext_vector_type(2), aligned(1)));
@@ -90,15 +90,11 @@ __device__ __forceinline__ WkbCol wkb_col(const uint8_t* dec, const covt_geom_de
     return c;
 }
 
-// the column's status before any work: the assembly's, then the layout's
+// the column's status before any work: the assembly's, then the layout's (the byte capacity an int32 offset)
 __device__ __forceinline__ int32_t wkb_precheck(const covt_geom_desc& gd, const covt_geom_result& gr,
                                                 const covt_wkb_desc& wd) {
-    if (gr.status != COVT_OK) return gr.status;
-    if (((uint32_t)gd.flags & COVT_GEOM_TOO_LARGE) || (wd.flags & COVT_WKB_TOO_LARGE) || wd.byte_cap < 0 ||
-        wd.byte_cap > INT32_MAX)
-        return COVT_ERR_INVALID_ARG;
-    const int32_t n = gd.in_off[0] >= 0 ? gd.in_len[0] : 0;  // the features the assembly walked
-    return wd.n_features == n ? COVT_OK : COVT_ERR_INVALID_ARG;
+    return geom_product_precheck(gd, gr, (wd.flags & COVT_WKB_TOO_LARGE) != 0,
+                                 wd.byte_cap >= 0 && wd.byte_cap <= INT32_MAX, wd.n_features);
 }
 
 // ---- 1. size scan ------------------------------------------------------------------------------------
@@ -275,27 +271,6 @@ __device__ __forceinline__ void wkb_put_header(uint8_t* p, uint32_t code, uint32
     wkb_put_u32(p + 5, count);
 }
 
-// The column's transform as the write kernel holds it (uniform): nothing for the plain pass (GEO 0), the
-// affine coefficients for a launch without latitudes (GEO 1: a tile-local column maps by 0 + 1 * p), and
-// with them whether y goes on through the Gudermannian (GEO 2).
-template <int GEO>
-struct WkbGeo {
-    covt_geo_xform t;
-    bool lat;
-};
-template <>
-struct WkbGeo<0> {};
-template <int GEO>
-__device__ __forceinline__ WkbGeo<GEO> wkb_geo(const covt_geo_xform* __restrict__ xf, int64_t col) {
-    WkbGeo<GEO> g;
-    if constexpr (GEO != 0) {
-        g.t = xf[col];
-        g.lat = GEO == 2 && g.t.kind == COVT_GEO_AFFINE_LAT;
-        if (g.t.kind == COVT_GEO_IDENTITY) g.t = geo_identity_affine();
-    }
-    return g;
-}
-
 // The latitude as a call, not inlined: inlined into the unrolled item loop the four items' sinh / atan
 // temporaries are live at once (140 VGPRs, 3 waves a SIMD against the plain pass's 68 and 7).
 __device__ __attribute__((noinline)) double wkb_lat(double t) { return geo_lat(t); }
@@ -304,7 +279,7 @@ __device__ __attribute__((noinline)) double wkb_lat(double t) { return geo_lat(t
 // before the chunk's first owners
 template <int GEO>
 __device__ __forceinline__ void wkb_write_coords(const WkbCol& c, WkbLevel& lr, WkbLevel& lp, WkbLevel& lf,
-                                                 int32_t v0, int32_t L, int64_t nb, const WkbGeo<GEO>& geo) {
+                                                 int32_t v0, int32_t L, int64_t nb, const GeoHold<GEO>& geo) {
     const int l = lane_id();
     uint64_t xy[kWkbIpl];
 #pragma unroll
@@ -488,7 +463,7 @@ __global__ __launch_bounds__(64 * kWkbWriteWaves) void wkb_write_kernel(
     const WkbCol c = wkb_col(dec, gd, asmb, wd, wkb);
     const int32_t P = gr.num_parts, R = gr.num_rings, V = gr.num_coords;
     const int64_t nb = wr.n_bytes;
-    const WkbGeo<GEO> geo = wkb_geo<GEO>(xf, col);
+    const GeoHold<GEO> geo = geo_hold<GEO>(xf, col);
     const int w = threadIdx.x >> 6;
     const int32_t wave = uni((int32_t)(blockIdx.y * kWkbWriteWaves + w));
     const int32_t waves = (int32_t)(gridDim.y * kWkbWriteWaves);
@@ -537,9 +512,8 @@ int wkb_launch(const uint8_t* d_decoded, const covt_geom_desc* d_gdesc, const ui
         hipLaunchKernelGGL(wkb_scan_kernel<G>, dim3((unsigned)blocks), dim3(64 * kWkbWriteWaves), 0, s, d_decoded,
                            d_gdesc, d_asm, d_gres, d_wdesc, n_columns, d_wkb, d_wres, d_xf, kinds);
     }
-    // small batches: up to 64 workgroups per column (a 72k-coordinate column: a chunk or two per wave)
-    const int64_t gy = small ? std::max<int64_t>(1, std::min<int64_t>(64, kWkbSmallBlocks / n_columns)) : 1;
-    hipLaunchKernelGGL(wkb_write_kernel<GEO>, dim3((unsigned)n_columns, (unsigned)gy), dim3(64 * kWkbWriteWaves), 0, s,
+    const unsigned gy = small ? product_blocks_y(n_columns) : 1u;
+    hipLaunchKernelGGL(wkb_write_kernel<GEO>, dim3((unsigned)n_columns, gy), dim3(64 * kWkbWriteWaves), 0, s,
                        d_decoded, d_gdesc, d_asm, d_gres, d_wdesc, d_wkb, d_wres, d_xf);
     return hipGetLastError() == hipSuccess ? COVT_OK : COVT_ERR_DEVICE;
 }
