@@ -30,6 +30,16 @@
 // gathers in flight per dependent step (the passes are latency-bound chains of gathers).
 // Pass 4 skips the expansion when the column inserts no closing vertex (ICE rings of Gen C, line
 // and point layers): coordinate v is then source vertex v.
+//
+// Where things live: `Column` is one column's view (input streams and lengths, output arrays, capacities,
+// built once from the descriptor) and states each pass's per-item rule once -- which types consume a
+// count, the clamp and the negative / short-stream checks (`take_count`), the scratch words, the closing
+// vertex, the source index, the gather's range check.  Two walkers apply the rules.  `assemble_column`
+// is a single wave over a whole column (a batch's columns; a small batch's small columns), items
+// lane-major; it adds the one-item-segment and no-polygon shortcuts, the count windows and pass 4's
+// two-step straight copy.  `split_chunk<PASS>` is a 16-wave workgroup over one 4,096-item chunk of one pass
+// of a big column in a small batch; it adds the chunk-to-chunk scans (publish and gather), the next
+// pass's chunk starts and the failure marks, and runs passes 2 and 3 as one sweep body in three modes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -60,7 +70,7 @@ constexpr int32_t kSplitMinItems = 512;
 // of int32), where four consecutive items per lane spread each instruction over 1 KiB -- the batch
 // assembly is bound by the texture address unit's per-line work (TA busy 87 % of the kernel, issue
 // stalls 31 % of wave time; 8 consecutive items per lane: 2 KiB per instruction, 3.82 -> 5.35 ms).
-// A cooperative group (NW > 1, the split passes) keeps IPL consecutive items per thread.
+// A workgroup (the split passes' chunks) keeps four consecutive items per thread.
 #ifndef COVT_ASM_IPL
 #define COVT_ASM_IPL 8
 #endif
@@ -74,58 +84,59 @@ constexpr int32_t kSplitMinItems = 512;
 #define COVT_ASM_NT 1
 #endif
 constexpr int kAsmIpl = COVT_ASM_IPL;
+constexpr bool kAsmWin = COVT_ASM_WIN;
 typedef AsmSmemT<1, kAsmIpl> AsmSmem;
 
 __device__ __forceinline__ uint32_t wave_shr1(uint32_t x) {  // lane l - 1's value (lane 0: 0), DPP wave_shr:1
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x138, 0xf, 0xf, false);
 }
+__device__ __forceinline__ bool wave_any(bool p) { return __ballot(p) != 0ull; }
 
-// items q + IPL l + k (k < IPL) of a step of L: 16-byte stores when the lane's items are valid and
-// aligned (arrays are 16-byte aligned; aligned when q % 4 == 0), else element stores
-template <int NW, int IPL>
-__device__ __forceinline__ void store4(int32_t* a, int32_t q, int32_t L, const uint32_t (&v)[IPL]) {
-    if (NW == 1) {  // lane-major: each store 64 consecutive items
+// a wave's N lane-major items q + 64 k + lane (k < N) of a step of L: each store 64 consecutive items
+template <int N>
+__device__ __forceinline__ void store_lm(int32_t* a, int32_t q, int32_t L, const uint32_t (&v)[N]) {
 #pragma unroll
-        for (int k = 0; k < IPL; ++k)
-            if (64 * k + lane_id() < L) a[q + 64 * k + lane_id()] = (int32_t)v[k];
-        return;
-    }
-    const int32_t i0 = IPL * Coop<NW, IPL>::tid();
-    if ((q & 3) == 0 && i0 + IPL <= L) {
+    for (int k = 0; k < N; ++k)
+        if (64 * k + lane_id() < L) a[q + 64 * k + lane_id()] = (int32_t)v[k];
+}
+// coordinates (8 bytes each, 512 bytes per store), nontemporal
+template <int N>
+__device__ __forceinline__ void store_lm_xy(uint64_t* a, int32_t q, int32_t L, const uint64_t (&v)[N]) {
 #pragma unroll
-        for (int k = 0; k < IPL; k += 4)
-            *(i32x4*)(a + q + i0 + k) = i32x4{(int32_t)v[k], (int32_t)v[k + 1], (int32_t)v[k + 2], (int32_t)v[k + 3]};
+    for (int k = 0; k < N; ++k)
+        if (64 * k + lane_id() < L) __builtin_nontemporal_store(v[k], a + q + 64 * k + lane_id());
+}
+// a workgroup thread's four consecutive items q + 4 t + k of a step of L: a 16-byte store when the thread's
+// items are valid and aligned (arrays are 16-byte aligned; aligned when q % 4 == 0), else element stores
+__device__ __forceinline__ void store4(int32_t* a, int32_t q, int32_t L, const uint32_t (&v)[4]) {
+    const int32_t i0 = 4 * (int32_t)threadIdx.x;
+    if ((q & 3) == 0 && i0 + 4 <= L) {
+        *(i32x4*)(a + q + i0) = i32x4{(int32_t)v[0], (int32_t)v[1], (int32_t)v[2], (int32_t)v[3]};
     } else {
 #pragma unroll
-        for (int k = 0; k < IPL; ++k)
+        for (int k = 0; k < 4; ++k)
             if (i0 + k < L) a[q + i0 + k] = (int32_t)v[k];
     }
 }
 // coordinates (8 bytes each): 16-byte nontemporal stores for aligned valid items
-template <int NW, int IPL>
-__device__ __forceinline__ void store4_xy(uint64_t* a, int32_t q, int32_t L, const uint64_t (&v)[IPL]) {
-    if (NW == 1) {  // lane-major: each store 64 consecutive coordinates (512 bytes)
-#pragma unroll
-        for (int k = 0; k < IPL; ++k)
-            if (64 * k + lane_id() < L) __builtin_nontemporal_store(v[k], a + q + 64 * k + lane_id());
-        return;
-    }
-    const int32_t i0 = IPL * Coop<NW, IPL>::tid();
-    if ((q & 3) == 0 && i0 + IPL <= L) {
+__device__ __forceinline__ void store4_xy(uint64_t* a, int32_t q, int32_t L, const uint64_t (&v)[4]) {
+    const int32_t i0 = 4 * (int32_t)threadIdx.x;
+    if ((q & 3) == 0 && i0 + 4 <= L) {
         i32x4* p = (i32x4*)(a + q + i0);
 #pragma unroll
-        for (int k = 0; k < IPL; k += 2)
+        for (int k = 0; k < 4; k += 2)
             __builtin_nontemporal_store(
                 i32x4{(int32_t)v[k], (int32_t)(v[k] >> 32), (int32_t)v[k + 1], (int32_t)(v[k + 1] >> 32)}, p + k / 2);
     } else {
 #pragma unroll
-        for (int k = 0; k < IPL; ++k)
+        for (int k = 0; k < 4; ++k)
             if (i0 + k < L) a[q + i0 + k] = v[k];
     }
 }
 
 // Segmented expansion cursor over O[0..S] (nondecreasing, O[0] = 0, O[S] = total), uniform over the
-// group.  A step covers up to K items, thread t the IPL items q + IPL t + k.
+// group.  A step covers up to K items: a workgroup's thread t the IPL items q + IPL t + k (`step`), a
+// single wave's lane l the items q + 64 k + l (`step_lm`).
 template <int NW, int IPL = 4>
 struct Expand {
     static constexpr int K = Coop<NW, IPL>::K;
@@ -135,12 +146,12 @@ struct Expand {
     int32_t obase;  // O[base]
     int32_t q;      // first item of the next step
 
-    // one step: L items (uniform); item k of the thread (valid if IPL t + k < L) gets its segment, the
-    // segment's start and end
+    // one step of a workgroup: L items (uniform); item k of the thread (valid if IPL t + k < L) gets its
+    // segment, the segment's start and end
     __device__ __forceinline__ int32_t step(AsmSmemT<NW, IPL>& sm, int& buf, int32_t (&seg)[IPL], int32_t (&start)[IPL],
                                             int32_t (&end)[IPL]) {
-        if (NW == 1) return step_lm(sm, seg, start, end);
-        const int t = Coop<NW, IPL>::tid();
+        static_assert(NW > 1, "a single wave steps lane-major (step_lm)");
+        const int t = (int)threadIdx.x;
         int32_t e[IPL];
         const int32_t j0 = base + 1 + IPL * t;  // ends of segments base + 1 + IPL t + k
         if (j0 + IPL - 1 <= S) {  // 16-byte loads (4-byte aligned)
@@ -159,16 +170,15 @@ struct Expand {
             *(i32x4*)&sm.ends[IPL * t + k] = i32x4{e[k], e[k + 1], e[k + 2], e[k + 3]};
             *(i32x4*)&sm.slot[IPL * t + k] = i32x4{0, 0, 0, 0};
         }
-        Coop<NW, IPL>::sync();
+        __syncthreads();
         int32_t r[IPL + 1];
 #pragma unroll
         for (int k = 0; k < IPL; ++k) r[k] = max(e[k] - q, 0);  // item offset where segment base+2+IPL t+k starts
-        if (NW == 1) r[IPL] = (int32_t)lane_next((uint32_t)r[0], 0x7fffffffu);
-        else r[IPL] = IPL * t + IPL < K ? max(sm.ends[IPL * t + IPL] - q, 0) : 0x7fffffff;
+        r[IPL] = IPL * t + IPL < K ? max(sm.ends[IPL * t + IPL] - q, 0) : 0x7fffffff;
 #pragma unroll
         for (int k = 0; k < IPL; ++k)
             if (r[k] < K && r[k + 1] != r[k]) sm.slot[r[k]] = IPL * t + k + 1;  // the last of equal ends wins
-        Coop<NW, IPL>::sync();
+        __syncthreads();
         uint32_t m[IPL];
 #pragma unroll
         for (int k = 0; k < IPL; k += 4) {
@@ -180,14 +190,13 @@ struct Expand {
         }
         const uint32_t wincl = incl_max_scan(m[IPL - 1]);
         uint32_t prev = wave_shr1(wincl);
-        if (NW > 1) {  // the maximum over the lower waves' marks
-            if (lane_id() == 63) sm.red[buf][Coop<NW, IPL>::wid()] = wincl;
-            __syncthreads();
+        // the maximum over the lower waves' marks
+        if (lane_id() == 63) sm.red[buf][Coop<NW, IPL>::wid()] = wincl;
+        __syncthreads();
 #pragma unroll
-            for (int i = 0; i < NW; ++i)
-                if (i < Coop<NW, IPL>::wid()) prev = max(prev, sm.red[buf][i]);
-            buf ^= 1;
-        }
+        for (int i = 0; i < NW; ++i)
+            if (i < Coop<NW, IPL>::wid()) prev = max(prev, sm.red[buf][i]);
+        buf ^= 1;
 #pragma unroll
         for (int k = 0; k < IPL; ++k) {
             const int32_t cnt = (int32_t)max(prev, m[k]);  // segment ends <= q + IPL t + k
@@ -197,19 +206,17 @@ struct Expand {
         }
         // items this step: at most K, the rest of the column, and what the K loaded ends cover
         int32_t L = min(K, total - q);
-        if (base + K < S) L = min(L, (NW == 1 ? (int32_t)lane_bcast((uint32_t)e[IPL - 1], 63) : sm.ends[K - 1]) - q);
+        if (base + K < S) L = min(L, sm.ends[K - 1] - q);
         L = max(L, 0);
         int adv = 0;  // segments ending at or before the next q
 #pragma unroll
         for (int k = 0; k < IPL; ++k) adv += __popcll(__ballot(e[k] <= q + L));
-        if (NW > 1) {
-            uint32_t tot;
-            (void)Coop<NW, IPL>::group_prefix(sm, lane_id() == 63 ? (uint32_t)adv : 0u, 0u, tot, buf);
-            buf ^= 1;
-            adv = (int)tot;
-        }
+        uint32_t tot;
+        (void)Coop<NW, IPL>::group_prefix(sm, lane_id() == 63 ? (uint32_t)adv : 0u, 0u, tot, buf);
+        buf ^= 1;
+        adv = (int)tot;
         const int32_t nob = adv > 0 ? uni(sm.ends[adv - 1]) : obase;
-        Coop<NW, IPL>::sync();
+        __syncthreads();
         obase = nob;
         base += adv;
         q += L;
@@ -266,22 +273,134 @@ struct Expand {
     }
 };
 
-template <int NW>
-__device__ __forceinline__ void mem_publish() {  // the group's global stores visible to its own loads
+__device__ __forceinline__ void mem_publish() {  // the wave's global stores visible to its own loads
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    if (NW > 1) __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-template <int NW, int IPL = 4>
+// entries of input stream s of a column (an absent stream has a negative offset)
+__device__ __forceinline__ int32_t stream_len(const covt_geom_desc& d, int s) { return d.in_off[s] >= 0 ? d.in_len[s] : 0; }
+
+// One column: its decoded input streams, its output arrays and capacities (from the descriptor), and the
+// per-item rule of each pass.  The rules say what an item is and yields; they do not know the order items
+// are held in, nor where a count-stream entry comes from (`fetch(i)` reads entry i: a wave picks it from
+// its LDS window, a chunk loads it).  Both walkers below apply them and add only what is theirs.
+struct Column {
+    const uint8_t* types;
+    const int32_t *go, *po, *ro, *vo;
+    const uint64_t* vb;  // x,y pairs
+    int32_t n, n_go, n_po, n_ro, n_vo, n_vb;
+    bool ice;       // vertices through vertexOffsets
+    int32_t n_src;  // source vertices the rings can consume
+    bool closed;    // polygon rings carry their closing vertex in the stream
+    int32_t *geo_off, *part_off, *ring_off;
+    uint64_t* coords;
+    int32_t *part_scr, *ring_scr;
+    uint32_t pcap, rcap, ccap;
+
+    __device__ __forceinline__ Column(const uint8_t* dec, const covt_geom_desc& d, uint8_t* outb)
+        : types(dec + d.in_off[0]), go((const int32_t*)(dec + d.in_off[1])), po((const int32_t*)(dec + d.in_off[2])),
+          ro((const int32_t*)(dec + d.in_off[3])), vo((const int32_t*)(dec + d.in_off[4])),
+          vb((const uint64_t*)(dec + d.in_off[5])), n(stream_len(d, 0)), n_go(stream_len(d, 1)),
+          n_po(stream_len(d, 2)), n_ro(stream_len(d, 3)), n_vo(stream_len(d, 4)), n_vb(stream_len(d, 5)),
+          ice(d.in_off[4] >= 0), n_src(ice ? n_vo : n_vb), closed(d.flags & COVT_GEOM_CLOSED_IN_STREAM),
+          geo_off((int32_t*)(outb + d.out_off[0])), part_off((int32_t*)(outb + d.out_off[1])),
+          ring_off((int32_t*)(outb + d.out_off[2])), coords((uint64_t*)(outb + d.out_off[3])),
+          part_scr((int32_t*)(outb + d.out_off[4])), ring_scr((int32_t*)(outb + d.out_off[5])),
+          pcap((uint32_t)d.part_cap), rcap((uint32_t)d.ring_cap), ccap((uint32_t)d.coord_cap) {}
+
+    // an item that consumes entry i of a count stream of `len` entries: c = the entry clamped to cap + 1
+    // (the scans saturate, so a clamped count still fails the capacity check); a negative entry or one
+    // past the stream's end sets `bad` (COUNT_MISMATCH) and, past the end, leaves c as it was
+    template <class Fetch>
+    __device__ __forceinline__ static void take_count(bool consumes, uint32_t& c, uint32_t i, int32_t len, uint32_t cap,
+                                                      bool& bad, Fetch fetch) {
+        if (!consumes) return;
+        if (i < (uint32_t)len) {
+            const int32_t v = fetch(i);
+            bad |= v < 0;
+            c = min((uint32_t)max(v, 0), cap + 1u);
+        } else {
+            bad = true;
+        }
+    }
+    // pass 1, feature of type t (0 past the step's items): MULTI* features (returned 1) take their part
+    // count from geometryOffsets, the others are one part
+    __device__ __forceinline__ static uint32_t feature(uint32_t t, bool valid, bool& bad_type, bool& has_poly) {
+        bad_type |= t > 5u;  // GeometryType.values()[b]
+        has_poly |= t == 2u || t == 5u;
+        return (valid && t >= 3u && t <= 5u) ? 1u : 0u;
+    }
+    template <class Fetch>
+    __device__ __forceinline__ void feature_parts(uint32_t multi, uint32_t& parts, uint32_t i, bool& bad, Fetch fetch) const {
+        take_count(multi, parts, i, n_go, pcap, bad, fetch);
+    }
+    // pass 2, part of a feature of type t: line and polygon parts (returned 1) take a partOffsets entry c
+    // (`part_count`; 0 for the others) -- a polygon's ring count, a line's vertex count.  `part` gives the
+    // part's rings and its scratch word: 1 for a polygon part, else the vertex count << 1
+    __device__ __forceinline__ static uint32_t part_uses_po(uint32_t t, bool valid) {
+        return (valid && t != 0u && t != 3u) ? 1u : 0u;
+    }
+    template <class Fetch>
+    __device__ __forceinline__ uint32_t part_count(uint32_t usep, uint32_t i, bool& bad, Fetch fetch) const {
+        uint32_t c = 0;
+        take_count(usep, c, i, n_po, rcap, bad, fetch);
+        return c;
+    }
+    __device__ __forceinline__ void part(uint32_t t, bool valid, uint32_t c, uint32_t& rings, uint32_t& word) const {
+        const bool poly = t == 2u || t == 5u;
+        rings = valid ? (poly ? c : 1u) : 0u;
+        const uint32_t vcount = (t == 1u || t == 4u) ? c : 1u;  // vertices of a line / point part
+        word = poly ? 1u : (min(vcount, ccap + 1u) << 1);
+    }
+    // pass 3, ring of a part with scratch word `word` (0 past the step's items): a polygon ring takes its
+    // vertex count from ringOffsets (`ring_count`), the single ring of another part has the word's; `ring`
+    // gives the closing vertex to insert and the ring's output vertices; `ring_word` is the ring's scratch
+    // word: its first source vertex, bit 31 the closing flag
+    __device__ __forceinline__ static void ring_part(int32_t word, bool valid, uint32_t& poly, uint32_t& vs) {
+        poly = (valid && (word & 1)) ? 1u : 0u;
+        vs = valid ? (uint32_t)word >> 1 : 0u;
+    }
+    template <class Fetch>
+    __device__ __forceinline__ void ring_count(uint32_t poly, uint32_t& vs, uint32_t i, bool& bad, Fetch fetch) const {
+        take_count(poly, vs, i, n_ro, ccap, bad, fetch);
+    }
+    __device__ __forceinline__ void ring(uint32_t poly, uint32_t vs, uint32_t& closing, uint32_t& vout) const {
+        closing = (poly && !closed && vs > 0u) ? 1u : 0u;
+        vout = vs + closing;
+    }
+    __device__ __forceinline__ static uint32_t ring_word(uint32_t first, uint32_t closing) { return first | (closing << 31); }
+    // pass 4, coordinate v of a ring [rs, re) with scratch word `word`: the index into the vertex buffer
+    // (source vertex first + rank, the closing coordinate repeats the first; ICE: through vertexOffsets)
+    __device__ __forceinline__ int32_t coord_index(uint32_t word, int32_t v, int32_t rs, int32_t re, bool valid) const {
+        const int32_t first = (int32_t)(word & 0x7fffffffu);
+        const int32_t src = ((word >> 31) && v == re - 1) ? first : first + (v - rs);
+        return valid ? (ice ? ((const g_i32*)vo)[src] : src) : 0;
+    }
+    // the x,y pair at idx (`load(idx)` reads it); out of range sets bad_idx: vertexBuffer[offset]
+    // (ArrayIndexOutOfBounds)
+    template <class Load>
+    __device__ __forceinline__ uint64_t gather(int32_t idx, bool valid, bool& bad_idx, Load load) const {
+        const bool inr = (uint32_t)idx < (uint32_t)n_vb;
+        bad_idx |= valid && !inr;
+        return (valid && inr) ? load(idx) : 0ull;
+    }
+    __device__ __forceinline__ uint64_t gather(int32_t idx, bool valid, bool& bad_idx) const {
+        return gather(idx, valid, bad_idx, [&](int32_t i) { return ((const g_u64*)vb)[i]; });
+    }
+};
+
+// One wave walks a column's four passes, IPL lane-major items per lane and step.  Its own: one-item
+// segments skip the expansion (ident_step), a column without polygons finishes in pass 2 (nopoly), the count
+// windows, pass 4's two-step straight copy with nontemporal loads, the ablation stops.
+template <int IPL>
 __device__ void assemble_column(const uint8_t* __restrict__ dec, const covt_stream_result* __restrict__ dres,
                                 const covt_geom_desc& d, uint8_t* __restrict__ outb, covt_geom_result& res,
-                                AsmSmemT<NW, IPL>& sm) {
-    constexpr int K = Coop<NW, IPL>::K;
-    const int l = Coop<NW, IPL>::tid();
-    // step item of this thread's k-th item: lane-major for a wave, IPL consecutive per thread for a group
-    auto ioff = [&](int k) { return NW == 1 ? 64 * k + l : IPL * l + k; };
-    int buf = 0;  // cooperative partials buffer (see excl_scan4)
+                                AsmSmemT<1, IPL>& sm) {
+    constexpr int K = 64 * IPL;
+    const int l = lane_id();
+    auto ioff = [&](int k) { return 64 * k + l; };  // step item of this lane's k-th item
+    int buf = 0;  // (excl_scan4's partials buffer: a wave has none)
     res.num_parts = res.num_rings = res.num_coords = 0;
     if ((uint32_t)d.flags & COVT_GEOM_TOO_LARGE) { res.status = COVT_ERR_INVALID_ARG; return; }
     for (int k = 0; k < 6; ++k) {  // a failed source stream fails the column
@@ -291,28 +410,9 @@ __device__ void assemble_column(const uint8_t* __restrict__ dec, const covt_stre
             if (st) { res.status = st; return; }
         }
     }
-    const uint8_t* types = dec + d.in_off[0];
-    const int32_t* go = (const int32_t*)(dec + d.in_off[1]);
-    const int32_t* po = (const int32_t*)(dec + d.in_off[2]);
-    const int32_t* ro = (const int32_t*)(dec + d.in_off[3]);
-    const int32_t* vo = (const int32_t*)(dec + d.in_off[4]);
-    const uint64_t* vb = (const uint64_t*)(dec + d.in_off[5]);  // x,y pairs
-    const int32_t n = d.in_off[0] >= 0 ? d.in_len[0] : 0;
-    const int32_t n_go = d.in_off[1] >= 0 ? d.in_len[1] : 0;
-    const int32_t n_po = d.in_off[2] >= 0 ? d.in_len[2] : 0;
-    const int32_t n_ro = d.in_off[3] >= 0 ? d.in_len[3] : 0;
-    const bool ice = d.in_off[4] >= 0;
-    const int32_t n_vo = ice ? d.in_len[4] : 0;
-    const int32_t n_vb = d.in_off[5] >= 0 ? d.in_len[5] : 0;
-    const int32_t n_src = ice ? n_vo : n_vb;  // source vertices the rings can consume
-    const bool closed = d.flags & COVT_GEOM_CLOSED_IN_STREAM;
-    int32_t* geo_off = (int32_t*)(outb + d.out_off[0]);
-    int32_t* part_off = (int32_t*)(outb + d.out_off[1]);
-    int32_t* ring_off = (int32_t*)(outb + d.out_off[2]);
-    uint64_t* coords = (uint64_t*)(outb + d.out_off[3]);
-    int32_t* part_scr = (int32_t*)(outb + d.out_off[4]);
-    int32_t* ring_scr = (int32_t*)(outb + d.out_off[5]);
-    const uint32_t pcap = (uint32_t)d.part_cap, rcap = (uint32_t)d.ring_cap, ccap = (uint32_t)d.coord_cap;
+    const Column col(dec, d, outb);
+    const int32_t n = col.n;
+    const uint32_t pcap = col.pcap, rcap = col.rcap, ccap = col.ccap;
     bool bad_type = false, bad_cnt = false;
 
     // ---- pass 1: features -> parts (items: features) ----
@@ -320,128 +420,93 @@ __device__ void assemble_column(const uint8_t* __restrict__ dec, const covt_stre
     bool multi_n = false;   // some feature's part count is not 1
     bool has_poly = false;  // some feature is a polygon or multi-polygon
     for (int32_t f0 = 0; f0 < n; f0 += K) {
-        uint32_t t[IPL], multi[IPL], gi[IPL], pf[IPL], ex[IPL], nm, tot;
-        if (NW == 1) {  // lane-major: one byte per item
+        uint32_t multi[IPL], gi[IPL], pf[IPL], ex[IPL], nm, tot;
 #pragma unroll
-            for (int k = 0; k < IPL; ++k) {
-                const bool valid = f0 + ioff(k) < n;
-                t[k] = valid ? (uint32_t)((const g_u8*)types)[f0 + ioff(k)] : 0u;
-                bad_type |= t[k] > 5u;
-                has_poly |= t[k] == 2u || t[k] == 5u;
-                multi[k] = (valid && t[k] >= 3u && t[k] <= 5u) ? 1u : 0u;
-                pf[k] = valid ? 1u : 0u;
-            }
-        } else {
-            const int32_t fl = f0 + IPL * l;  // this thread's first feature; types are 16-byte aligned
-            const uint32_t tw = fl < n ? ((const g_u32*)types)[fl >> 2] : 0u;
-#pragma unroll
-            for (int k = 0; k < IPL; ++k) {
-                const bool valid = fl + k < n;
-                t[k] = valid ? (tw >> (8 * k)) & 0xffu : 0u;
-                bad_type |= t[k] > 5u;
-                has_poly |= t[k] == 2u || t[k] == 5u;
-                multi[k] = (valid && t[k] >= 3u && t[k] <= 5u) ? 1u : 0u;
-                pf[k] = valid ? 1u : 0u;
-            }
+        for (int k = 0; k < IPL; ++k) {  // one byte per item
+            const bool valid = f0 + ioff(k) < n;
+            const uint32_t t = valid ? (uint32_t)((const g_u8*)col.types)[f0 + ioff(k)] : 0u;
+            multi[k] = Column::feature(t, valid, bad_type, has_poly);
+            pf[k] = valid ? 1u : 0u;
         }
         excl_scan4(sm, buf, multi, gi, nm);
 #pragma unroll
-        for (int k = 0; k < IPL; ++k) {
-            if (multi[k]) {
-                const uint32_t i = go_base + gi[k];
-                if (i < (uint32_t)n_go) {
-                    const int32_t c = ((const g_i32*)go)[i];
-                    bad_cnt |= c < 0;
-                    pf[k] = min((uint32_t)max(c, 0), pcap + 1u);  // clamped, and the scans saturate (group_prefix)
-                } else {
-                    bad_cnt = true;
-                }
-            }
-        }
+        for (int k = 0; k < IPL; ++k)
+            col.feature_parts(multi[k], pf[k], go_base + gi[k], bad_cnt, [&](uint32_t i) { return ((const g_i32*)col.go)[i]; });
         excl_scan4(sm, buf, pf, ex, tot);
 #pragma unroll
         for (int k = 0; k < IPL; ++k) {
             ex[k] += P;
             multi_n |= multi[k] && pf[k] != 1u;
         }
-        store4<NW>(geo_off, f0, n - f0, ex);
+        store_lm(col.geo_off, f0, n - f0, ex);
         go_base += nm;
         P = add_sat(P, tot);
-        if (Coop<NW>::any(bad_type || bad_cnt) || P > pcap) break;
+        if (wave_any(bad_type || bad_cnt) || P > pcap) break;
     }
-    if (Coop<NW>::any(bad_type)) { res.status = COVT_ERR_BAD_HEADER; return; }  // GeometryType.values()[b]
-    if (Coop<NW>::any(bad_cnt) || P > pcap) { res.status = COVT_ERR_COUNT_MISMATCH; return; }
-    if (l == 0) geo_off[n] = (int32_t)P;
-    mem_publish<NW>();
+    if (wave_any(bad_type)) { res.status = COVT_ERR_BAD_HEADER; return; }
+    if (wave_any(bad_cnt) || P > pcap) { res.status = COVT_ERR_COUNT_MISMATCH; return; }
+    if (l == 0) col.geo_off[n] = (int32_t)P;
+    mem_publish();
 
 #if defined(COVT_ASM_PASSES) && COVT_ASM_PASSES < 2  // ablation build: stop here
     res.status = COVT_OK;
     return;
 #endif
     // a pass whose segments all hold one item: item i is segment i
-    auto ident_step = [&](Expand<NW, IPL>& x, int32_t (&sg)[IPL]) {
+    auto ident_step = [&](Expand<1, IPL>& x, int32_t (&sg)[IPL]) {
         const int32_t L = min(K, x.total - x.q);
 #pragma unroll
         for (int k = 0; k < IPL; ++k) sg[k] = x.q + ioff(k);
         x.q += L;
         return L;
     };
-    const bool ident2 = !Coop<NW>::any(multi_n);
+    // the step's count window: the next K entries of a count stream from the rank base, loaded with the
+    // step's own loads, then (after the rank scan) put in LDS to be picked by rank
+    auto load_window = [&](const int32_t* cs, int32_t len, uint32_t cbase, int32_t (&w)[IPL]) {
+#pragma unroll
+        for (int k = 0; k < IPL; ++k) {
+            const uint32_t i = cbase + (uint32_t)ioff(k);
+            w[k] = i < (uint32_t)len ? ((const g_i32*)cs)[i] : 0;
+        }
+    };
+    auto put_window = [&](const int32_t (&w)[IPL]) {  // (the step's expansion is done with the LDS tables)
+        wave_sync();
+#pragma unroll
+        for (int k = 0; k < IPL; ++k) sm.slot[ioff(k)] = w[k];
+        wave_sync();
+    };
+    const bool ident2 = !wave_any(multi_n);
     // no polygon: every part is one ring (rings = parts), so pass 2 also writes the ring offsets (the
     // exclusive scan of the parts' vertex counts) and pass 3, with both scratch arrays, is skipped
-    const bool nopoly = !Coop<NW>::any(has_poly);
+    const bool nopoly = !wave_any(has_poly);
     uint32_t V = 0, VS = 0;
     // ---- pass 2: parts -> rings (items: parts, segments: features) ----
     uint32_t po_base = 0, R = 0;
     bool poly_n = false;  // some part's ring count is not 1
     {
-        Expand<NW, IPL> x{geo_off, n, (int32_t)P, 0, 0, 0};
+        Expand<1, IPL> x{col.geo_off, n, (int32_t)P, 0, 0, 0};
         while (x.q < x.total) {
             const int32_t p0 = x.q;
             int32_t f[IPL], fs[IPL], fe[IPL], pw[IPL];
-            constexpr bool kWin = NW == 1 && COVT_ASM_WIN;
-            if (kWin) {
-#pragma unroll
-                for (int k = 0; k < IPL; ++k) {
-                    const uint32_t i = po_base + (uint32_t)ioff(k);
-                    pw[k] = i < (uint32_t)n_po ? ((const g_i32*)po)[i] : 0;
-                }
-            }
+            if (kAsmWin) load_window(col.po, col.n_po, po_base, pw);
             // one part per feature (no multi-geometry with a count other than 1): part p is feature p, no
             // expansion (most columns; the step's loads, marks and scans are half of the pass)
-            const int32_t L = ident2 ? ident_step(x, f) : x.step(sm, buf, f, fs, fe);
+            const int32_t L = ident2 ? ident_step(x, f) : x.step_lm(sm, f, fs, fe);
             uint32_t t[IPL], usep[IPL], pi[IPL], rp[IPL], scr[IPL], ex[IPL], npo, tot;
 #pragma unroll
             for (int k = 0; k < IPL; ++k) {
                 const bool valid = ioff(k) < L;
-                t[k] = valid ? (uint32_t)((const g_u8*)types)[f[k]] : 0u;
-                usep[k] = (valid && t[k] != 0u && t[k] != 3u) ? 1u : 0u;  // line and polygon parts
+                t[k] = valid ? (uint32_t)((const g_u8*)col.types)[f[k]] : 0u;
+                usep[k] = Column::part_uses_po(t[k], valid);
             }
             excl_scan4(sm, buf, usep, pi, npo);
-            if (kWin) {  // (the step's expansion is done with the LDS tables)
-                wave_sync();
-#pragma unroll
-                for (int k = 0; k < IPL; ++k) sm.slot[ioff(k)] = pw[k];
-                wave_sync();
-            }
+            if (kAsmWin) put_window(pw);
 #pragma unroll
             for (int k = 0; k < IPL; ++k) {
-                const bool valid = ioff(k) < L;
-                uint32_t c = 0;
-                if (usep[k]) {
-                    const uint32_t i = po_base + pi[k];
-                    if (i < (uint32_t)n_po) {
-                        const int32_t v = kWin ? sm.slot[pi[k]] : ((const g_i32*)po)[i];
-                        bad_cnt |= v < 0;
-                        c = min((uint32_t)max(v, 0), rcap + 1u);
-                    } else {
-                        bad_cnt = true;
-                    }
-                }
-                const bool poly = t[k] == 2u || t[k] == 5u;
-                rp[k] = valid ? (poly ? c : 1u) : 0u;
-                const uint32_t vcount = (t[k] == 1u || t[k] == 4u) ? c : 1u;  // vertices of a line / point part
-                scr[k] = poly ? 1u : (min(vcount, ccap + 1u) << 1);
+                const uint32_t c = col.part_count(usep[k], po_base + pi[k], bad_cnt, [&](uint32_t i) {
+                    return kAsmWin ? sm.slot[pi[k]] : ((const g_i32*)col.po)[i];
+                });
+                col.part(t[k], ioff(k) < L, c, rp[k], scr[k]);
             }
             excl_scan4(sm, buf, rp, ex, tot);
 #pragma unroll
@@ -449,7 +514,7 @@ __device__ void assemble_column(const uint8_t* __restrict__ dec, const covt_stre
                 ex[k] += R;
                 poly_n |= ioff(k) < L && rp[k] != 1u;
             }
-            store4<NW>(part_off, p0, L, ex);
+            store_lm(col.part_off, p0, L, ex);
             if (nopoly) {  // ring p = part p: its coordinates start at the scan of the vertex counts
                 uint32_t vc[IPL], vex[IPL], vt;
 #pragma unroll
@@ -457,92 +522,69 @@ __device__ void assemble_column(const uint8_t* __restrict__ dec, const covt_stre
                 excl_scan4(sm, buf, vc, vex, vt);
 #pragma unroll
                 for (int k = 0; k < IPL; ++k) vex[k] += V;
-                store4<NW>(ring_off, p0, L, vex);
+                store_lm(col.ring_off, p0, L, vex);
                 V = add_sat(V, vt);
             } else {
-                store4<NW>(part_scr, p0, L, scr);
+                store_lm(col.part_scr, p0, L, scr);
             }
             po_base += npo;
             R = add_sat(R, tot);
-            if (Coop<NW>::any(bad_cnt) || R > rcap || (nopoly && V > ccap)) break;
+            if (wave_any(bad_cnt) || R > rcap || (nopoly && V > ccap)) break;
         }
     }
-    if (Coop<NW>::any(bad_cnt) || R > rcap) { res.status = COVT_ERR_COUNT_MISMATCH; return; }
-    if (l == 0) part_off[P] = (int32_t)R;
-    mem_publish<NW>();
+    if (wave_any(bad_cnt) || R > rcap) { res.status = COVT_ERR_COUNT_MISMATCH; return; }
+    if (l == 0) col.part_off[P] = (int32_t)R;
+    mem_publish();
 
 #if defined(COVT_ASM_PASSES) && COVT_ASM_PASSES < 3  // ablation build: stop here
     res.status = COVT_OK;
     return;
 #endif
-    const bool ident3 = !Coop<NW>::any(poly_n);
+    const bool ident3 = !wave_any(poly_n);
     // ---- pass 3: rings -> coordinates (items: rings, segments: parts) ----
     uint32_t ro_base = 0;
     if (nopoly) {
         VS = V;  // (no closing vertex; the checks of pass 3's end)
     } else {
-        Expand<NW, IPL> x{part_off, (int32_t)P, (int32_t)R, 0, 0, 0};
+        Expand<1, IPL> x{col.part_off, (int32_t)P, (int32_t)R, 0, 0, 0};
         while (x.q < x.total) {
             const int32_t r0 = x.q;
             int32_t p[IPL], ps[IPL], pe[IPL], rw[IPL];
-            constexpr bool kWin = NW == 1 && COVT_ASM_WIN;
-            if (kWin) {
-#pragma unroll
-                for (int k = 0; k < IPL; ++k) {
-                    const uint32_t i = ro_base + (uint32_t)ioff(k);
-                    rw[k] = i < (uint32_t)n_ro ? ((const g_i32*)ro)[i] : 0;
-                }
-            }
-            const int32_t L = ident3 ? ident_step(x, p) : x.step(sm, buf, p, ps, pe);  // (one ring per part)
-            uint32_t poly[IPL], ri[IPL], vs[IPL], vo_[IPL], ex[IPL], src[IPL], nr, tv, ts;
+            if (kAsmWin) load_window(col.ro, col.n_ro, ro_base, rw);
+            const int32_t L = ident3 ? ident_step(x, p) : x.step_lm(sm, p, ps, pe);  // (one ring per part)
+            uint32_t poly[IPL], ri[IPL], vs[IPL], closing[IPL], vo_[IPL], ex[IPL], src[IPL], nr, tv, ts;
 #pragma unroll
             for (int k = 0; k < IPL; ++k) {
                 const bool valid = ioff(k) < L;
-                const int32_t sp = valid ? ((const g_i32*)part_scr)[p[k]] : 0;
-                poly[k] = (valid && (sp & 1)) ? 1u : 0u;
-                vs[k] = valid ? (uint32_t)sp >> 1 : 0u;
+                Column::ring_part(valid ? ((const g_i32*)col.part_scr)[p[k]] : 0, valid, poly[k], vs[k]);
             }
             excl_scan4(sm, buf, poly, ri, nr);
-            if (kWin) {
-                wave_sync();
-#pragma unroll
-                for (int k = 0; k < IPL; ++k) sm.slot[ioff(k)] = rw[k];
-                wave_sync();
-            }
-            uint32_t closing[IPL];
+            if (kAsmWin) put_window(rw);
 #pragma unroll
             for (int k = 0; k < IPL; ++k) {
-                if (poly[k]) {
-                    const uint32_t i = ro_base + ri[k];
-                    if (i < (uint32_t)n_ro) {
-                        const int32_t v = kWin ? sm.slot[ri[k]] : ((const g_i32*)ro)[i];
-                        bad_cnt |= v < 0;
-                        vs[k] = min((uint32_t)max(v, 0), ccap + 1u);
-                    } else {
-                        bad_cnt = true;
-                    }
-                }
-                closing[k] = (poly[k] && !closed && vs[k] > 0u) ? 1u : 0u;
-                vo_[k] = vs[k] + closing[k];
+                col.ring_count(poly[k], vs[k], ro_base + ri[k], bad_cnt, [&](uint32_t i) {
+                    return kAsmWin ? sm.slot[ri[k]] : ((const g_i32*)col.ro)[i];
+                });
+                col.ring(poly[k], vs[k], closing[k], vo_[k]);
             }
             excl_scan4(sm, buf, vo_, ex, tv);
             excl_scan4(sm, buf, vs, src, ts);
 #pragma unroll
             for (int k = 0; k < IPL; ++k) {
                 ex[k] += V;
-                src[k] = (VS + src[k]) | (closing[k] << 31);
+                src[k] = Column::ring_word(VS + src[k], closing[k]);
             }
-            store4<NW>(ring_off, r0, L, ex);
-            if (!closed) store4<NW>(ring_scr, r0, L, src);  // (read by pass 4 only when rings get a closing vertex)
+            store_lm(col.ring_off, r0, L, ex);
+            if (!col.closed) store_lm(col.ring_scr, r0, L, src);  // (read by pass 4 only when rings get a closing vertex)
             ro_base += nr;
             V = add_sat(V, tv);
             VS = add_sat(VS, ts);
-            if (Coop<NW>::any(bad_cnt) || V > ccap || VS > (uint32_t)n_src) break;
+            if (wave_any(bad_cnt) || V > ccap || VS > (uint32_t)col.n_src) break;
         }
     }
-    if (Coop<NW>::any(bad_cnt) || V > ccap || VS > (uint32_t)n_src) { res.status = COVT_ERR_COUNT_MISMATCH; return; }
-    if (l == 0) ring_off[R] = (int32_t)V;
-    mem_publish<NW>();
+    if (wave_any(bad_cnt) || V > ccap || VS > (uint32_t)col.n_src) { res.status = COVT_ERR_COUNT_MISMATCH; return; }
+    if (l == 0) col.ring_off[R] = (int32_t)V;
+    mem_publish();
 
 #if defined(COVT_ASM_PASSES) && COVT_ASM_PASSES < 4  // ablation build: stop here
     res.status = COVT_OK;
@@ -553,88 +595,44 @@ __device__ void assemble_column(const uint8_t* __restrict__ dec, const covt_stre
     if (V == VS) {
         // no closing vertex to insert: coordinate v is source vertex v (a straight copy / gather).  Two
         // steps per iteration, their index loads and gathers issued before any store (stores may alias
-        // the loads as far as the compiler knows, so a one-step loop waits out every chain in turn)
-        auto idx4 = [&](int32_t i0, int32_t (&idx)[IPL]) {
-            if (ice && i0 + IPL <= (int32_t)V) {  // vertexOffsets are 16-byte aligned, i0 % 4 == 0
+        // the loads as far as the compiler knows, so a one-step loop waits out every chain in turn);
+        // every instruction covers 64 consecutive coordinates
+        const bool ice = col.ice;
+        for (int32_t v0 = 0; v0 < (int32_t)V; v0 += 2 * K) {
+            int32_t ia[2 * IPL];
 #pragma unroll
-                for (int k = 0; k < IPL; k += 4) {
-                    const i32x4 w = *(const g_i32x4*)(vo + i0 + k);
-                    idx[k] = w.x; idx[k + 1] = w.y; idx[k + 2] = w.z; idx[k + 3] = w.w;
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < IPL; ++k)
-                    idx[k] = i0 + k < (int32_t)V ? (ice ? ((const g_i32*)vo)[i0 + k] : i0 + k) : 0;
+            for (int k = 0; k < 2 * IPL; ++k) {
+                const int32_t i = v0 + ioff(k);
+                // (vertexOffsets are read once: streamed past L2, which keeps the dictionary the gathers reuse)
+                ia[k] = i < (int32_t)V ? (ice ? (COVT_ASM_NT ? __builtin_nontemporal_load(col.vo + i) : ((const g_i32*)col.vo)[i]) : i) : 0;
             }
-        };
-        auto gather4 = [&](int32_t i0, const int32_t (&idx)[IPL], uint64_t (&xy)[IPL]) {
+            uint64_t xa[2 * IPL];
 #pragma unroll
-            for (int k = 0; k < IPL; ++k) {
-                const bool valid = i0 + k < (int32_t)V;
-                const bool inr = (uint32_t)idx[k] < (uint32_t)n_vb;
-                bad_idx |= valid && !inr;
-                xy[k] = (valid && inr) ? ((const g_u64*)vb)[idx[k]] : 0ull;
-            }
-        };
-        if (NW == 1) {  // lane-major: two steps per iteration, every instruction 64 consecutive coordinates
-            for (int32_t v0 = 0; v0 < (int32_t)V; v0 += 2 * K) {
-                int32_t ia[2 * IPL];
-#pragma unroll
-                for (int k = 0; k < 2 * IPL; ++k) {
-                    const int32_t i = v0 + 64 * k + l;
-                    // (vertexOffsets are read once: streamed past L2, which keeps the dictionary the gathers reuse)
-                    ia[k] = i < (int32_t)V ? (ice ? (COVT_ASM_NT ? __builtin_nontemporal_load(vo + i) : ((const g_i32*)vo)[i]) : i) : 0;
-                }
-                uint64_t xa[2 * IPL];
-#pragma unroll
-                for (int k = 0; k < 2 * IPL; ++k) {
-                    const bool valid = v0 + 64 * k + l < (int32_t)V;
-                    const bool inr = (uint32_t)ia[k] < (uint32_t)n_vb;
-                    bad_idx |= valid && !inr;
-                    // (a plain column's vertices are copied once: streamed too; an ICE dictionary is gathered ~2.7
-                    // times per vertex and stays cached)
-                    xa[k] = (valid && inr) ? ((COVT_ASM_NT && !ice) ? __builtin_nontemporal_load(vb + ia[k]) : ((const g_u64*)vb)[ia[k]]) : 0ull;
-                }
-#pragma unroll
-                for (int k = 0; k < 2 * IPL; ++k)
-                    if (v0 + 64 * k + l < (int32_t)V) __builtin_nontemporal_store(xa[k], coords + v0 + 64 * k + l);
-            }
-        } else {
-            for (int32_t v0 = 0; v0 < (int32_t)V; v0 += 2 * K) {
-                const int32_t i0 = v0 + IPL * l, i1 = i0 + K;
-                int32_t ia[IPL], ib[IPL];
-                idx4(i0, ia);
-                idx4(i1, ib);
-                uint64_t xa[IPL], xb[IPL];
-                gather4(i0, ia, xa);
-                gather4(i1, ib, xb);
-                store4_xy<NW>(coords, v0, (int32_t)V - v0, xa);
-                if (v0 + K < (int32_t)V) store4_xy<NW>(coords, v0 + K, (int32_t)V - v0 - K, xb);
-            }
+            for (int k = 0; k < 2 * IPL; ++k)
+                // (a plain column's vertices are copied once: streamed too; an ICE dictionary is gathered ~2.7
+                // times per vertex and stays cached)
+                xa[k] = col.gather(ia[k], v0 + ioff(k) < (int32_t)V, bad_idx, [&](int32_t i) {
+                    return (COVT_ASM_NT && !ice) ? __builtin_nontemporal_load(col.vb + i) : ((const g_u64*)col.vb)[i];
+                });
+            store_lm_xy(col.coords, v0, (int32_t)V - v0, xa);
         }
     } else {
-        Expand<NW, IPL> x{ring_off, (int32_t)R, (int32_t)V, 0, 0, 0};
+        Expand<1, IPL> x{col.ring_off, (int32_t)R, (int32_t)V, 0, 0, 0};
         while (x.q < x.total) {
             const int32_t v0 = x.q;
             int32_t r[IPL], rs[IPL], re[IPL];
-            const int32_t L = x.step(sm, buf, r, rs, re);
+            const int32_t L = x.step_lm(sm, r, rs, re);
             uint64_t xy[IPL];
 #pragma unroll
             for (int k = 0; k < IPL; ++k) {
-                const int32_t v = v0 + ioff(k);
                 const bool valid = ioff(k) < L;
-                const uint32_t sr = valid ? (uint32_t)((const g_i32*)ring_scr)[r[k]] : 0u;
-                const int32_t first = (int32_t)(sr & 0x7fffffffu);
-                const int32_t src = ((sr >> 31) && v == re[k] - 1) ? first : first + (v - rs[k]);
-                const int32_t idx = valid ? (ice ? ((const g_i32*)vo)[src] : src) : 0;
-                const bool inr = (uint32_t)idx < (uint32_t)n_vb;
-                bad_idx |= valid && !inr;  // vertexBuffer[offset] out of range (ArrayIndexOutOfBounds)
-                xy[k] = (valid && inr) ? ((const g_u64*)vb)[idx] : 0ull;
+                const uint32_t sr = valid ? (uint32_t)((const g_i32*)col.ring_scr)[r[k]] : 0u;
+                xy[k] = col.gather(col.coord_index(sr, v0 + ioff(k), rs[k], re[k], valid), valid, bad_idx);
             }
-            store4_xy<NW>(coords, v0, L, xy);
+            store_lm_xy(col.coords, v0, L, xy);
         }
     }
-    if (Coop<NW>::any(bad_idx)) { res.status = COVT_ERR_TRUNCATED; return; }
+    if (wave_any(bad_idx)) { res.status = COVT_ERR_TRUNCATED; return; }
     res.status = COVT_OK;
     res.num_parts = (int32_t)P;
     res.num_rings = (int32_t)R;
@@ -643,8 +641,7 @@ __device__ void assemble_column(const uint8_t* __restrict__ dec, const covt_stre
 
 // the items a column's passes step over (features, parts, rings, coordinates): its capacities
 __device__ __forceinline__ int32_t column_items(const covt_geom_desc& d) {
-    const int32_t n = d.in_off[0] >= 0 ? d.in_len[0] : 0;
-    return max(max(n, d.part_cap), max(d.ring_cap, d.coord_cap));
+    return max(max(stream_len(d, 0), d.part_cap), max(d.ring_cap, d.coord_cap));
 }
 
 // one wave per column (large batches: every wave has a column, the batch keeps the chip busy)
@@ -659,7 +656,7 @@ __global__ __launch_bounds__(64 * kAsmWaves) void assemble_kernel(const uint8_t*
     if (c >= n_cols) return;
     const covt_geom_desc d = descs[c];
     covt_geom_result r{COVT_OK, 0, 0, 0};
-    assemble_column<1, kAsmIpl>(dec, dres, d, outb, r, smem[w]);
+    assemble_column<kAsmIpl>(dec, dres, d, outb, r, smem[w]);
     if (lane_id() == 0) gres[c] = r;
 }
 
@@ -708,8 +705,7 @@ struct SplitScratch {
 
 // chunks per pass of a column: ceil(capacity / kSplitK) (chunks past the pass's real item count exit)
 __device__ __forceinline__ void split_chunks(const covt_geom_desc& d, int32_t (&c)[4]) {
-    const int32_t n = d.in_off[0] >= 0 ? d.in_len[0] : 0;
-    c[0] = max(1, (n + kSplitK - 1) / kSplitK);  // at least one chunk: chunk 0 writes the terminal offset
+    c[0] = max(1, (stream_len(d, 0) + kSplitK - 1) / kSplitK);  // at least one chunk: chunk 0 writes the terminal offset
     c[1] = max(1, (d.part_cap + kSplitK - 1) / kSplitK);
     c[2] = max(1, (d.ring_cap + kSplitK - 1) / kSplitK);
     c[3] = max(1, (d.coord_cap + kSplitK - 1) / kSplitK);
@@ -888,7 +884,16 @@ __device__ __forceinline__ void split_bases(int2* __restrict__ base, int32_t nch
         base[b] = make_int2(seg, (int32_t)s);
 }
 
-// one chunk of one pass of split column k (global chunk g of the pass)
+// what a sweep over a chunk's steps (passes 2 and 3) does with each step: the count-stream rank only; the
+// counts and their scans too (the chunk's totals); and the stores
+enum { kSweepRank, kSweepTotals, kSweepStore };
+
+// One chunk of one pass of split column k (chunk j of the column), by a 16-wave workgroup, four consecutive
+// items per thread: Column's rules on the chunk's items.  Its own: the chained scans' publish-and-gather,
+// the next pass's chunk starts (split_bases), failure marks (split_fail, only after the chunk's gathers),
+// the last chunk's totals.  Passes 2 and 3 need the rank before the chunk (a gather) to read their
+// counts, and the counts' total before the chunk (a second gather) to store: a sweep over the chunk's
+// steps per stage, except that a chunk of a single step keeps the step in registers between the stages.
 template <int PASS>
 __device__ void split_chunk(const uint8_t* __restrict__ dec, const covt_stream_result* __restrict__ dres,
                             const covt_geom_desc& d, uint8_t* __restrict__ outb, SplitScratch* __restrict__ sc,
@@ -899,31 +904,17 @@ __device__ void split_chunk(const uint8_t* __restrict__ dec, const covt_stream_r
     int buf = 0;
     SplitCol& st = sc->st[k];
     const int32_t g0 = sc->pre[PASS - 1][k];  // this column's first chunk slot in the pass
-    const uint8_t* types = dec + d.in_off[0];
-    const int32_t* go = (const int32_t*)(dec + d.in_off[1]);
-    const int32_t* po = (const int32_t*)(dec + d.in_off[2]);
-    const int32_t* ro = (const int32_t*)(dec + d.in_off[3]);
-    const int32_t* vo = (const int32_t*)(dec + d.in_off[4]);
-    const uint64_t* vb = (const uint64_t*)(dec + d.in_off[5]);
-    const int32_t n = d.in_off[0] >= 0 ? d.in_len[0] : 0;
-    const int32_t n_go = d.in_off[1] >= 0 ? d.in_len[1] : 0;
-    const int32_t n_po = d.in_off[2] >= 0 ? d.in_len[2] : 0;
-    const int32_t n_ro = d.in_off[3] >= 0 ? d.in_len[3] : 0;
-    const bool ice = d.in_off[4] >= 0;
-    const int32_t n_vo = ice ? d.in_len[4] : 0;
-    const int32_t n_vb = d.in_off[5] >= 0 ? d.in_len[5] : 0;
-    const int32_t n_src = ice ? n_vo : n_vb;
-    const bool closed = d.flags & COVT_GEOM_CLOSED_IN_STREAM;
-    int32_t* geo_off = (int32_t*)(outb + d.out_off[0]);
-    int32_t* part_off = (int32_t*)(outb + d.out_off[1]);
-    int32_t* ring_off = (int32_t*)(outb + d.out_off[2]);
-    uint64_t* coords = (uint64_t*)(outb + d.out_off[3]);
-    int32_t* part_scr = (int32_t*)(outb + d.out_off[4]);
-    int32_t* ring_scr = (int32_t*)(outb + d.out_off[5]);
-    const uint32_t pcap = (uint32_t)d.part_cap, rcap = (uint32_t)d.ring_cap, ccap = (uint32_t)d.coord_cap;
+    const Column col(dec, d, outb);
+    const int32_t n = col.n;
     int32_t nch[4];
     split_chunks(d, nch);
     const int32_t q0 = j * K;
+    // the chunk's total of one chained scan published, the sum over the chunks before it gathered
+    auto chain = [&](unsigned long long (*rec)[kSplitMaxChunks], uint32_t own) {
+        uint32_t o[1] = {own}, pre[1];
+        split_gather<1>(sm, rec, g0, j, o, pre, epoch);
+        return pre[0];
+    };
 
     if constexpr (PASS == 1) {
         if (j == 0) {  // a failed source stream fails the column (assemble_column's first check)
@@ -940,329 +931,211 @@ __device__ void split_chunk(const uint8_t* __restrict__ dec, const covt_stream_r
         for (int s = 0; s < 6; ++s) src_bad |= d.in_res[s] >= 0 && dres[d.in_res[s]].status != 0;
         if (src_bad) return;  // (uniform)
         if (q0 >= n) {  // no features (n == 0, chunk 0): no parts
-            if (l == 0) geo_off[0] = 0;
+            if (l == 0) col.geo_off[0] = 0;
             return;
         }
-        const int32_t fl = q0 + 4 * l;
-        const uint32_t tw = fl < n ? ((const g_u32*)types)[fl >> 2] : 0u;
-        uint32_t t[4], multi[4], gi[4], pf[4], ex[4], nm, tot;
-        bool bad_type = false, bad_cnt = false;
+        const int32_t fl = q0 + 4 * l;  // this thread's first feature; types are 16-byte aligned
+        const uint32_t tw = fl < n ? ((const g_u32*)col.types)[fl >> 2] : 0u;
+        uint32_t multi[4], gi[4], pf[4], ex[4], nm, tot;
+        bool bad_type = false, bad_cnt = false, has_poly = false;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const bool valid = fl + q < n;
-            t[q] = valid ? (tw >> (8 * q)) & 0xffu : 0u;
-            bad_type |= t[q] > 5u;
-            multi[q] = (valid && t[q] >= 3u && t[q] <= 5u) ? 1u : 0u;
+            multi[q] = Column::feature(valid ? (tw >> (8 * q)) & 0xffu : 0u, valid, bad_type, has_poly);
             pf[q] = valid ? 1u : 0u;
         }
         excl_scan4(sm, buf, multi, gi, nm);
-        uint32_t own1[1] = {nm}, pre1[1];
-        split_gather<1>(sm, sc->rec[0], g0, j, own1, pre1, epoch);
-        const uint32_t go_base = pre1[0];
+        const uint32_t go_base = chain(sc->rec[0], nm);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (multi[q]) {
-                const uint32_t i = add_sat(go_base, gi[q]);
-                if (i < (uint32_t)n_go) {
-                    const int32_t cc = ((const g_i32*)go)[i];
-                    bad_cnt |= cc < 0;
-                    pf[q] = min((uint32_t)max(cc, 0), pcap + 1u);
-                } else {
-                    bad_cnt = true;
-                }
-            }
-        }
+        for (int q = 0; q < 4; ++q)
+            col.feature_parts(multi[q], pf[q], add_sat(go_base, gi[q]), bad_cnt,
+                              [&](uint32_t i) { return ((const g_i32*)col.go)[i]; });
         excl_scan4(sm, buf, pf, ex, tot);
-        uint32_t own2[1] = {tot}, pre2[1];
-        split_gather<1>(sm, sc->rec[0] + 1, g0, j, own2, pre2, epoch);
-        const uint32_t P0 = pre2[0], P1 = add_sat(P0, tot);
+        const uint32_t P0 = chain(sc->rec[0] + 1, tot), P1 = add_sat(P0, tot);
         const bool any_type = __syncthreads_or(bad_type), any_cnt = __syncthreads_or(bad_cnt);
-        if (any_type || any_cnt || P1 > pcap) {
+        if (any_type || any_cnt || P1 > col.pcap) {
             if (l == 0) split_fail(st, 1, j, any_type ? COVT_ERR_BAD_HEADER : COVT_ERR_COUNT_MISMATCH);
             return;
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) ex[q] += P0;
-        store4<NW>(geo_off, q0, n - q0, ex);
+        store4(col.geo_off, q0, n - q0, ex);
         int2* base = sc->base[1] + sc->pre[1][k];
 #pragma unroll
         for (int q = 0; q < 4; ++q)
             if (fl + q < n) split_bases(base, nch[1], fl + q, ex[q], pf[q]);
         if (q0 + K >= n && l == 0) {  // the last chunk: the column's part count
-            geo_off[n] = (int32_t)P1;
+            col.geo_off[n] = (int32_t)P1;
             st.P = P1;
         }
     } else if constexpr (PASS == 2) {
         if (split_failed_before(st, 2)) return;
         const uint32_t P = st.P;
         if ((uint32_t)q0 >= P) {
-            if (j == 0 && l == 0) part_off[0] = 0;  // no parts: no rings
+            if (j == 0 && l == 0) col.part_off[0] = 0;  // no parts: no rings
             return;
         }
         const int32_t q1 = (int32_t)min((uint32_t)(q0 + K), P);
         const int2 b0 = sc->base[1][sc->pre[1][k] + j];
-        // sweep A: the features of the chunk's parts -> the chunk's count of partOffsets-consuming parts
-        Expand<NW> x{geo_off, n, q1, b0.x, b0.y, q0};
-        const Expand<NW> x0 = x;
-        uint32_t usep_all = 0;
+        const Expand<NW> x0{col.geo_off, n, q1, b0.x, b0.y, q0};
+        int2* base = sc->base[2] + sc->pre[2][k];
+        bool bad_cnt = false;
+        // one step's items (a one-step chunk keeps them from stage to stage)
         int32_t f[4], fs[4], fe[4], L = 0;
-        bool one_step = true;
-        uint32_t t[4], usep[4], pi[4], npo = 0;
-        while (x.q < q1) {
+        uint32_t t[4], usep[4], pi[4], rp[4], scr[4], ex[4], stot = 0, tot = 0;
+        auto rank = [&](Expand<NW>& x) {  // the step's parts: their features' types, their partOffsets rank
             L = x.step(sm, buf, f, fs, fe);
-            one_step = one_step && x.q >= q1;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const bool valid = 4 * l + q < L;
-                t[q] = valid ? (uint32_t)((const g_u8*)types)[f[q]] : 0u;
-                usep[q] = (valid && t[q] != 0u && t[q] != 3u) ? 1u : 0u;
+                t[q] = valid ? (uint32_t)((const g_u8*)col.types)[f[q]] : 0u;
+                usep[q] = Column::part_uses_po(t[q], valid);
             }
-            uint32_t stot;
             excl_scan4(sm, buf, usep, pi, stot);
-            usep_all = add_sat(usep_all, stot);
-        }
-        npo = usep_all;
-        uint32_t own1[1] = {npo}, pre1[1];
-        split_gather<1>(sm, sc->rec[1], g0, j, own1, pre1, epoch);
-        uint32_t po_base = pre1[0];
-        // sweep B: the ring counts (re-expanding only if the chunk took more than one step)
-        uint32_t R0 = 0, Rrun = 0;
-        bool bad_cnt = false;
-        int2* base = sc->base[2] + sc->pre[2][k];
-        // pass 2 has a second chained scan (rings before the chunk): gather it from the first sweep's ring
-        // totals is not possible (ring counts need po_base), so sweep B computes the totals, publishes,
-        // and stores after the gather (registers hold a single step; longer chunks redo the expansion)
-        uint32_t rp[4], scr[4], ex[4], tot = 0, rtot = 0;
-        auto ring_counts = [&](const uint32_t (&tt)[4], const uint32_t (&us)[4], const uint32_t (&pix)[4], int32_t LL,
-                               uint32_t pob) {
+        };
+        auto counts = [&](uint32_t pob) {  // their ring counts and scratch words
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const bool valid = 4 * l + q < LL;
-                uint32_t cc = 0;
-                if (us[q]) {
-                    const uint32_t i = add_sat(pob, pix[q]);
-                    if (i < (uint32_t)n_po) {
-                        const int32_t v = ((const g_i32*)po)[i];
-                        bad_cnt |= v < 0;
-                        cc = min((uint32_t)max(v, 0), rcap + 1u);
-                    } else {
-                        bad_cnt = true;
-                    }
-                }
-                const bool poly = tt[q] == 2u || tt[q] == 5u;
-                rp[q] = valid ? (poly ? cc : 1u) : 0u;
-                const uint32_t vcount = (tt[q] == 1u || tt[q] == 4u) ? cc : 1u;
-                scr[q] = poly ? 1u : (min(vcount, ccap + 1u) << 1);
+                const uint32_t cc = col.part_count(usep[q], add_sat(pob, pi[q]), bad_cnt,
+                                                   [&](uint32_t i) { return ((const g_i32*)col.po)[i]; });
+                col.part(t[q], 4 * l + q < L, cc, rp[q], scr[q]);
             }
-        };
-        if (one_step) {
-            ring_counts(t, usep, pi, L, po_base);
             excl_scan4(sm, buf, rp, ex, tot);
-            uint32_t own2[1] = {tot}, pre2[1];
-            split_gather<1>(sm, sc->rec[1] + 1, g0, j, own2, pre2, epoch);
-            R0 = pre2[0];
-            Rrun = add_sat(R0, tot);
-            const bool any_cnt = __syncthreads_or(bad_cnt);
-            if (any_cnt || Rrun > rcap) {
-                if (l == 0) split_fail(st, 2, j, COVT_ERR_COUNT_MISMATCH);
-                return;
-            }
+        };
+        auto store = [&](int32_t p0, uint32_t Rb) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) ex[q] += R0;
-            store4<NW>(part_off, q0, L, ex);
-            store4<NW>(part_scr, q0, L, scr);
+            for (int q = 0; q < 4; ++q) ex[q] += Rb;
+            store4(col.part_off, p0, L, ex);
+            store4(col.part_scr, p0, L, scr);
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                if (4 * l + q < L) split_bases(base, nch[2], q0 + 4 * l + q, ex[q], rp[q]);
-        } else {
-            // several steps: first their ring totals (no stores), then the gather, then the stores
-            x = x0;
-            uint32_t pob = po_base;
-            while (x.q < q1) {
-                L = x.step(sm, buf, f, fs, fe);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const bool valid = 4 * l + q < L;
-                    t[q] = valid ? (uint32_t)((const g_u8*)types)[f[q]] : 0u;
-                    usep[q] = (valid && t[q] != 0u && t[q] != 3u) ? 1u : 0u;
-                }
-                uint32_t stot;
-                excl_scan4(sm, buf, usep, pi, stot);
-                ring_counts(t, usep, pi, L, pob);
-                excl_scan4(sm, buf, rp, ex, tot);
-                rtot = add_sat(rtot, tot);
-                pob = add_sat(pob, stot);
-            }
-            uint32_t own2[1] = {rtot}, pre2[1];
-            split_gather<1>(sm, sc->rec[1] + 1, g0, j, own2, pre2, epoch);
-            R0 = pre2[0];
-            Rrun = add_sat(R0, rtot);
-            const bool any_cnt = __syncthreads_or(bad_cnt);
-            if (any_cnt || Rrun > rcap) {
-                if (l == 0) split_fail(st, 2, j, COVT_ERR_COUNT_MISMATCH);
-                return;
-            }
-            x = x0;
-            pob = po_base;
-            uint32_t R = R0;
-            while (x.q < q1) {
+                if (4 * l + q < L) split_bases(base, nch[2], p0 + 4 * l + q, ex[q], rp[q]);
+        };
+        // a sweep from (pob, Rb), the rank and the rings before the chunk: the chunk's totals npo, rtot; returns
+        // its steps
+        uint32_t npo = 0, rtot = 0;
+        auto sweep = [&](const int mode, uint32_t pob, uint32_t Rb) {
+            Expand<NW> x = x0;
+            int steps = 0;
+            for (npo = rtot = 0; x.q < q1; ++steps) {
                 const int32_t p0 = x.q;
-                L = x.step(sm, buf, f, fs, fe);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const bool valid = 4 * l + q < L;
-                    t[q] = valid ? (uint32_t)((const g_u8*)types)[f[q]] : 0u;
-                    usep[q] = (valid && t[q] != 0u && t[q] != 3u) ? 1u : 0u;
-                }
-                uint32_t stot;
-                excl_scan4(sm, buf, usep, pi, stot);
-                ring_counts(t, usep, pi, L, pob);
-                excl_scan4(sm, buf, rp, ex, tot);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) ex[q] += R;
-                store4<NW>(part_off, p0, L, ex);
-                store4<NW>(part_scr, p0, L, scr);
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (4 * l + q < L) split_bases(base, nch[2], p0 + 4 * l + q, ex[q], rp[q]);
-                R = add_sat(R, tot);
+                rank(x);
+                npo = add_sat(npo, stot);
+                if (mode == kSweepRank) continue;
+                counts(pob);
+                if (mode == kSweepStore) store(p0, Rb);
+                rtot = add_sat(rtot, tot);
+                Rb = add_sat(Rb, tot);
                 pob = add_sat(pob, stot);
             }
+            return steps;
+        };
+        const bool one_step = sweep(kSweepRank, 0, 0) == 1;
+        const uint32_t po_base = chain(sc->rec[1], npo);
+        if (one_step) {
+            counts(po_base);
+            rtot = tot;
+        } else {
+            sweep(kSweepTotals, po_base, 0);
         }
+        const uint32_t R0 = chain(sc->rec[1] + 1, rtot), R1 = add_sat(R0, rtot);
+        const bool any_cnt = __syncthreads_or(bad_cnt);
+        if (any_cnt || R1 > col.rcap) {
+            if (l == 0) split_fail(st, 2, j, COVT_ERR_COUNT_MISMATCH);
+            return;
+        }
+        if (one_step) store(q0, R0);
+        else sweep(kSweepStore, po_base, R0);
         if (q1 == (int32_t)P && l == 0) {  // the last chunk: the column's ring count
-            part_off[P] = (int32_t)Rrun;
-            st.R = Rrun;
+            col.part_off[P] = (int32_t)R1;
+            st.R = R1;
         }
     } else if constexpr (PASS == 3) {
         if (split_failed_before(st, 3)) return;
         const uint32_t P = st.P, R = st.R;
         if ((uint32_t)q0 >= R) {
-            if (j == 0 && l == 0) ring_off[0] = 0;  // no rings: no coordinates
+            if (j == 0 && l == 0) col.ring_off[0] = 0;  // no rings: no coordinates
             return;
         }
         const int32_t q1 = (int32_t)min((uint32_t)(q0 + K), R);
         const int2 b0 = sc->base[2][sc->pre[2][k] + j];
-        Expand<NW> x{part_off, (int32_t)P, q1, b0.x, b0.y, q0};
-        const Expand<NW> x0 = x;
-        // sweep A: polygon rings of the chunk (the ringOffsets rank)
-        uint32_t npoly = 0;
+        const Expand<NW> x0{col.part_off, (int32_t)P, q1, b0.x, b0.y, q0};
+        int2* base = sc->base[3] + sc->pre[3][k];
+        bool bad_cnt = false;
         int32_t p[4], ps[4], pe[4], L = 0;
-        uint32_t poly[4], ri[4], vs[4];
-        bool one_step = true;
-        while (x.q < q1) {
+        uint32_t poly[4], ri[4], vs[4], closing[4], vo_[4], ex[4], src[4], stot = 0, tv = 0, ts = 0;
+        auto rank = [&](Expand<NW>& x) {  // the step's rings: their parts' scratch words, their ringOffsets rank
             L = x.step(sm, buf, p, ps, pe);
-            one_step = one_step && x.q >= q1;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const bool valid = 4 * l + q < L;
-                const int32_t sp = valid ? ((const g_i32*)part_scr)[p[q]] : 0;
-                poly[q] = (valid && (sp & 1)) ? 1u : 0u;
-                vs[q] = valid ? (uint32_t)sp >> 1 : 0u;
+                Column::ring_part(valid ? ((const g_i32*)col.part_scr)[p[q]] : 0, valid, poly[q], vs[q]);
             }
-            uint32_t stot;
             excl_scan4(sm, buf, poly, ri, stot);
-            npoly = add_sat(npoly, stot);
-        }
-        uint32_t own1[1] = {npoly}, pre1[1];
-        split_gather<1>(sm, sc->rec[2], g0, j, own1, pre1, epoch);
-        const uint32_t ro_base = pre1[0];
-        bool bad_cnt = false;
-        uint32_t closing[4], vo_[4], ex[4], src[4], tv = 0, ts = 0;
-        auto vertex_counts = [&](uint32_t rob) {
+        };
+        auto counts = [&](uint32_t rob) {  // their source and output vertex counts
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                if (poly[q]) {
-                    const uint32_t i = add_sat(rob, ri[q]);
-                    if (i < (uint32_t)n_ro) {
-                        const int32_t v = ((const g_i32*)ro)[i];
-                        bad_cnt |= v < 0;
-                        vs[q] = min((uint32_t)max(v, 0), ccap + 1u);
-                    } else {
-                        bad_cnt = true;
-                    }
-                }
-                closing[q] = (poly[q] && !closed && vs[q] > 0u) ? 1u : 0u;
-                vo_[q] = vs[q] + closing[q];
+                col.ring_count(poly[q], vs[q], add_sat(rob, ri[q]), bad_cnt,
+                               [&](uint32_t i) { return ((const g_i32*)col.ro)[i]; });
+                col.ring(poly[q], vs[q], closing[q], vo_[q]);
             }
-        };
-        auto reload = [&](int32_t LL) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const bool valid = 4 * l + q < LL;
-                const int32_t sp = valid ? ((const g_i32*)part_scr)[p[q]] : 0;
-                poly[q] = (valid && (sp & 1)) ? 1u : 0u;
-                vs[q] = valid ? (uint32_t)sp >> 1 : 0u;
-            }
-        };
-        int2* base = sc->base[3] + sc->pre[3][k];
-        uint32_t V0, VS0, V1, VS1;
-        if (one_step) {
-            vertex_counts(ro_base);
             excl_scan4(sm, buf, vo_, ex, tv);
             excl_scan4(sm, buf, vs, src, ts);
-        } else {
-            x = x0;
-            uint32_t rob = ro_base;
-            while (x.q < q1) {
-                L = x.step(sm, buf, p, ps, pe);
-                reload(L);
-                uint32_t stot;
-                excl_scan4(sm, buf, poly, ri, stot);
-                vertex_counts(rob);
-                uint32_t a, b;
-                excl_scan4(sm, buf, vo_, ex, a);
-                excl_scan4(sm, buf, vs, src, b);
-                tv = add_sat(tv, a);
-                ts = add_sat(ts, b);
-                rob = add_sat(rob, stot);
-            }
-        }
-        uint32_t own2[2] = {tv, ts}, pre2[2];
-        split_gather<2>(sm, sc->rec[2] + 1, g0, j, own2, pre2, epoch);
-        V0 = pre2[0];
-        VS0 = pre2[1];
-        V1 = add_sat(V0, tv);
-        VS1 = add_sat(VS0, ts);
-        const bool any_cnt = __syncthreads_or(bad_cnt);
-        if (any_cnt || V1 > ccap || VS1 > (uint32_t)n_src) {
-            if (l == 0) split_fail(st, 3, j, COVT_ERR_COUNT_MISMATCH);
-            return;
-        }
-        auto store_rings = [&](int32_t r0, int32_t LL, uint32_t Vb, uint32_t VSb) {
+        };
+        auto store = [&](int32_t r0, uint32_t Vb, uint32_t VSb) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 ex[q] += Vb;
-                src[q] = (VSb + src[q]) | (closing[q] << 31);
+                src[q] = Column::ring_word(VSb + src[q], closing[q]);
             }
-            store4<NW>(ring_off, r0, LL, ex);
-            store4<NW>(ring_scr, r0, LL, src);
+            store4(col.ring_off, r0, L, ex);
+            store4(col.ring_scr, r0, L, src);
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                if (4 * l + q < LL) split_bases(base, nch[3], r0 + 4 * l + q, ex[q], vo_[q]);
+                if (4 * l + q < L) split_bases(base, nch[3], r0 + 4 * l + q, ex[q], vo_[q]);
         };
-        if (one_step) {
-            store_rings(q0, L, V0, VS0);
-        } else {
-            x = x0;
-            uint32_t rob = ro_base, Vb = V0, VSb = VS0;
-            while (x.q < q1) {
+        // a sweep from (rob, Vb, VSb), the rank and the output / source vertices before the chunk: the chunk's
+        // totals npoly, vtot, svtot; returns its steps
+        uint32_t npoly = 0, vtot = 0, svtot = 0;
+        auto sweep = [&](const int mode, uint32_t rob, uint32_t Vb, uint32_t VSb) {
+            Expand<NW> x = x0;
+            int steps = 0;
+            for (npoly = vtot = svtot = 0; x.q < q1; ++steps) {
                 const int32_t r0 = x.q;
-                L = x.step(sm, buf, p, ps, pe);
-                reload(L);
-                uint32_t stot;
-                excl_scan4(sm, buf, poly, ri, stot);
-                vertex_counts(rob);
-                uint32_t a, b;
-                excl_scan4(sm, buf, vo_, ex, a);
-                excl_scan4(sm, buf, vs, src, b);
-                store_rings(r0, L, Vb, VSb);
-                Vb = add_sat(Vb, a);
-                VSb = add_sat(VSb, b);
+                rank(x);
+                npoly = add_sat(npoly, stot);
+                if (mode == kSweepRank) continue;
+                counts(rob);
+                if (mode == kSweepStore) store(r0, Vb, VSb);
+                vtot = add_sat(vtot, tv);
+                svtot = add_sat(svtot, ts);
+                Vb = add_sat(Vb, tv);
+                VSb = add_sat(VSb, ts);
                 rob = add_sat(rob, stot);
             }
+            return steps;
+        };
+        const bool one_step = sweep(kSweepRank, 0, 0, 0) == 1;
+        const uint32_t ro_base = chain(sc->rec[2], npoly);
+        if (one_step) {
+            counts(ro_base);
+            vtot = tv, svtot = ts;
+        } else {
+            sweep(kSweepTotals, ro_base, 0, 0);
         }
+        uint32_t own2[2] = {vtot, svtot}, pre2[2];
+        split_gather<2>(sm, sc->rec[2] + 1, g0, j, own2, pre2, epoch);
+        const uint32_t V0 = pre2[0], VS0 = pre2[1], V1 = add_sat(V0, vtot), VS1 = add_sat(VS0, svtot);
+        const bool any_cnt = __syncthreads_or(bad_cnt);
+        if (any_cnt || V1 > col.ccap || VS1 > (uint32_t)col.n_src) {
+            if (l == 0) split_fail(st, 3, j, COVT_ERR_COUNT_MISMATCH);
+            return;
+        }
+        if (one_step) store(q0, V0, VS0);
+        else sweep(kSweepStore, ro_base, V0, VS0);
         if (q1 == (int32_t)R && l == 0) {  // the last chunk: the column's coordinate counts
-            ring_off[R] = (int32_t)V1;
+            col.ring_off[R] = (int32_t)V1;
             st.V = V1;
             st.VS = VS1;
         }
@@ -1275,25 +1148,21 @@ __device__ void split_chunk(const uint8_t* __restrict__ dec, const covt_stream_r
                 if (V == VS) {  // straight gather: coordinate v is source vertex v
                     const int32_t i0 = q0 + 4 * l;
                     int32_t idx[4];
-                    if (ice && i0 + 4 <= q1) {
-                        const i32x4 w = *(const g_i32x4*)(vo + i0);
+                    if (col.ice && i0 + 4 <= q1) {  // vertexOffsets are 16-byte aligned, i0 % 4 == 0
+                        const i32x4 w = *(const g_i32x4*)(col.vo + i0);
                         idx[0] = w.x; idx[1] = w.y; idx[2] = w.z; idx[3] = w.w;
                     } else {
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) idx[q] = i0 + q < q1 ? (ice ? ((const g_i32*)vo)[i0 + q] : i0 + q) : 0;
+                        for (int q = 0; q < 4; ++q)
+                            idx[q] = i0 + q < q1 ? (col.ice ? ((const g_i32*)col.vo)[i0 + q] : i0 + q) : 0;
                     }
                     uint64_t xy[4];
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const bool valid = i0 + q < q1;
-                        const bool inr = (uint32_t)idx[q] < (uint32_t)n_vb;
-                        bad_idx |= valid && !inr;
-                        xy[q] = (valid && inr) ? ((const g_u64*)vb)[idx[q]] : 0ull;
-                    }
-                    store4_xy<NW>(coords, q0, q1 - q0, xy);
+                    for (int q = 0; q < 4; ++q) xy[q] = col.gather(idx[q], i0 + q < q1, bad_idx);
+                    store4_xy(col.coords, q0, q1 - q0, xy);
                 } else {
                     const int2 b0 = sc->base[3][sc->pre[3][k] + j];
-                    Expand<NW> x{ring_off, (int32_t)R, q1, b0.x, b0.y, q0};
+                    Expand<NW> x{col.ring_off, (int32_t)R, q1, b0.x, b0.y, q0};
                     while (x.q < q1) {
                         const int32_t v0 = x.q;
                         int32_t r[4], rs[4], re[4];
@@ -1301,17 +1170,11 @@ __device__ void split_chunk(const uint8_t* __restrict__ dec, const covt_stream_r
                         uint64_t xy[4];
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
-                            const int32_t v = v0 + 4 * l + q;
                             const bool valid = 4 * l + q < L;
-                            const uint32_t sr = valid ? (uint32_t)((const g_i32*)ring_scr)[r[q]] : 0u;
-                            const int32_t first = (int32_t)(sr & 0x7fffffffu);
-                            const int32_t s = ((sr >> 31) && v == re[q] - 1) ? first : first + (v - rs[q]);
-                            const int32_t idx = valid ? (ice ? ((const g_i32*)vo)[s] : s) : 0;
-                            const bool inr = (uint32_t)idx < (uint32_t)n_vb;
-                            bad_idx |= valid && !inr;
-                            xy[q] = (valid && inr) ? ((const g_u64*)vb)[idx] : 0ull;
+                            const uint32_t sr = valid ? (uint32_t)((const g_i32*)col.ring_scr)[r[q]] : 0u;
+                            xy[q] = col.gather(col.coord_index(sr, v0 + 4 * l + q, rs[q], re[q], valid), valid, bad_idx);
                         }
-                        store4_xy<NW>(coords, v0, L, xy);
+                        store4_xy(col.coords, v0, L, xy);
                     }
                 }
             }
@@ -1374,7 +1237,7 @@ __global__ __launch_bounds__(64 * kCoopWaves) void split_pass_kernel(const uint8
                 const int32_t c = uni(sc->small[si]);
                 const covt_geom_desc d = descs[c];
                 covt_geom_result r{COVT_OK, 0, 0, 0};
-                assemble_column<1>(dec, dres, d, outb, r, smem.wave[w]);
+                assemble_column<kAsmIpl>(dec, dres, d, outb, r, smem.wave[w]);
                 if (lane_id() == 0) gres[c] = r;
             }
             __syncthreads();

@@ -33,11 +33,6 @@ struct Coop {
     static constexpr int K = IPL * 64 * NW;
     __device__ __forceinline__ static int tid() { return NW == 1 ? lane_id() : (int)threadIdx.x; }
     __device__ __forceinline__ static int wid() { return NW == 1 ? 0 : (int)(threadIdx.x >> 6); }
-    __device__ __forceinline__ static void sync() {
-        if (NW == 1) wave_sync();
-        else __syncthreads();
-    }
-    __device__ __forceinline__ static bool any(bool p) { return NW == 1 ? __ballot(p) != 0ull : __syncthreads_or(p) != 0; }
     // exclusive prefix of a per-thread value over the group (wave inclusive `inc` given, saturating),
     // group total.  Sums saturate at 0xffffffff: every count is checked against a capacity below 2^31, so
     // a saturated total fails the check, where a wrapped one could pass it (a 4096-item cooperative step

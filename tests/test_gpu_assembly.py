@@ -109,8 +109,8 @@ def _check_vs_oracle(oracle, cols, asm, gres, lay):
                 assert np.array_equal(g[k], o[k]), (ci, k)
 
 
-@pytest.mark.parametrize("seed", [1, 2, 3])
-def test_synthetic_columns(covt, oracle, gpu_available, seed):
+def _synthetic_set(seed):
+    """51 seeded columns: every type mix, ICE and plain, closed and open, sizes around the step sizes."""
     rng = np.random.default_rng(seed)
     cols = []
     for i in range(48):
@@ -121,6 +121,12 @@ def test_synthetic_columns(covt, oracle, gpu_available, seed):
     cols.append(A.synth_column(rng, 3000, False, False, probs=[1, 0, 0, 0, 0, 0]))
     cols.append(A.synth_column(rng, 3000, True, False, probs=[0, 0, 0, 1, 0, 0]))
     cols.append(A.synth_column(rng, 6, False, False, big=True, probs=[0, 0, 0, 0, 0, 1]))
+    return cols
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3])
+def test_synthetic_columns(covt, oracle, gpu_available, seed):
+    cols = _synthetic_set(seed)
     assert all(max(A.caps(c)) <= covt.GEOM_MAX_CAP for c in cols)
     asm, gres, lay = _run_kernel(covt, cols)
     assert (gres["status"] == 0).all()
@@ -155,7 +161,8 @@ def test_assembly_errors(covt, oracle, gpu_available):
 
 def test_assembly_errors_cooperative(covt, oracle, gpu_available):
     """The same error checks on columns big enough (>= 8192 items, batches of <= 4096 columns) for the
-    workgroup-cooperative path (assemble_coop_kernel): the first failing check's status, as the oracle."""
+    split passes (split_pass_kernel, several 16-wave workgroups per column): the first failing check's
+    status, as the oracle."""
     rng = np.random.default_rng(8)
     base = A.synth_column(rng, 9000, True, False)
     bad_type = dict(base, types=base["types"].copy())
@@ -209,6 +216,62 @@ def test_split_columns_multi_chunk(covt, oracle, gpu_available):
     assert int(gres["status"][-1]) == covt.ERR_COUNT_MISMATCH
     _check_vs_oracle(oracle, cols, asm, gres, lay)
     assert int(gres["num_coords"][0]) > 8 * 4096  # several chunks in every pass
+
+
+def _sparse_polygon_column():
+    """60,000 POLYGON features, plain, open rings: most polygons have no ring and most rings no vertex,
+    with a dense run of each in the middle, so some 4,096-item chunk of passes 3 and 4 holds more segment
+    ends than one expansion step loads."""
+    rng = np.random.default_rng(12)
+    n = 60000
+    po = np.where(rng.random(n) < 0.9, 0, rng.integers(1, 4, n)).astype(np.int32)
+    po[30000:33000] = 3
+    nr = int(po.sum())
+    ro = np.where(rng.random(nr) < 0.85, 0, rng.integers(3, 10, nr)).astype(np.int32)
+    ro[nr // 2:nr // 2 + 3000] = 5
+    vb = rng.integers(-(1 << 20), 1 << 20, size=2 * int(ro.sum()), dtype=np.int64).astype(np.int32)
+    return {"types": np.full(n, 2, np.uint8), "go": np.zeros(0, np.int32), "po": po, "ro": ro, "vo": None,
+            "vb": vb, "closed": False}
+
+
+def _max_ends_per_chunk(off, chunk=4096):
+    """Over the chunks [b * chunk, (b + 1) * chunk) of the items that `off` (segment offsets, off[0] = 0)
+    counts, the largest number of segment ends off[1:] that fall inside one chunk."""
+    ends = np.asarray(off[1:], dtype=np.int64)
+    return int(np.bincount(ends // chunk).max())
+
+
+def test_split_chunks_multi_step_passes_3_and_4(covt, oracle, gpu_available):
+    """Chunks of passes 3 and 4 whose expansion takes several steps (more than 4,096 part ends / ring ends
+    inside one 4,096-item chunk), pinned by construction: the split passes' sweeps of pass 3 in all three
+    modes, and pass 4's expansion path (open rings: closing vertices are inserted, so coordinate v is
+    not source vertex v)."""
+    col = _sparse_polygon_column()
+    col["caps"] = A.caps(col)
+    assert max(col["caps"]) <= covt.GEOM_MAX_CAP
+    o = oracle.assemble_geometry(col["types"], col["go"], col["po"], col["ro"], col["vo"], col["vb"],
+                                 col["closed"], col["caps"])
+    assert o[0] == 0
+    part_off, ring_off = o[2], o[3]
+    assert _max_ends_per_chunk(part_off) > 4096  # pass 3: part ends inside one chunk of rings
+    assert _max_ends_per_chunk(ring_off) > 4096  # pass 4: ring ends inside one chunk of coordinates
+    asm, gres, lay = _run_kernel(covt, [col])
+    assert int(gres["status"][0]) == 0
+    assert int(gres["num_coords"][0]) > int(col["ro"].sum())  # closing vertices: pass 4 expands
+    _check_vs_oracle(oracle, [col], asm, gres, lay)
+
+
+def test_synthetic_columns_single_wave_batch(covt, oracle, gpu_available):
+    """The seed-1 synthetic set in a batch of more than 4,096 columns, where every column runs on one wave
+    of assemble_kernel (test_synthetic_columns' batches are small: split passes and their small-column
+    waves): the set against the oracle, one-feature pad columns up to 4,097 accepted."""
+    cols = _synthetic_set(1)
+    n_set = len(cols)
+    pad = A.synth_column(np.random.default_rng(9), 1, False, False)
+    cols += [pad] * (4097 - n_set)
+    asm, gres, lay = _run_kernel(covt, cols)
+    assert (gres["status"] == 0).all()
+    _check_vs_oracle(oracle, cols[:n_set], asm, gres, lay)
 
 
 def _overflow_column(n_multi, parts_each, n_vertices):
