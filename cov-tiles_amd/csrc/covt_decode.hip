@@ -635,6 +635,39 @@ __device__ __forceinline__ void win_value(const WaveSmem& sm, int32_t sj, int32_
 #ifndef COVT_VARINT_LINES
 #define COVT_VARINT_LINES 1
 #endif
+// A VariableByte value without a terminator in a whole window: its continuation bytes go on adding (c & 127) <<
+// (7 k & 31), k counted from its first byte, until a byte with bit 7 set.  Reads the words at sb from logical byte
+// `pos` on (MODE_WORDREV); returns the position after the terminator, or -1 if the region ends first (a trailing
+// partial value).  Malformed streams only: one uniform word at a time through the scalar cache, so the path
+// costs the kernels around it no vector registers.
+__device__ inline int32_t vb_long_value(const uint8_t* sb, int32_t pos, int32_t end, uint32_t& value) {
+    uint32_t sum = 0;
+    for (int32_t j = pos & ~3; j < end; j += 4) {
+        const uint32_t wd = sld_be32(sb + j);  // logical bytes j .. j + 3, the first in bits 0-7
+        for (int k = 0; k < 4; ++k) {
+            if (j + k < pos) continue;
+            const uint32_t c = (wd >> (8 * k)) & 0xffu;
+            sum += (c & 0x7fu) << ((7 * (j + k - pos)) & 31);
+            if (c & 0x80u) {
+                value = sum;
+                return j + k + 1;
+            }
+        }
+    }
+    return -1;
+}
+// A 64-bit value without a terminator in a whole window is longer than its 10 bytes.  readVulong reads on to
+// the terminator, so the value is over-long (BAD_HEADER) if one comes before `end` and cut off (TRUNCATED) if
+// the stream ends first.  `from`: the window's end, 16-byte aligned to the absolute address.  Error path only.
+__device__ inline int32_t overlong_status(const uint8_t* sb, int32_t from, int32_t end) {
+    for (int32_t q = from; q < end; q += kWin) {
+        const int32_t q0 = q + 16 * lane_id();
+        uint32_t T = 0;
+        if (q0 < end) T = ~hibits16(ld128((uintptr_t)(sb + q0))) & range16(0, end - q0);
+        if (__any(T != 0)) return COVT_ERR_BAD_HEADER;
+    }
+    return COVT_ERR_TRUNCATED;
+}
 template <int MODE, int VAL, int K = 1, class Emit>
 __device__ int32_t varint_take(WaveSmem& sm, const uint8_t* sb, Win& w, int32_t& pos, int32_t end, int32_t want,
                                bool until_end, int32_t& err, Emit&& emit, int32_t out0 = 0,
@@ -657,8 +690,22 @@ __device__ int32_t varint_take(WaveSmem& sm, const uint8_t* sb, Win& w, int32_t&
                 win_load<MODE, VAL>(sm, sb, w, pos, end);
                 continue;
             }
-            if (until_end) break;  // VariableByte: trailing partial value is dropped
-            err = (w.woff + kWin >= end) ? COVT_ERR_TRUNCATED : COVT_ERR_BAD_HEADER;
+            if (until_end) {
+                if constexpr (VAL == VAL_VB) {
+                    uint32_t lo[K] = {0u}, hi[K] = {0u};
+                    const int32_t next = w.woff + kWin < end ? vb_long_value(sb, pos, end, lo[0]) : -1;
+                    if (next >= 0) {  // one value longer than the window
+                        if (got >= want) { err = COVT_ERR_COUNT_MISMATCH; break; }
+                        emit(lo, hi, got, 0, 1);
+                        got += 1;
+                        pos = next;
+                        continue;
+                    }
+                }
+                break;  // VariableByte: trailing partial value is dropped
+            }
+            // (Java's values end within 4 bytes: no terminator in a window is the stream's end)
+            err = (VAL == VAL_J4 || w.woff + kWin >= end) ? COVT_ERR_TRUNCATED : overlong_status(sb, w.woff + kWin, end);
             break;
         }
         int32_t take = have;
@@ -823,6 +870,14 @@ __device__ __forceinline__ void run_varint_stream(Ctx& c) {
             // Java decodes the x,y pair and then overruns values[] (ArrayIndexOutOfBounds)
             varint_take<MODE_RAW, VAL_J4, 4>(*c.sm, c.sb, w, pos, c.avail, c.n - 1, false, c.err, sink4, 0, nullptr,
                                              kLine);
+            // ... after it has read the pair: a stream that ends inside it fails there (DecodingUtils.java:99-105)
+            int32_t q = pos;
+            for (int v = 0; v < 2 && !c.err; ++v)
+                for (int b = 0; b < 4; ++b) {
+                    if (q >= c.avail) { c.err = COVT_ERR_TRUNCATED; break; }
+                    const uint32_t x = uniu(ld_le32(c.sb + q++));
+                    if ((x & 0x80u) == 0) break;
+                }
             if (!c.err) c.err = COVT_ERR_COUNT_MISMATCH;
         } else {
             varint_take<MODE_RAW, VAL_J4, 4>(*c.sm, c.sb, w, pos, c.avail, c.n, false, c.err, sink4, 0, nullptr, kLine);
@@ -2590,10 +2645,10 @@ __device__ __forceinline__ void run_varint_chunk(Ctx& c, int32_t s, int32_t e, i
             cnt = bad;  // the values before the over-long one
         } else if (kU64 && pos < e) {
             // the chunk's tail without a terminator: fine if the window reached the chunk end (the value
-            // ends in a later chunk), over-long otherwise (the one-wave decode's BAD_HEADER)
+            // ends in a later chunk), else longer than a window: over-long, or cut off by the stream's end
             const int32_t aligned = (int32_t)(((uintptr_t)(c.sb + pos) & ~(uintptr_t)15) - (uintptr_t)c.sb);
-            if (aligned + kWin < e) {
-                err = COVT_ERR_BAD_HEADER;
+            if (aligned + kWin < e) {  // (to the stream's end, not the chunk's: the row of the one-wave decode)
+                err = overlong_status(c.sb, aligned + kWin, c.avail);
                 bad = cnt;
             }
         }

@@ -79,7 +79,31 @@ def _synthetic_layer(rng, L):
     for name, vals in (("big", big), ("small", small), ("mono", mono), ("f", flt), ("s", strs), ("b", bools)):
         if any(v is not None for v in vals):
             cols.append(W.property_column(name, vals))
+    # an INT_64 column whose zigzag-delta varints are the shortest encoding and whose running sum needs all 64
+    # bits: small steps around a level that jumps past 2^32 and then below zero (a generator of its own, so the
+    # columns above keep their values)
+    wide = _wide_sums(np.random.default_rng(977 + L), int(pres.sum()))
+    if wide.size >= 8:
+        col = W.property_column("wide", _spread(wide, pres))
+        assert col["streams"][0][1] == W.VARINT_DELTA_ZIG_ZAG and wide.max() > (1 << 32) and wide.min() < 0
+        cols.append(col)
     return W.layer("L%d" % L, 8192, n, cols, optimized=bool(L & 1), layer_id=L)
+
+
+def _wide_sums(rng, m):
+    """m int64 values: steps of at most 1000 with a jump of 2^33 after the first third and of -2^34 after the
+    second (as varints the values take 5 bytes where their deltas take 1 or 2, and no two steps are equal runs)."""
+    d = rng.integers(-1000, 1000, size=m)
+    if m >= 8:
+        d[m // 3] += 1 << 33
+        d[2 * m // 3] -= 1 << 34
+    return np.cumsum(d)
+
+
+def _spread(dense, pres):
+    """The dense values at the present features, None elsewhere."""
+    it = iter(int(v) for v in dense)
+    return [next(it) if p else None for p in pres]
 
 
 @pytest.mark.parametrize("mode", [0, 1], ids=["format", "java"])
@@ -95,5 +119,5 @@ def test_synthetic_gend_layers(covt, oracle, gpu_available, mode):
     # 64-bit property varints: format mode decodes them, Java's 4-byte cap does not
     ops = set(plan.streams["op"][plan.streams["column_kind"] == 2].tolist())
     if mode == 0:
-        assert {covt.OP_VARINT_ZZ_S64, covt.OP_BYTE_RLE_RAW, covt.OP_RLE_I32} <= ops
+        assert {covt.OP_VARINT_ZZ_S64, covt.OP_VARINT_ZZ_DELTA_S64, covt.OP_BYTE_RLE_RAW, covt.OP_RLE_I32} <= ops
         assert (pres["status"] == 0).all()
