@@ -1512,7 +1512,8 @@ _BUILD_SOURCES = (  # the Makefile's SRC, then its HDR, one to one
     + ("../include/covt.h", "csrc/covt_internal.h", "csrc/covt_wave.h", "csrc/covt_segscan.h", "csrc/covt_walk.h",
        "csrc/covt_props_plan.h",
        "csrc/covt_scratch.h", "csrc/covt_coop.h", "csrc/covt_wkb_plan.h", "csrc/covt_bbox_plan.h",
-       "csrc/covt_measures_plan.h", "csrc/covt_geo_plan.h", "csrc/covt_arena.h", "csrc/covt_split_plan.h"))
+       "csrc/covt_measures_plan.h", "csrc/covt_geo_plan.h", "csrc/covt_arena.h", "csrc/covt_split_plan.h",
+       "csrc/covt_container.h"))
 
 
 def source_build_id() -> str:

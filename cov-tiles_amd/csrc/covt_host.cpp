@@ -23,6 +23,7 @@
 #include "covt_internal.h"
 #include "covt_walk.h"
 #include "covt_props_plan.h"
+#include "covt_container.h"
 #include "covt_wkb_plan.h"
 #include "covt_bbox_plan.h"
 #include "covt_measures_plan.h"
@@ -30,266 +31,53 @@
 
 namespace {
 
-bool name_is(const uint8_t* t, int64_t off, int64_t len, const char* s) {
-    return (size_t)len == std::strlen(s) && std::memcmp(t + off, s, (size_t)len) == 0;
-}
-// PropRaw, the property walkers' record, and the planning rule: covt_props_plan.h (shared with the device plan)
-
-// LEB128 (metadata of Gen C is written with EncodingUtils.encodeVarints, i.e. 64-bit varints)
-bool rd_uv(const uint8_t* t, size_t len, size_t& o, uint64_t& v) {
-    v = 0;
-    for (int i = 0; i < 10; ++i) {
-        if (o >= len) return false;
-        const uint8_t b = t[o++];
-        v |= (uint64_t)(b & 0x7f) << (7 * i);
-        if (!(b & 0x80)) return true;
+// The container walk: the grammars of covt_container.h (the ones the device plan's serial walkers run) over
+// a tile in host memory, with a visitor that takes the stream records, the property records and the
+// layers' extents in one pass.  PropRaw and the planning rule: covt_props_plan.h.
+struct HostWindow {
+    using Off = int64_t;
+    const uint8_t* t;
+    int64_t len;
+    uint64_t peek8(int64_t i) const {  // (0 <= i < len; bytes past the tile read as zero)
+        uint64_t v = 0;
+        if (len - i >= 8) std::memcpy(&v, t + i, 8);  // (one load)
+        else std::memcpy(&v, t + i, (size_t)(len - i));
+        return v;
     }
-    return false;
-}
-// DecodingUtils.decodeVarint (4-byte cap) as used by the Gen D metadata reader
-bool rd_j4(const uint8_t* t, size_t len, size_t& o, int32_t& v) {
-    uint32_t r = 0;
-    for (int i = 0; i < 4; ++i) {
-        if (o >= len) return false;
-        const uint8_t b = t[o++];
-        r |= (uint32_t)(b & 0x7f) << (7 * i);
-        if (i < 3 && !(b & 0x80)) break;
-    }
-    v = (int32_t)r;
-    return true;
-}
-int genc_stream_type(const uint8_t* s, uint64_t n) {
-    static const char* kNames[] = {"present", "data", "length", "dictionary", "geometry_types",
-                                   "geometry_offsets", "part_offsets", "ring_offsets", "vertex_offsets",
-                                   "vertex_buffer"};
-    for (int i = 0; i < 10; ++i)
-        if (std::strlen(kNames[i]) == n && std::memcmp(kNames[i], s, n) == 0) return i;
-    return -1;
-}
-
-// Gen C container (all committed fixtures), SURVEY.md Appendix A.1.  Geometry streams are laid
-// out in StreamType order whatever their metadata order; other columns in metadata order.  `extents` gets
-// every layer's extent as its header states it (-1 where it does not fit int32), one entry per layer.
-int walk_genc(const uint8_t* t, size_t len, std::vector<RawStream>& out, std::vector<PropRaw>* props,
-              std::vector<int32_t>& extents) {
-    size_t o = 0;
-    uint64_t version, nlayers;
-    if (!rd_uv(t, len, o, version) || !rd_uv(t, len, o, nlayers)) return COVT_ERR_TRUNCATED;
-    if (version != 1) return COVT_ERR_BAD_HEADER;
-    struct SM { int type, enc; int64_t nv, bl, name_off, name_len, off; };
-    struct CM { int kind, dtype, ctype; int64_t name_off, name_len; std::vector<SM> s; };
-    static thread_local std::vector<CM> cols;  // reused across tiles: no allocation per column
-    for (uint64_t L = 0; L < nlayers; ++L) {
-        uint64_t nlen, extent, nfeat, ncols;
-        if (!rd_uv(t, len, o, nlen) || nlen > len - o) return COVT_ERR_TRUNCATED;  // (no wrap)
-        o += nlen;
-        if (!rd_uv(t, len, o, extent) || !rd_uv(t, len, o, nfeat) || !rd_uv(t, len, o, ncols))
-            return COVT_ERR_TRUNCATED;
-        if (ncols > 4096) return COVT_ERR_BAD_HEADER;
-        extents.push_back(extent > 0x7fffffffull ? -1 : (int32_t)extent);
-        cols.assign(ncols, CM{});
-        for (auto& c : cols) {
-            uint64_t cn, ns;
-            if (!rd_uv(t, len, o, cn) || cn > len - o || len - o - cn < 2) return COVT_ERR_TRUNCATED;
-            const uint8_t* name = t + o;
-            c.name_off = (int64_t)o;
-            c.name_len = (int64_t)cn;
-            o += cn;
-            c.dtype = t[o++];
-            c.ctype = t[o++];
-            c.kind = (cn == 2 && !std::memcmp(name, "id", 2)) ? 0
-                     : ((cn == 8 && !std::memcmp(name, "geometry", 8)) || c.dtype == 6) ? 1 : 2;
-            if (!rd_uv(t, len, o, ns)) return COVT_ERR_TRUNCATED;
-            if (ns > 256) return COVT_ERR_BAD_HEADER;
-            c.s.resize(ns);
-            for (auto& s : c.s) {
-                uint64_t sn, nv, bl;
-                if (!rd_uv(t, len, o, sn) || sn > len - o) return COVT_ERR_TRUNCATED;
-                // stream names matter for Id / Geometry columns; property streams only when planned
-                s.type = (c.kind != 2 || props) ? genc_stream_type(t + o, sn) : -1;
-                s.name_off = (int64_t)o;
-                s.name_len = (int64_t)sn;
-                o += sn;
-                if (!rd_uv(t, len, o, nv) || !rd_uv(t, len, o, bl) || o >= len) return COVT_ERR_TRUNCATED;
-                s.enc = t[o++];
-                if (nv > 0x7fffffff || bl > 0x7fffffff) return COVT_ERR_BAD_HEADER;
-                s.nv = (int64_t)nv;
-                s.bl = (int64_t)bl;
-            }
-        }
-        const int nb = nbits_of_extent(extent);
-        for (auto& c : cols) {
-            if (c.kind == 1) {
-                for (int type = ST_GEOMETRY_TYPES; type <= ST_VERTEX_BUFFER; ++type)
-                    for (auto& s : c.s)
-                        if (s.type == type) {
-                            out.push_back({(int32_t)L, 1, type, s.enc, c.ctype, (int32_t)s.nv, (int32_t)s.bl, nb,
-                                           (int64_t)o});
-                            o += s.bl;
-                        }
-                for (auto& s : c.s)
-                    if (s.type < ST_GEOMETRY_TYPES || s.type > ST_VERTEX_BUFFER) o += s.bl;
-            } else {
-                for (auto& s : c.s) {
-                    if (c.kind == 0 && s.type == ST_DATA)
-                        out.push_back({(int32_t)L, 0, ST_DATA, s.enc, c.ctype, (int32_t)s.nv, (int32_t)s.bl, nb,
-                                       (int64_t)o});
-                    s.off = (int64_t)o;
-                    o += s.bl;
-                }
-            }
-            if (o > len) return COVT_ERR_TRUNCATED;
-            if (props && c.kind == 2) {  // streams of a property column in metadata order
-                PropRaw p = prop_init((int32_t)L, (int32_t)(&c - cols.data()), (int32_t)nfeat);
-                p.name_off = c.name_off;
-                p.name_len = (int32_t)c.name_len;
-                p.type = genc_prop_type(c.dtype);
-                p.ctype = c.ctype;
-                if (p.type == COVT_PROP_STRING && c.ctype == 2) {
-                    // LOCALIZED_DICTIONARY: (present_<lang>, <lang>)*, then the shared length + dictionary
-                    const SM *ls = nullptr, *ds = nullptr;
-                    for (const SM& s : c.s) {
-                        if (name_is(t, s.name_off, s.name_len, "length")) ls = &s;
-                        else if (name_is(t, s.name_off, s.name_len, "dictionary")) ds = &s;
-                    }
-                    int32_t lang = 0;
-                    for (const SM& s : c.s) {
-                        if (s.name_len <= 8 || std::memcmp(t + s.name_off, "present_", 8)) continue;
-                        const int64_t ll = s.name_len - 8;
-                        const SM* d = nullptr;
-                        for (const SM& k : c.s)
-                            if (k.name_len == ll && !std::memcmp(t + k.name_off, t + s.name_off + 8, (size_t)ll)) d = &k;
-                        PropRaw q = p;
-                        q.lang = lang++;
-                        q.lang_off = s.name_off + 8;
-                        q.lang_len = (int32_t)ll;
-                        prop_stream(q, 0, s.off, (int32_t)s.nv, (int32_t)s.bl, s.enc);
-                        if (d) prop_stream(q, 1, d->off, (int32_t)d->nv, (int32_t)d->bl, d->enc);
-                        if (ls) prop_stream(q, 2, ls->off, (int32_t)ls->nv, (int32_t)ls->bl, ls->enc);
-                        if (ds) prop_stream(q, 3, ds->off, (int32_t)ds->nv, (int32_t)ds->bl, ds->enc);
-                        props->push_back(q);
-                    }
-                } else {
-                    static const char* kRoles[4] = {"present", "data", "length", "dictionary"};
-                    for (const SM& s : c.s)
-                        for (int r = 0; r < 4; ++r)
-                            if (name_is(t, s.name_off, s.name_len, kRoles[r]))
-                                prop_stream(p, r, s.off, (int32_t)s.nv, (int32_t)s.bl, s.enc);
-                    props->push_back(p);
-                }
-            }
-        }
-    }
-    return o == len ? COVT_OK : COVT_ERR_BAD_HEADER;
-}
-
-// Bytes an ORC byte-RLE stream of n values starting at tile offset o occupies (control bytes walked,
-// values skipped); -1 if it runs past the tile.
-int32_t byte_rle_length(const uint8_t* t, size_t len, size_t o, int32_t n) {
-    size_t q = o;
-    int64_t done = 0;
-    while (done < n) {
-        if (q >= len) return -1;
-        const uint32_t c = t[q++];
-        if (c < 0x80u) { done += c + 3; q += 1; }
-        else { done += 0x100 - c; q += 0x100 - c; }
-        if (q > len) return -1;
-    }
-    return (int32_t)(q - o);
-}
-
-// Gen D container: CovtParser.decodeLayerMetadata (CovtParser.java:574-652) + the column loop
-// of decodeCovt (:56-85).  Streams of a column follow TreeMap<StreamType> order.
-int walk_gend(const uint8_t* t, size_t len, std::vector<RawStream>& out, std::vector<PropRaw>* props,
-              std::vector<int32_t>& extents) {
-    size_t o = 0;
-    int32_t layer = 0;
-    struct SM { int enc; int32_t nv, bl; bool have; };
-    struct CM { int kind, dtype, ctype; int64_t name_off; int32_t name_len; SM s[12]; };
-    std::vector<CM> cols;
-    while (o < len) {
-        const int hdr = t[o++];
-        const bool optimized = hdr & 1;
-        int32_t v, extent, nfeat, ncols;
-        if (!rd_j4(t, len, o, v)) return COVT_ERR_TRUNCATED;
-        if (!optimized) {  // decodeString: varint length + UTF-8 bytes
-            if (v < 0 || o + (size_t)v > len) return COVT_ERR_TRUNCATED;
-            o += (size_t)v;
-        }
-        if (!rd_j4(t, len, o, extent) || !rd_j4(t, len, o, nfeat) || !rd_j4(t, len, o, ncols))
-            return COVT_ERR_TRUNCATED;
-        if (ncols < 0 || ncols > 4096) return COVT_ERR_BAD_HEADER;
+};
+template <bool kP>
+struct HostVisitor {
+    static constexpr bool kStreams = true, kProps = kP;
+    std::vector<RawStream>& out;
+    std::vector<PropRaw>* props;
+    std::vector<int32_t>& extents;  // every layer's extent as its header states it (-1 where it does not fit int32)
+    size_t s0 = 0, p0 = 0;
+    void layer_begin(int32_t extent, int32_t) {
         extents.push_back(extent);
-        cols.assign((size_t)ncols, CM{});
-        for (int32_t ci = 0; ci < ncols; ++ci) {
-            CM& c = cols[(size_t)ci];
-            c.name_off = -1;
-            c.name_len = 0;
-            if (optimized || ci == 0) {
-                int32_t cid;
-                if (!rd_j4(t, len, o, cid)) return COVT_ERR_TRUNCATED;
-                c.kind = cid == 0 ? 0 : (cid == 1 ? 1 : 2);
-            } else {
-                int32_t sl;
-                if (!rd_j4(t, len, o, sl) || sl < 0 || o + (size_t)sl > len) return COVT_ERR_TRUNCATED;
-                c.kind = (sl == 2 && !std::memcmp(t + o, "id", 2)) ? 0
-                         : (sl == 8 && !std::memcmp(t + o, "geometry", 8)) ? 1 : 2;
-                c.name_off = (int64_t)o;
-                c.name_len = sl;
-                o += (size_t)sl;
-            }
-            if (o >= len) return COVT_ERR_TRUNCATED;
-            const int desc = t[o++];
-            c.dtype = (desc >> 3) & 0xF;
-            c.ctype = desc & 0x7;
-            if (c.ctype > 4) return COVT_ERR_BAD_HEADER;
-            for (;;) {
-                if (o >= len) return COVT_ERR_TRUNCATED;
-                const int sd = t[o++];
-                const int type = sd >> 4, enc = sd & 0xF;
-                if (type > ST_M || enc > 9) return COVT_ERR_BAD_HEADER;
-                int32_t nv, bl;
-                if (!rd_j4(t, len, o, nv) || !rd_j4(t, len, o, bl)) return COVT_ERR_TRUNCATED;
-                c.s[type] = SM{enc, nv, bl, true};
-                if (c.dtype == 8 && type == ST_VERTEX_BUFFER) break;
-                if (type == ST_DATA && c.ctype == CT_PLAIN) break;
-                if (type == ST_DICTIONARY) break;
-            }
-        }
-        const int nb = nbits_of_extent((uint32_t)extent);
-        for (auto& c : cols) {
-            PropRaw p = prop_init(layer, (int32_t)(&c - cols.data()), nfeat);
-            if (c.kind == 2 && c.dtype != 0) {
-                // implicit present stream: its bytes lead the column without metadata
-                // (CovtConverter.addNamedColumnMetadata skips PRESENT, :452-458; CovtParser.java:296 reads
-                // ceil(numFeatures/8) bytes with the 3-argument decodeByteRle); BOOLEAN (0) has none
-                const int32_t pl = byte_rle_length(t, len, o, nfeat < 0 ? 0 : (int32_t)(((int64_t)nfeat + 7) / 8));
-                if (pl < 0) return COVT_ERR_TRUNCATED;
-                prop_stream(p, 0, (int64_t)o, nfeat, pl, 7);
-                o += (size_t)pl;
-            }
-            for (int type = 0; type < 12; ++type) {
-                const SM& s = c.s[type];
-                if (!s.have || (c.kind == 2 && type == ST_PRESENT)) continue;
-                const bool hot = (c.kind == 0 && type == ST_DATA) ||
-                                 (c.kind == 1 && type >= ST_GEOMETRY_TYPES && type <= ST_VERTEX_BUFFER);
-                if (hot) out.push_back({layer, c.kind, type, s.enc, c.ctype, s.nv, s.bl, nb, (int64_t)o});
-                if (s.bl < 0) return COVT_ERR_BAD_HEADER;
-                if (type > ST_PRESENT && type <= ST_DICTIONARY) prop_stream(p, type, (int64_t)o, s.nv, s.bl, s.enc);
-                o += (size_t)s.bl;
-            }
-            if (o > len) return COVT_ERR_TRUNCATED;
-            if (props && c.kind == 2) {  // TreeMap<StreamType> order: present, data, length, dictionary
-                p.name_off = c.name_off;
-                p.name_len = c.name_len;
-                p.type = gend_prop_type(c.dtype);
-                p.ctype = c.ctype;
-                props->push_back(p);
-            }
-        }
-        ++layer;
+        s0 = out.size();
+        p0 = kP ? props->size() : 0;
     }
-    return COVT_OK;
+    void operator()(const RawStream& s) { out.push_back(s); }
+    void operator()(const PropRaw& p) { props->push_back(p); }
+    void layer_end(int64_t data_start) {  // Gen C: the layer's data offsets were relative to its data start
+        if (!data_start) return;
+        for (size_t i = s0; i < out.size(); ++i) out[i].off += data_start;
+        if (kP)
+            for (size_t i = p0; i < props->size(); ++i)
+                for (int r = 0; r < 4; ++r)
+                    if ((*props)[i].s_off[r] >= 0) (*props)[i].s_off[r] += data_start;
+    }
+};
+template <bool kP>
+int walk_tile(const uint8_t* t, size_t len, int32_t format, std::vector<RawStream>& out, std::vector<PropRaw>* props,
+              std::vector<int32_t>& extents) {
+    ContainerRd<HostWindow> r;
+    r.t = t;
+    r.len = (int64_t)len;
+    HostVisitor<kP> v{out, props, extents};
+    if (format != COVT_FORMAT_GENC) return walk_gend(r, v);
+    ArrayTab tab;
+    return walk_genc(r, v, tab);
 }
 
 inline int64_t align16(int64_t x) { return (x + 15) & ~(int64_t)15; }
@@ -1407,8 +1195,8 @@ int covt_plan_create_opts(const uint8_t* bytes, const uint64_t* tile_offsets, co
             const uint8_t* tile = bytes + tile_offsets[t];
             const size_t r0 = c->rs.size(), q0 = c->props.size(), e0 = c->ext.size();
             std::vector<PropRaw>* pp = (flags & COVT_PLAN_PROPERTIES) ? &c->props : nullptr;
-            const int st = format == COVT_FORMAT_GENC ? walk_genc(tile, (size_t)tile_sizes[t], c->rs, pp, c->ext)
-                                                      : walk_gend(tile, (size_t)tile_sizes[t], c->rs, pp, c->ext);
+            const int st = pp ? walk_tile<true>(tile, (size_t)tile_sizes[t], format, c->rs, pp, c->ext)
+                              : walk_tile<false>(tile, (size_t)tile_sizes[t], format, c->rs, pp, c->ext);
             p->tile_status[(size_t)t] = st;
             if (st) {  // a failed tile contributes nothing
                 c->rs.resize(r0);

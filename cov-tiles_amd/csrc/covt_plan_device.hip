@@ -4,8 +4,10 @@
 // The host plan (covt_plan_create, covt_host.cpp) walks each tile's container metadata on host
 // threads -- the host half of CovtParser.decodeCovt (CovtParser.java:53-133) and decodeLayerMetadata
 // (:574-652) -- and turns every Id / Geometry stream into a descriptor.  This file does the same walk
-// with one wave per tile, so a caller whose tiles are already in HBM gets a decodable descriptor table
-// without a round trip through the host:
+// with one wave per tile (the serial walkers instantiate the grammars the host walk instantiates,
+// covt_container.h; the speculative Gen C walk below is an algorithm of its own that falls back to them),
+// so a caller whose tiles are already in HBM gets a decodable descriptor table without a round trip
+// through the host:
 //   1. walk_count   one wave per tile: the container walk, counting the tile's streams and output bytes
 //                   and leaving up to 128 stream records per tile in slots
 //   2. prefix sums  (hipcub) of the per-tile counts and output bytes -> each tile's first stream and
@@ -29,12 +31,14 @@
 #include <cstring>
 #include <algorithm>
 #include <mutex>
+#include <type_traits>
 
 #include "covt.h"
 #include "covt_internal.h"
 #include "covt_arena.h"
 #include "covt_walk.h"
 #include "covt_props_plan.h"
+#include "covt_container.h"
 #include "covt_wkb_plan.h"
 #include "covt_bbox_plan.h"
 #include "covt_measures_plan.h"
@@ -109,18 +113,6 @@ hipError_t plan_malloc(void** q, size_t n, int dev, hipStream_t s) {
 enum { T_STREAMS = 0, T_OUT = 1, T_IN = 2, T_PAYLOAD = 3, T_VERTS = 4, T_LANE = 5, T_FAM = 8,
        T_RCH = 8 + COVT_NUM_FAMILIES, T_N = T_RCH + 1 };
 
-// One tile's bytes, read through a 64-byte window held in registers: four 16-byte loads issued
-// together (one memory latency per 64 bytes of the front-to-back metadata walk instead of four).
-// Only granules overlapping the tile are loaded (each lies inside the allocation holding the tile);
-// every byte the walk uses is inside [0, len).
-// compile-time packing of a name literal (bytes [from, from + 8) of its first len bytes)
-__host__ __device__ constexpr uint64_t cstrlen(const char* s) { return *s ? 1 + cstrlen(s + 1) : 0; }
-__host__ __device__ constexpr uint64_t pk(const char* s, uint64_t from, uint64_t len) {
-    uint64_t v = 0;
-    for (uint64_t i = from; i < from + 8 && i < len; ++i) v |= (uint64_t)(uint8_t)s[i] << (8 * (i - from));
-    return v;
-}
-
 // the walking lanes' 64-byte windows (dynamic LDS: 64 bytes per lane of the workgroup)
 extern __shared__ uint4 covt_walk_win[];
 
@@ -158,17 +150,19 @@ __device__ __forceinline__ uint64_t win_bytes8(const uint32_t* w, uint32_t off) 
     return ((uint64_t)__builtin_amdgcn_alignbyte(d2, d1, s) << 32) | __builtin_amdgcn_alignbyte(d1, d0, s);
 }
 
+// One tile's bytes for the container walks (the window of covt_container.h's ContainerRd, which adds the
+// varint / name / record arithmetic and the two grammars): a window of the tile kept in LDS (only its base
+// is carried through the walk's loops: a register window of 16 dwords cost ~1,400 64-bit moves per kernel at
+// loop edges).  Lane layout: 64 bytes per lane, refilled by that lane.  Wave layout: 512 bytes per wave,
+// refilled by 32 lanes at once (one 16-byte load each) starting 128 bytes before the byte wanted, so the
+// walk's look-backs (a column's name) stay inside the window.  Only granules overlapping the tile are
+// loaded (each lies inside the allocation holding the tile); bytes past the tile are unspecified.
 template <bool kWave>
-struct Rd {
+struct LdsWindow {
+    using Off = int32_t;  // 32-bit cursors (walk_tile: tiles under 2 GiB)
     const uint8_t* t;
-    int64_t len;   // < 2^31 (walk_tile), so tile offsets compare as 32-bit values below
+    int64_t len;
     int64_t wo;    // the window's start as a tile offset (its address is 16-byte aligned)
-    // 8 bytes at tile offset i from a window of the tile kept in LDS (only its base is carried through
-    // the walk's loops: a register window of 16 dwords cost ~1,400 64-bit moves per kernel at loop edges).
-    // Lane layout: 64 bytes per lane, refilled by that lane.  Wave layout: 512 bytes per wave, refilled by
-    // 32 lanes at once (one 16-byte load each) starting 128 bytes before the byte wanted, so the walk's
-    // look-backs (a column's name, the geometry column's type-ordered rescans) stay inside the window.
-    // Bytes past the tile are unspecified: callers mask by len.
     static constexpr uint32_t kWin = kWave ? 512 : 64;
     __device__ __forceinline__ uint64_t peek8(int32_t i) {
         const uint4* w = covt_walk_win + (kWave ? 0 : threadIdx.x * 4);
@@ -181,7 +175,6 @@ struct Rd {
         }
         return win_bytes8(reinterpret_cast<const uint32_t*>(w), off);  // (off <= kWin - 8)
     }
-    __device__ __forceinline__ int at(int32_t i) { return (int)(peek8(i) & 0xff); }
     // (wave layout) the window holds bytes [i, i + n) (n <= 384); returns i's offset in it
     __device__ __forceinline__ uint32_t ensure(int32_t i, uint32_t n) {
         uint32_t off = (uint32_t)i - (uint32_t)wo;
@@ -192,350 +185,25 @@ struct Rd {
         }
         return off;
     }
-    // low n bytes (n <= 8) of x's 7-bit groups packed (LEB128 payload)
-    __device__ __forceinline__ static uint64_t leb_pack(uint64_t x, int n) {
-        x = (n >= 8 ? x : x & ((1ull << (8 * n)) - 1)) & 0x7f7f7f7f7f7f7f7full;
-        x = (x & 0x007f007f007f007full) | ((x & 0x7f007f007f007f00ull) >> 1);
-        x = (x & 0x00003fff00003fffull) | ((x & 0x3fff00003fff0000ull) >> 2);
-        return (x & 0x000000000fffffffull) | ((x & 0x0fffffff00000000ull) >> 4);
+};
+template <bool kWave>
+using Rd = ContainerRd<LdsWindow<kWave>>;
+
+// A Gen C geometry column's streams for the type-ordered layout (the grammar's table, covt_container.h), wave
+// layout: an LDS table after the window, written as the streams are read.  The lane layout keeps none and
+// reads the column's metadata again (GeoReread).
+struct GeoLds {
+    static constexpr bool kKeepsGeo = true;
+    __device__ __forceinline__ static uint4* tab() { return covt_walk_win + Rd<true>::kWin / 16; }
+    __device__ __forceinline__ void geo_set(uint32_t s, const GeoSm& g) {
+        tab()[s] = make_uint4((uint32_t)(g.type & 0xff) | ((uint32_t)g.enc << 8), (uint32_t)g.nv, (uint32_t)g.bl, 0);
     }
-    // rd_uv (covt_host.cpp): 64-bit LEB128, at most 10 bytes; up to 8 bytes decoded from one word
-    __device__ __forceinline__ bool uv(int32_t& o, uint64_t& v) {
-        const int32_t avail = (int32_t)len - (int32_t)o;
-        if (avail <= 0) return false;
-        const uint64_t w = peek8(o);
-        {  // values of up to 4 bytes (nearly all metadata) in 32-bit arithmetic
-            const uint32_t w4 = (uint32_t)w;
-            uint32_t stop4 = ~w4 & 0x80808080u;
-            if (avail < 4) stop4 &= (1u << (8 * avail)) - 1;
-            if (stop4) {
-                const int n = (__builtin_ctz(stop4) >> 3) + 1;
-                uint32_t x = (n >= 4 ? w4 : w4 & ((1u << (8 * n)) - 1)) & 0x7f7f7f7fu;
-                x = (x & 0x007f007fu) | ((x & 0x7f007f00u) >> 1);
-                v = (x & 0x3fffu) | ((x & 0x3fff0000u) >> 2);
-                o += n;
-                return true;
-            }
-        }
-        uint64_t stop = ~w & 0x8080808080808080ull;
-        if (avail < 8) stop &= (1ull << (8 * avail)) - 1;  // only the tile's bytes
-        if (stop) {
-            const int n = (__builtin_ctzll(stop) >> 3) + 1;
-            v = leb_pack(w, n);
-            o += n;
-            return true;
-        }
-        if (avail < 8) return false;  // no terminator before the tile's end
-        v = leb_pack(w, 8);           // 9- or 10-byte value
-        int32_t q = o + 8;
-#pragma unroll 1
-        for (int i = 8; i < 10; ++i) {
-            if (q >= len) return false;
-            const int b = at(q++);
-            v |= (uint64_t)(b & 0x7f) << (7 * i);
-            if (!(b & 0x80)) {
-                o = q;
-                return true;
-            }
-        }
-        return false;
-    }
-    // LEB128 payload of the low n (<= 4) bytes of x
-    __device__ __forceinline__ static uint32_t leb_pack4(uint32_t x, int n) {
-        x = (n >= 4 ? x : x & ((1u << (8 * n)) - 1)) & 0x7f7f7f7fu;
-        x = (x & 0x007f007fu) | ((x & 0x7f007f00u) >> 1);
-        return (x & 0x3fffu) | ((x & 0x3fff0000u) >> 2);
-    }
-    // Gen C stream record tail (numValues, byteLength varints and the encoding byte) from one 64-bit word
-    // when both varints have at most 4 bytes and all of it lies in the tile; false (nothing consumed)
-    // otherwise, and the caller reads the fields one by one (same values and statuses)
-    __device__ __forceinline__ bool rec3(int32_t& o, uint64_t& nv, uint64_t& bl, int& enc) {
-        const int32_t avail = (int32_t)len - o;
-        if (avail < 3) return false;
-        const uint64_t w = peek8(o);
-        uint64_t stop = ~w & 0x8080808080808080ull;
-        if (avail < 8) stop &= (1ull << (8 * avail)) - 1;
-        if (!stop) return false;
-        const int e1 = __builtin_ctzll(stop) >> 3;  // numValues' last byte
-        if (e1 > 3) return false;
-        const uint64_t stop2 = stop & (~0ull << (8 * (e1 + 1)));
-        if (!stop2) return false;
-        const int e2 = __builtin_ctzll(stop2) >> 3;  // byteLength's last byte
-        if (e2 - e1 > 4 || e2 + 1 >= avail || e2 + 1 >= 8) return false;
-        nv = leb_pack4((uint32_t)w, e1 + 1);
-        bl = leb_pack4((uint32_t)(w >> (8 * (e1 + 1))), e2 - e1);
-        enc = (int)((w >> (8 * (e2 + 1))) & 0xff);
-        o += e2 + 2;
-        return true;
-    }
-    // rd_j4: DecodingUtils.decodeVarint with its 4-byte cap (DecodingUtils.java:157-186): a byte
-    // without bit 7 among the first three ends the value, else the fourth byte does
-    __device__ __forceinline__ bool j4(int32_t& o, int32_t& v) {
-        const int32_t avail = (int32_t)len - (int32_t)o;
-        if (avail <= 0) return false;
-        const uint32_t w4 = (uint32_t)peek8(o);
-        const uint32_t stop = ~w4 & 0x808080u;
-        const int n = stop ? (__builtin_ctz(stop) >> 3) + 1 : 4;
-        if (n > avail) return false;
-        uint32_t x = (n >= 4 ? w4 : w4 & ((1u << (8 * n)) - 1)) & 0x7f7f7f7fu;
-        x = (x & 0x007f007fu) | ((x & 0x7f007f00u) >> 1);
-        v = (int32_t)((x & 0x3fffu) | ((x & 0x3fff0000u) >> 2));
-        o += n;
-        return true;
-    }
-    // the first 16 bytes of a name at o (n <= 16) packed little-endian (register compares below)
-    __device__ __forceinline__ void pack16(int32_t o, uint64_t n, uint64_t& lo, uint64_t& hi) {
-        lo = peek8(o);
-        if (n < 8) lo &= (1ull << (8 * n)) - 1;
-        hi = 0;
-        if (n > 8) {
-            hi = peek8(o + 8);
-            if (n < 16) hi &= (1ull << (8 * (n - 8))) - 1;
-        }
-    }
-    // name at o (n bytes) == the literal (constants evaluated at compile time: a runtime walk of the
-    // literal's bytes would be a memory load per character)
-#define COVT_IS(o, n, str)                                                                             \
-    ([&]() {                                                                                           \
-        constexpr uint64_t n_ = cstrlen(str), l_ = pk(str, 0, n_), h_ = pk(str, 8, n_);                \
-        static_assert(n_ <= 16, "names up to 16 bytes");                                               \
-        if ((uint64_t)(n) != n_) return false;                                                         \
-        uint64_t lo_, hi_;                                                                             \
-        r.pack16((o), n_, lo_, hi_);                                                                   \
-        return lo_ == l_ && hi_ == h_;                                                                 \
-    }())
-    // genc_stream_type: Gen C stream name -> StreamType (-1: other)
-    __device__ __forceinline__ int stream_type(int32_t o, uint64_t n) {
-        if (n < 4 || n > 16) return -1;
-        uint64_t lo, hi;
-        pack16(o, n, lo, hi);
-#define COVT_NAME(str, v)                                                              \
-    {                                                                                  \
-        constexpr uint64_t n_ = cstrlen(str), l_ = pk(str, 0, n_), h_ = pk(str, 8, n_); \
-        if (n == n_ && lo == l_ && hi == h_) return v;                                 \
-    }
-        COVT_NAME("data", ST_DATA)
-        COVT_NAME("length", ST_LENGTH)
-        COVT_NAME("present", ST_PRESENT)
-        COVT_NAME("dictionary", ST_DICTIONARY)
-        COVT_NAME("geometry_types", ST_GEOMETRY_TYPES)
-        COVT_NAME("geometry_offsets", ST_GEOMETRY_OFFSETS)
-        COVT_NAME("part_offsets", ST_PART_OFFSETS)
-        COVT_NAME("ring_offsets", ST_RING_OFFSETS)
-        COVT_NAME("vertex_offsets", ST_VERTEX_OFFSETS)
-        COVT_NAME("vertex_buffer", ST_VERTEX_BUFFER)
-#undef COVT_NAME
-        return -1;
-    }
-    // byte_rle_length: bytes of an ORC byte-RLE stream of n values at o (-1: runs past the tile)
-    __device__ __forceinline__ int32_t byte_rle_length(int32_t o, int32_t n) {
-        int32_t q = o;
-        int64_t done = 0;
-        while (done < n) {
-            if (q >= len) return -1;
-            const int c = at(q++);
-            if (c < 0x80) done += c + 3, q += 1;
-            else done += 0x100 - c, q += 0x100 - c;
-            if (q > len) return -1;
-        }
-        return (int32_t)(q - o);
+    __device__ __forceinline__ void geo_rewind(int32_t) {}
+    __device__ __forceinline__ GeoSm geo_get(Rd<true>&, uint32_t s) const {
+        const uint4 g = tab()[s];
+        return GeoSm{(int32_t)(int8_t)(g.x & 0xff), (int32_t)(g.x >> 8), (int32_t)g.y, (int32_t)g.z};
     }
 };
-
-// Gen C container (walk_genc, covt_host.cpp) in one pass over each layer's
-// column metadata: the host walk's metadata checks in the same order (same first failing status), data
-// offsets relative to the layer's data start (known once its metadata is read: the emitter rebases the
-// layer's streams then), and the host's per-column data bound checked once at the end of the layer (the
-// data cursor only grows, so the last column's check fires iff any column's does).  Geometry streams
-// are laid out in StreamType order (a rescan of that column's few streams).
-template <bool kWave, class E>
-__device__ __forceinline__ int walk_genc_dev(Rd<kWave>& r, E& emit) {
-    const int32_t len = (int32_t)r.len;  // 32-bit cursors (walk_tile: tiles under 2 GiB)
-    int32_t o = 0;
-    uint64_t version, nlayers;
-    if (!r.uv(o, version) || !r.uv(o, nlayers)) return COVT_ERR_TRUNCATED;
-    if (version != 1) return COVT_ERR_BAD_HEADER;
-    for (uint64_t L = 0; L < nlayers; ++L) {
-        uint64_t nlen, extent, nfeat, ncols;
-        if (!r.uv(o, nlen) || nlen > (uint64_t)(len - o)) return COVT_ERR_TRUNCATED;
-        o += (int32_t)nlen;
-        if (!r.uv(o, extent) || !r.uv(o, nfeat) || !r.uv(o, ncols)) return COVT_ERR_TRUNCATED;
-        if (ncols > 4096) return COVT_ERR_BAD_HEADER;
-        const int nb = nbits_of_extent(extent);
-        int64_t d = 0;  // data bytes of the layer's columns so far
-        emit.layer_begin();
-        for (uint32_t c = 0; c < (uint32_t)ncols; ++c) {
-            uint64_t cn, ns, sn, nv, bl;
-            if (!r.uv(o, cn) || cn > (uint64_t)(len - o) || (uint64_t)(len - o) - cn < 2) return COVT_ERR_TRUNCATED;
-            const int32_t name = o;
-            o += (int32_t)cn;
-            const int dtype = r.at(o), ctype = r.at(o + 1);
-            o += 2;
-            if (!r.uv(o, ns)) return COVT_ERR_TRUNCATED;
-            if (ns > 256) return COVT_ERR_BAD_HEADER;
-            const int kind = COVT_IS(name, cn, "id") ? 0 : (COVT_IS(name, cn, "geometry") || dtype == 6) ? 1 : 2;
-            const int32_t s0 = o;
-            // wave layout: the geometry column's streams (type, encoding, sizes) go to an LDS table as
-            // they are read, and the type-ordered layout below reads the table; the lane layout
-            // re-reads the column's metadata once per type instead (each re-read parses the names)
-            uint4* geo = covt_walk_win + Rd<kWave>::kWin / 16;
-            constexpr bool kTable = kWave;
-            uint32_t present = 0;  // geometry stream types seen
-            for (uint32_t s = 0; s < (uint32_t)ns; ++s) {
-                if (!r.uv(o, sn) || sn > (uint64_t)(len - o)) return COVT_ERR_TRUNCATED;
-                const int type = kind == 0 || (kTable && kind == 1) ? r.stream_type(o, sn) : -1;
-                o += (int32_t)sn;
-                int enc;
-                if (!r.rec3(o, nv, bl, enc)) {
-                    if (!r.uv(o, nv) || !r.uv(o, bl) || o >= len) return COVT_ERR_TRUNCATED;
-                    enc = r.at(o++);
-                }
-                if (nv > 0x7fffffff || bl > 0x7fffffff) return COVT_ERR_BAD_HEADER;
-                if (kind == 0 && type == ST_DATA)
-                    emit(RawStream{(int32_t)L, 0, ST_DATA, enc, ctype, (int32_t)nv, (int32_t)bl, nb, d});
-                if (kind != 1) d += (int64_t)bl;
-                if (kTable && kind == 1) {
-                    geo[s] = make_uint4((uint32_t)(type & 0xff) | ((uint32_t)enc << 8), (uint32_t)nv, (uint32_t)bl, 0);
-                    if (type >= ST_GEOMETRY_TYPES && type <= ST_VERTEX_BUFFER) present |= 1u << type;
-                }
-            }
-            if (kind == 1 && kTable) {  // types 4..9 in type order (metadata order within a type), then the rest
-                for (int want = ST_GEOMETRY_TYPES; want <= ST_VERTEX_BUFFER; ++want) {
-                    if (!(present >> want & 1)) continue;
-                    for (uint32_t s = 0; s < (uint32_t)ns; ++s) {
-                        const uint4 g = geo[s];
-                        if ((int)(g.x & 0xff) != want) continue;
-                        emit(RawStream{(int32_t)L, 1, want, (int)(g.x >> 8), ctype, (int32_t)g.y, (int32_t)g.z, nb, d});
-                        d += (int64_t)g.z;
-                    }
-                }
-                for (uint32_t s = 0; s < (uint32_t)ns; ++s) {
-                    const uint4 g = geo[s];
-                    const int type = (int)(int8_t)(g.x & 0xff);
-                    if (type < ST_GEOMETRY_TYPES || type > ST_VERTEX_BUFFER) d += (int64_t)g.z;
-                }
-            } else if (kind == 1) {  // streams of types 4..9 in type order, then the rest (all checked above)
-                for (int want = ST_GEOMETRY_TYPES; want <= ST_VERTEX_BUFFER + 1; ++want) {
-                    int32_t q = s0;
-                    for (uint32_t s = 0; s < (uint32_t)ns; ++s) {
-                        r.uv(q, sn);
-                        const int type = r.stream_type(q, sn);
-                        q += (int32_t)sn;
-                        r.uv(q, nv);
-                        r.uv(q, bl);
-                        const int enc = r.at(q++);
-                        const bool isgeo = type >= ST_GEOMETRY_TYPES && type <= ST_VERTEX_BUFFER;
-                        if (want <= ST_VERTEX_BUFFER ? type != want : isgeo) continue;
-                        if (isgeo) emit(RawStream{(int32_t)L, 1, type, enc, ctype, (int32_t)nv, (int32_t)bl, nb, d});
-                        d += (int64_t)bl;
-                    }
-                }
-            }
-        }
-        if (d > (int64_t)(len - o)) return COVT_ERR_TRUNCATED;
-        emit.layer_end(o);  // the layer's data starts where its metadata ends
-        o += (int32_t)d;
-    }
-    return o == len ? COVT_OK : COVT_ERR_BAD_HEADER;
-}
-
-// Gen D container (walk_gend, covt_host.cpp; CovtParser.decodeLayerMetadata, CovtParser.java:574-652).
-// A column's streams follow TreeMap<StreamType> order, the last metadata entry of a type winning.
-template <bool kWave, class E>
-__device__ __forceinline__ int walk_gend_dev(Rd<kWave>& r, E& emit) {
-    const int32_t len = (int32_t)r.len;  // 32-bit cursors (walk_tile: tiles under 2 GiB)
-    int32_t o = 0;
-    int32_t layer = 0;
-    while (o < len) {
-        const bool optimized = r.at(o++) & 1;
-        int32_t v, extent, nfeat, ncols;
-        if (!r.j4(o, v)) return COVT_ERR_TRUNCATED;
-        if (!optimized) {
-            if (v < 0 || v > len - o) return COVT_ERR_TRUNCATED;
-            o += v;
-        }
-        if (!r.j4(o, extent) || !r.j4(o, nfeat) || !r.j4(o, ncols)) return COVT_ERR_TRUNCATED;
-        if (ncols < 0 || ncols > 4096) return COVT_ERR_BAD_HEADER;
-        const int32_t meta = o;
-        for (int32_t ci = 0; ci < ncols; ++ci) {  // metadata checks
-            int32_t x;
-            if (optimized || ci == 0) {
-                if (!r.j4(o, x)) return COVT_ERR_TRUNCATED;
-            } else {
-                if (!r.j4(o, x) || x < 0 || x > len - o) return COVT_ERR_TRUNCATED;
-                o += x;
-            }
-            if (o >= len) return COVT_ERR_TRUNCATED;
-            const int desc = r.at(o++), dtype = (desc >> 3) & 0xF, ctype = desc & 0x7;
-            if (ctype > 4) return COVT_ERR_BAD_HEADER;
-            for (;;) {
-                if (o >= len) return COVT_ERR_TRUNCATED;
-                const int sd = r.at(o++), type = sd >> 4, enc = sd & 0xF;
-                if (type > ST_M || enc > 9) return COVT_ERR_BAD_HEADER;
-                int32_t nv, bl;
-                if (!r.j4(o, nv) || !r.j4(o, bl)) return COVT_ERR_TRUNCATED;
-                if ((dtype == 8 && type == ST_VERTEX_BUFFER) || (type == ST_DATA && ctype == CT_PLAIN) ||
-                    type == ST_DICTIONARY)
-                    break;
-            }
-        }
-        const int nb = nbits_of_extent((uint32_t)extent);
-        int32_t m = meta;
-        int64_t d = o;  // data cursor (64-bit: a column's streams may sum past 2^31 before its bound check)
-        emit.layer_begin();
-        for (int32_t ci = 0; ci < ncols; ++ci) {
-            int32_t x, kind;
-            if (optimized || ci == 0) {
-                r.j4(m, x);
-                kind = x == 0 ? 0 : (x == 1 ? 1 : 2);
-            } else {
-                r.j4(m, x);
-                kind = COVT_IS(m, x, "id") ? 0 : COVT_IS(m, x, "geometry") ? 1 : 2;
-                m += x;
-            }
-            const int desc = r.at(m++), dtype = (desc >> 3) & 0xF, ctype = desc & 0x7;
-            const int32_t s0 = m;
-            uint32_t have = 0;  // stream types present
-            for (;;) {
-                const int sd = r.at(m++), type = sd >> 4;
-                int32_t nv, bl;
-                r.j4(m, nv);
-                r.j4(m, bl);
-                have |= 1u << type;
-                if ((dtype == 8 && type == ST_VERTEX_BUFFER) || (type == ST_DATA && ctype == CT_PLAIN) ||
-                    type == ST_DICTIONARY)
-                    break;
-            }
-            if (kind == 2 && dtype != 0) {  // implicit present stream (walk_gend)
-                const int32_t pl = r.byte_rle_length((int32_t)d, nfeat < 0 ? 0 : (int32_t)(((int64_t)nfeat + 7) / 8));
-                if (pl < 0) return COVT_ERR_TRUNCATED;
-                d += pl;
-            }
-            for (int type = 0; type < 12; ++type) {
-                if (!(have >> type & 1) || (kind == 2 && type == ST_PRESENT)) continue;
-                int enc = 0;
-                int32_t nv = 0, bl = 0;
-                for (int32_t q = s0; q < m;) {  // the last entry of this type
-                    const int sd = r.at(q++);
-                    int32_t a, b;
-                    r.j4(q, a);
-                    r.j4(q, b);
-                    if ((sd >> 4) == type) enc = sd & 0xF, nv = a, bl = b;
-                }
-                const bool hot = (kind == 0 && type == ST_DATA) ||
-                                 (kind == 1 && type >= ST_GEOMETRY_TYPES && type <= ST_VERTEX_BUFFER);
-                if (hot) emit(RawStream{layer, kind, type, enc, ctype, nv, bl, nb, d});
-                if (bl < 0) return COVT_ERR_BAD_HEADER;
-                d += bl;
-            }
-            if (d > len) return COVT_ERR_TRUNCATED;
-        }
-        emit.layer_end(0);
-        o = (int32_t)d;
-        ++layer;
-    }
-    return COVT_OK;
-}
 
 __device__ inline int64_t align16(int64_t x) { return (x + 15) & ~(int64_t)15; }
 
@@ -559,7 +227,7 @@ __device__ __forceinline__ uint32_t entry_key(int32_t op, int32_t nv, int32_t bl
 // two tables; the walk then follows the chain one LDS read per record and parses fields only for the
 // Id / Geometry streams it emits.  Anything outside the fast grammar (a name or varint longer than the
 // tables hold, a record past the tile, a check the serial walk would fail) makes the tile fall back to the
-// serial walk (walk_genc_dev), which then gives the exact statuses; a successful fast walk emits the same
+// serial walk (walk_genc, covt_container.h), which then gives the exact statuses; a successful fast walk emits the same
 // records in the same order.
 #ifndef COVT_FW_SPAN
 #define COVT_FW_SPAN 512
@@ -809,15 +477,15 @@ struct FastGenc {
     }
 };
 
-// The fast walk of one Gen C tile (walk_genc_dev's grammar and emission order); kFastFallback when the
-// tile leaves the fast grammar (the caller then runs walk_genc_dev from scratch with a fresh emitter).
+// The fast walk of one Gen C tile (walk_genc's grammar and emission order); kFastFallback when the
+// tile leaves the fast grammar (the caller then runs walk_genc from scratch with a fresh emitter).
 template <class E>
 __device__ int walk_genc_fast(FastGenc& f, E& emit) {
     const int32_t len = f.len;
     int32_t o = 0;
     uint32_t version, nlayers;
     if (!f.uv4(o, version) || !f.uv4(o, nlayers) || version != 1) return kFastFallback;
-    uint4* geo = covt_walk_win + Rd<true>::kWin / 16;  // the geometry column's streams (as walk_genc_dev)
+    uint4* geo = covt_walk_win + Rd<true>::kWin / 16;  // the geometry column's streams (GeoLds's table)
     for (uint32_t L = 0; L < nlayers; ++L) {
         uint32_t nlen, extent, nfeat, ncols;
         if (!f.uv4(o, nlen) || nlen > (uint32_t)(len - o)) return kFastFallback;
@@ -932,7 +600,9 @@ __device__ __forceinline__ int walk_tile(const uint8_t* bytes, uint64_t n_bytes,
         if (st != kFastFallback) return st;
         emit = fresh;
     }
-    return format == COVT_FORMAT_GENC ? walk_genc_dev(r, emit) : walk_gend_dev(r, emit);
+    if (format != COVT_FORMAT_GENC) return walk_gend(r, emit);
+    typename std::conditional<kWave, GeoLds, GeoReread<int32_t>>::type tab;
+    return walk_genc(r, emit, tab);
 }
 
 // the walks' tile order in a property plan: largest first (the batch's few 442 KB tiles were the property
@@ -959,7 +629,8 @@ constexpr int64_t kSpecStreamsPerTile = 32;
 // library's busiest tile has 67): a batch averaging more is redone with its counted size (a third sync)
 constexpr int64_t kSpecCapPerTile = 64;
 
-struct CountEmit {
+struct CountEmit {  // (a visitor of the container walks: the Id / Geometry stream records)
+    static constexpr bool kStreams = true, kProps = false;
     int32_t id_mode;
     RawStream* slots = nullptr;  // this tile's kSlots record slots, or null
     bool writer = true, wave = false;
@@ -1017,7 +688,7 @@ struct CountEmit {
         cost += sc;
         cmax = sm > cmax ? sm : cmax;
     }
-    __device__ void layer_begin() { k0 = n; }
+    __device__ void layer_begin(int32_t = 0, int32_t = 0) { k0 = n; }
     __device__ void layer_end(int64_t data_start) {  // rebase the layer's recorded data offsets
         if (!data_start || !slots) return;
         const int64_t e = n < kSlots ? n : kSlots;
@@ -1118,6 +789,7 @@ __global__ void __launch_bounds__(1024) plan_head(const int64_t* __restrict__ cb
 }
 
 struct InfoEmit {
+    static constexpr bool kStreams = true, kProps = false;
     int32_t tile, id_mode;
     int64_t tile_off;
     covt_stream_info* info;
@@ -1127,7 +799,7 @@ struct InfoEmit {
     uint32_t* keys = nullptr;
     int64_t cap = INT64_MAX;  // entries the arena holds (a plan sized to a bound)
     bool writer, wave;
-    __device__ void layer_begin() { k0 = k; }
+    __device__ void layer_begin(int32_t = 0, int32_t = 0) { k0 = k; }
     __device__ void layer_end(int64_t data_start) {  // rebase the layer's data offsets (this lane's own stores)
         if (!data_start) return;
         if (wave) {  // the layer's records, one lane each (lane 0 wrote them: a barrier-free wave is in order)
@@ -1777,7 +1449,7 @@ __global__ void fpf_states_walk(const uint8_t* __restrict__ bytes, const covt_st
     }
 }
 
-// ---- Property columns (COVT_PLAN_PROPERTIES; covt_host.cpp walk_genc / walk_gend's property records,
+// ---- Property columns (COVT_PLAN_PROPERTIES; the container walks' property records, covt_host.cpp's
 // plan_property and plan_property_layout).  The host plan puts a tile's property streams after its Id /
 // Geometry streams and gives them output slices in that order; here:
 //   prop_walk<false>  one wave per tile (largest tiles first): the container walk again, counting property
@@ -1791,17 +1463,24 @@ __global__ void fpf_states_walk(const uint8_t* __restrict__ bytes, const covt_st
 // and once the stream arrays exist, prop_fill writes the records' stream entries and covt_prop_info,
 // prop_layout / prop_layout_fill the property output slices, a stable radix sort the largest-first
 // materialization order and prop_desc_fill the covt_prop_desc table.
-struct PropSm {  // a property column's stream, as the Gen C walk reads it
-    uint32_t h0, h8;  // localized string columns: hashes of the name and of its bytes from 8 on (names_hash)
-    int32_t noff, nlen, nv, bl;
-    int32_t off;      // layer-data-relative
-    uint16_t enc, role;  // role: PR_* bits of the name, classified while the window holds it
-};
-enum { PR_PRESENT = 1, PR_DATA = 2, PR_LENGTH = 4, PR_DICTIONARY = 8, PR_PRESENT_LANG = 16 };
-constexpr int kPropMaxStreams = 256;  // numStreams bound of the walk (walk_genc: > 256 is BAD_HEADER)
 // LDS: Rd<true>'s window, the fast walk's window and tables (walk_count's layout)
 constexpr size_t kPropRecOffset = (kFastSmemOffset + sizeof(FastSmem) + 15) & ~(size_t)15;
 constexpr size_t kPropWalkLds = kPropRecOffset + sizeof(FastSmemRec) > kWalkLds ? kPropRecOffset + sizeof(FastSmemRec) : kWalkLds;
+
+// a hash of bytes [a, a + n) (equal bytes, equal hashes): read while the walk's window holds the name, so
+// the localized columns' name matching (PropTab::last_named) compares hashes and confirms a match with Rd::same --
+// one window refill per match instead of a refill per byte compared (two names of a long column lie
+// further apart than the window, and the all-pairs compare ping-ponged between them: ~9 ms per walk)
+__device__ __forceinline__ uint32_t names_hash(Rd<true>& r, int32_t a, int32_t n) {
+    uint64_t h = 0x9e3779b97f4a7c15ull ^ (uint64_t)(uint32_t)n;
+    for (int32_t i = 0; i < n; i += 8) {
+        const int32_t k = n - i < 8 ? n - i : 8;
+        const uint64_t m = k >= 8 ? ~0ull : ((1ull << (8 * k)) - 1);
+        h = (h ^ (r.peek8(a + i) & m)) * 0xff51afd7ed558ccdull;
+        h ^= h >> 29;
+    }
+    return (uint32_t)(h ^ (h >> 32));
+}
 
 // A property column's stream table in registers: entry s in lane s % 64, slot s / 64 (32 VGPRs).  It
 // was 7 KB of LDS per wave, which halved the walk's resident waves against the Id walk's -- and the walk
@@ -1810,6 +1489,7 @@ struct PropTab {
     uint32_t h0[4], h8[4];
     int32_t noff[4], nlen[4], nv[4], bl[4], off[4];
     uint32_t er[4];  // enc | role << 16
+    static constexpr bool kKeepsGeo = false;  // (the property walk takes no stream records)
     template <class T>
     static __device__ __forceinline__ T pick(const T (&a)[4], uint32_t j) {  // a[j], j uniform
         return j == 0 ? a[0] : j == 1 ? a[1] : j == 2 ? a[2] : a[3];
@@ -1847,124 +1527,53 @@ struct PropTab {
         v.role = (uint16_t)(e >> 16);
         return v;
     }
+    // the serial walk's set: with the name's hashes (`hashes`: a localized column, whose names are matched),
+    // taken while the window holds the name
+    __device__ __forceinline__ void set(Rd<true>& r, uint32_t s, PropSm v, bool hashes) {
+        if (hashes) {
+            if (v.role & PR_PRESENT_LANG) v.h8 = names_hash(r, v.noff + kLangPrefix, v.nlen - kLangPrefix);
+            v.h0 = names_hash(r, v.noff, v.nlen);
+        }
+        set(s, v);
+    }
     // the highest entry below ns whose role has any of `bits` (-1: none)
-    __device__ __forceinline__ int32_t last_role(uint32_t ns, uint32_t bits, uint32_t notbits) const {
+    __device__ __forceinline__ int32_t last_role(uint32_t ns, uint32_t bits) const {
         for (int32_t j = 3; j >= 0; --j) {
             const uint32_t k = 64u * (uint32_t)j + threadIdx.x;
-            const uint32_t role = pick(er, (uint32_t)j) >> 16;
-            const uint64_t b = __ballot(k < ns && (role & bits) && !(role & notbits));
+            const uint64_t b = __ballot(k < ns && ((pick(er, (uint32_t)j) >> 16) & bits));
             if (b) return 64 * j + 63 - __builtin_clzll(b);
         }
         return -1;
     }
-};
-
-// bytes [a, a + n) == bytes [b, b + n) of the tile (names; uniform)
-__device__ __forceinline__ bool names_equal(Rd<true>& r, int32_t a, int32_t b, int32_t n) {
-    for (int32_t i = 0; i < n; i += 8) {
-        const int32_t k = n - i < 8 ? n - i : 8;
-        const uint64_t m = k >= 8 ? ~0ull : ((1ull << (8 * k)) - 1);
-        if ((r.peek8(a + i) & m) != (r.peek8(b + i) & m)) return false;
-    }
-    return true;
-}
-// a hash of bytes [a, a + n) (equal bytes, equal hashes): read while the walk's window holds the name, so
-// the localized columns' name matching below compares hashes and confirms a match with names_equal --
-// one window refill per match instead of a refill per byte compared (two names of a long column lie
-// further apart than the window, and the all-pairs compare ping-ponged between them: ~9 ms per walk)
-__device__ __forceinline__ uint32_t names_hash(Rd<true>& r, int32_t a, int32_t n) {
-    uint64_t h = 0x9e3779b97f4a7c15ull ^ (uint64_t)(uint32_t)n;
-    for (int32_t i = 0; i < n; i += 8) {
-        const int32_t k = n - i < 8 ? n - i : 8;
-        const uint64_t m = k >= 8 ? ~0ull : ((1ull << (8 * k)) - 1);
-        h = (h ^ (r.peek8(a + i) & m)) * 0xff51afd7ed558ccdull;
-        h ^= h >> 29;
-    }
-    return (uint32_t)(h ^ (h >> 32));
-}
-
-// Gen C property records (walk_genc's props branch): a column's streams in metadata order, roles by
-// name; LOCALIZED_DICTIONARY strings as one sub-column per present_<lang> stream
-template <class PE>
-__device__ int prop_walk_genc(Rd<true>& r, PE& pe, PropTab& tab) {
-    const int32_t len = (int32_t)r.len;
-    int32_t o = 0;
-    uint64_t version, nlayers;
-    if (!r.uv(o, version) || !r.uv(o, nlayers)) return COVT_ERR_TRUNCATED;
-    if (version != 1) return COVT_ERR_BAD_HEADER;
-    for (uint64_t L = 0; L < nlayers; ++L) {
-        uint64_t nlen, extent, nfeat, ncols;
-        if (!r.uv(o, nlen) || nlen > (uint64_t)(len - o)) return COVT_ERR_TRUNCATED;
-        o += (int32_t)nlen;
-        if (!r.uv(o, extent) || !r.uv(o, nfeat) || !r.uv(o, ncols)) return COVT_ERR_TRUNCATED;
-        if (ncols > 4096) return COVT_ERR_BAD_HEADER;
-        int64_t d = 0;
-        pe.layer_begin();
-        for (uint32_t c = 0; c < (uint32_t)ncols; ++c) {
-            uint64_t cn, ns, sn, nv, bl;
-            if (!r.uv(o, cn) || cn > (uint64_t)(len - o) || (uint64_t)(len - o) - cn < 2) return COVT_ERR_TRUNCATED;
-            const int32_t name = o;
-            o += (int32_t)cn;
-            const int dtype = r.at(o), ctype = r.at(o + 1);
-            o += 2;
-            if (!r.uv(o, ns)) return COVT_ERR_TRUNCATED;
-            if (ns > 256) return COVT_ERR_BAD_HEADER;
-            const int kind = COVT_IS(name, cn, "id") ? 0 : (COVT_IS(name, cn, "geometry") || dtype == 6) ? 1 : 2;
-            const bool localized = kind == 2 && genc_prop_type(dtype) == COVT_PROP_STRING && ctype == 2;
-            for (uint32_t q = 0; q < (uint32_t)ns; ++q) {
-                if (!r.uv(o, sn) || sn > (uint64_t)(len - o)) return COVT_ERR_TRUNCATED;
-                const int32_t sname = o;
-                o += (int32_t)sn;
-                int enc;
-                if (!r.rec3(o, nv, bl, enc)) {
-                    if (!r.uv(o, nv) || !r.uv(o, bl) || o >= len) return COVT_ERR_TRUNCATED;
-                    enc = r.at(o++);
-                }
-                if (nv > 0x7fffffff || bl > 0x7fffffff) return COVT_ERR_BAD_HEADER;
-                if (kind == 2) {  // the name's role (and, localized, its hashes) while the window holds it
-                    uint32_t role = 0;
-                    if (COVT_IS(sname, sn, "present")) role |= PR_PRESENT;
-                    if (COVT_IS(sname, sn, "data")) role |= PR_DATA;
-                    if (COVT_IS(sname, sn, "length")) role |= PR_LENGTH;
-                    if (COVT_IS(sname, sn, "dictionary")) role |= PR_DICTIONARY;
-                    uint32_t h0 = 0, h8 = 0;
-                    if (localized) {
-                        if (sn > 8 && r.peek8(sname) == pk("present_", 0, 8)) {
-                            role |= PR_PRESENT_LANG;
-                            h8 = names_hash(r, sname + 8, (int32_t)sn - 8);
-                        }
-                        h0 = names_hash(r, sname, (int32_t)sn);
-                    }
-                    tab.set(q, PropSm{h0, h8, sname, (int32_t)sn, (int32_t)nv, (int32_t)bl, (int32_t)d, (uint16_t)enc,
-                                      (uint16_t)role});
-                }
-                d += (int64_t)bl;
-            }
-            if (kind != 2) continue;
-            PropRaw p = prop_init((int32_t)L, (int32_t)c, (int32_t)nfeat);
-            p.name_off = name;
-            p.name_len = (int32_t)cn;
-            p.type = genc_prop_type(dtype);
-            p.ctype = ctype;
-            if (localized) {
-                prop_localized(r, pe, tab, ns, p);
-            } else {
-                for (uint32_t q = 0; q < (uint32_t)ns; ++q) {
-                    const PropSm sm = tab.get(q);
-                    if (sm.role & PR_PRESENT) prop_stream(p, 0, sm.off, sm.nv, sm.bl, sm.enc);
-                    if (sm.role & PR_DATA) prop_stream(p, 1, sm.off, sm.nv, sm.bl, sm.enc);
-                    if (sm.role & PR_LENGTH) prop_stream(p, 2, sm.off, sm.nv, sm.bl, sm.enc);
-                    if (sm.role & PR_DICTIONARY) prop_stream(p, 3, sm.off, sm.nv, sm.bl, sm.enc);
-                }
-                pe(p);
+    // f(s) for the present_<lang> entries below ns, in order
+    template <class F>
+    __device__ __forceinline__ void for_each_lang(uint32_t ns, F&& f) const {
+        for (uint32_t j = 0; 64 * j < ns; ++j) {
+            uint64_t pm = __ballot(64 * j + threadIdx.x < ns && ((pick(er, j) >> 16) & PR_PRESENT_LANG));
+            while (pm) {
+                const uint32_t q = 64 * j + (uint32_t)__builtin_ctzll(pm);
+                pm &= pm - 1;
+                f(q);
             }
         }
-        if (d > (int64_t)(len - o)) return COVT_ERR_TRUNCATED;
-        pe.layer_end(o);  // the layer's data starts where its metadata ends
-        o += (int32_t)d;
     }
-    return o == len ? COVT_OK : COVT_ERR_BAD_HEADER;
-}
+    // the last entry named as lang's name after its present_ prefix (-1: none): 64 candidates per step, hash
+    // matches confirmed from the highest down (a serial all-pairs scan was ~ns^2 dependent LDS reads: ms per tile)
+    __device__ __forceinline__ int32_t last_named(Rd<true>& r, uint32_t ns, const PropSm& lang) const {
+        const int32_t ll = lang.nlen - kLangPrefix;
+        for (int32_t k0 = ((int32_t)ns - 1) & ~63; k0 >= 0; k0 -= 64) {
+            const uint32_t jj = (uint32_t)k0 >> 6;
+            const int32_t k = k0 + (int32_t)threadIdx.x;
+            uint64_t bal = __ballot(k < (int32_t)ns && pick(nlen, jj) == ll && pick(h0, jj) == lang.h8);
+            while (bal) {
+                const int hi = 63 - __builtin_clzll(bal);
+                if (r.same(rl(pick(noff, jj), (uint32_t)hi), lang.noff + kLangPrefix, ll)) return k0 + hi;
+                bal &= ~(1ull << hi);
+            }
+        }
+        return -1;
+    }
+};
 
 // names_hash of every stream name of a localized column at once, a lane per stream (name bytes read from
 // the tile): on the scalar unit, the walk's bound, two hashes cost ~60 instructions per stream.  h8 (the
@@ -2008,53 +1617,9 @@ __device__ __forceinline__ void names_hash_lanes(const uint8_t* t, int32_t len, 
     }
 }
 
-// The localized sub-columns of a Gen C string column from its stream table (prop_walk_genc's rule): one
-// per present_<lang> stream, with the last stream named <lang> as data and the last length / dictionary
-template <class PE>
-__device__ __forceinline__ void prop_localized(Rd<true>& r, PE& pe, const PropTab& tab, uint32_t ns, const PropRaw& p) {
-    const int32_t ls = tab.last_role(ns, PR_LENGTH, 0), ds = tab.last_role(ns, PR_DICTIONARY, PR_LENGTH);
-    const PropSm lsm = tab.get(ls >= 0 ? (uint32_t)ls : 0u), dsm = tab.get(ds >= 0 ? (uint32_t)ds : 0u);
-    int32_t lang = 0;
-    for (uint32_t j = 0; 64 * j < ns; ++j) {  // the present_<lang> streams in order
-        uint64_t pm = __ballot(64 * j + threadIdx.x < ns && ((PropTab::pick(tab.er, j) >> 16) & PR_PRESENT_LANG));
-        while (pm) {
-            const uint32_t q = 64 * j + (uint32_t)__builtin_ctzll(pm);
-            pm &= pm - 1;
-            const PropSm sm = tab.get(q);
-            const int32_t ll = sm.nlen - 8;
-            // the last stream named <lang>: 64 candidates per step, hash matches confirmed from the highest
-            // down (a serial all-pairs scan was ~ns^2 dependent LDS reads: ms per tile)
-            int dd = -1;
-            for (int32_t k0 = ((int32_t)ns - 1) & ~63; k0 >= 0 && dd < 0; k0 -= 64) {
-                const uint32_t jj = (uint32_t)k0 >> 6;
-                const int32_t k = k0 + (int32_t)threadIdx.x;
-                const bool m = k < (int32_t)ns && PropTab::pick(tab.nlen, jj) == ll && PropTab::pick(tab.h0, jj) == sm.h8;
-                uint64_t bal = __ballot(m);
-                while (bal && dd < 0) {
-                    const int hi = 63 - __builtin_clzll(bal);
-                    if (names_equal(r, PropTab::rl(PropTab::pick(tab.noff, jj), (uint32_t)hi), sm.noff + 8, ll)) dd = k0 + hi;
-                    bal &= ~(1ull << hi);
-                }
-            }
-            PropRaw x = p;
-            x.lang = lang++;
-            x.lang_off = sm.noff + 8;
-            x.lang_len = ll;
-            prop_stream(x, 0, sm.off, sm.nv, sm.bl, sm.enc);
-            if (dd >= 0) {
-                const PropSm dm = tab.get((uint32_t)dd);
-                prop_stream(x, 1, dm.off, dm.nv, dm.bl, dm.enc);
-            }
-            if (ls >= 0) prop_stream(x, 2, lsm.off, lsm.nv, lsm.bl, lsm.enc);
-            if (ds >= 0) prop_stream(x, 3, dsm.off, dsm.nv, dsm.bl, dsm.enc);
-            pe(x);
-        }
-    }
-}
-
-// prop_walk_genc on walk_count's speculative tables (FastGenc): a column header and a stream record are
+// walk_genc's property records on walk_count's speculative tables (FastGenc): a column header and a stream record are
 // one LDS read each, and a stream's name, numValues and encoding are parsed only in property columns.
-// kFastFallback when the tile leaves the fast grammar (the caller walks it with prop_walk_genc); a
+// kFastFallback when the tile leaves the fast grammar (the caller walks it with walk_genc); a
 // successful fast walk emits the same records.
 template <class PE>
 __device__ int prop_walk_genc_fast(FastGenc& f, Rd<true>& r, PE& pe, PropTab& tab) {
@@ -2148,120 +1713,15 @@ __device__ int prop_walk_genc_fast(FastGenc& f, Rd<true>& r, PE& pe, PropTab& ta
     return o == len ? COVT_OK : kFastFallback;
 }
 
-// Gen D property records (walk_gend's props branch): the implicit present stream, then data / length /
-// dictionary in TreeMap<StreamType> order (the last metadata entry of a type)
-template <class PE>
-__device__ int prop_walk_gend(Rd<true>& r, PE& pe) {
-    const int32_t len = (int32_t)r.len;
-    int32_t o = 0;
-    int32_t layer = 0;
-    while (o < len) {
-        const bool optimized = r.at(o++) & 1;
-        int32_t v, extent, nfeat, ncols;
-        if (!r.j4(o, v)) return COVT_ERR_TRUNCATED;
-        if (!optimized) {
-            if (v < 0 || v > len - o) return COVT_ERR_TRUNCATED;
-            o += v;
-        }
-        if (!r.j4(o, extent) || !r.j4(o, nfeat) || !r.j4(o, ncols)) return COVT_ERR_TRUNCATED;
-        if (ncols < 0 || ncols > 4096) return COVT_ERR_BAD_HEADER;
-        const int32_t meta = o;
-        for (int32_t ci = 0; ci < ncols; ++ci) {  // skip the metadata (checked by the Id / Geometry walk)
-            int32_t x;
-            if (optimized || ci == 0) {
-                if (!r.j4(o, x)) return COVT_ERR_TRUNCATED;
-            } else {
-                if (!r.j4(o, x) || x < 0 || x > len - o) return COVT_ERR_TRUNCATED;
-                o += x;
-            }
-            if (o >= len) return COVT_ERR_TRUNCATED;
-            const int desc = r.at(o++), dtype = (desc >> 3) & 0xF, ctype = desc & 0x7;
-            if (ctype > 4) return COVT_ERR_BAD_HEADER;
-            for (;;) {
-                if (o >= len) return COVT_ERR_TRUNCATED;
-                const int sd = r.at(o++), type = sd >> 4, enc = sd & 0xF;
-                if (type > ST_M || enc > 9) return COVT_ERR_BAD_HEADER;
-                int32_t nv, bl;
-                if (!r.j4(o, nv) || !r.j4(o, bl)) return COVT_ERR_TRUNCATED;
-                if ((dtype == 8 && type == ST_VERTEX_BUFFER) || (type == ST_DATA && ctype == CT_PLAIN) ||
-                    type == ST_DICTIONARY)
-                    break;
-            }
-        }
-        int32_t m = meta;
-        int64_t d = o;
-        pe.layer_begin();
-        for (int32_t ci = 0; ci < ncols; ++ci) {
-            int32_t x, kind;
-            int32_t name_off = -1, name_len = 0;
-            if (optimized || ci == 0) {
-                r.j4(m, x);
-                kind = x == 0 ? 0 : (x == 1 ? 1 : 2);
-            } else {
-                r.j4(m, x);
-                kind = COVT_IS(m, x, "id") ? 0 : COVT_IS(m, x, "geometry") ? 1 : 2;
-                name_off = m;
-                name_len = x;
-                m += x;
-            }
-            const int desc = r.at(m++), dtype = (desc >> 3) & 0xF, ctype = desc & 0x7;
-            const int32_t s0 = m;
-            uint32_t have = 0;
-            for (;;) {
-                const int sd = r.at(m++), type = sd >> 4;
-                int32_t nv, bl;
-                r.j4(m, nv);
-                r.j4(m, bl);
-                have |= 1u << type;
-                if ((dtype == 8 && type == ST_VERTEX_BUFFER) || (type == ST_DATA && ctype == CT_PLAIN) ||
-                    type == ST_DICTIONARY)
-                    break;
-            }
-            PropRaw p = prop_init(layer, ci, nfeat);
-            if (kind == 2 && dtype != 0) {  // the implicit present stream
-                const int32_t pl = r.byte_rle_length((int32_t)d, nfeat < 0 ? 0 : (int32_t)(((int64_t)nfeat + 7) / 8));
-                if (pl < 0) return COVT_ERR_TRUNCATED;
-                prop_stream(p, 0, d, nfeat, pl, 7);
-                d += pl;
-            }
-            for (int type = 0; type < 12; ++type) {
-                if (!(have >> type & 1) || (kind == 2 && type == ST_PRESENT)) continue;
-                int enc = 0;
-                int32_t nv = 0, bl = 0;
-                for (int32_t q = s0; q < m;) {  // the last entry of this type
-                    const int sd = r.at(q++);
-                    int32_t a, b;
-                    r.j4(q, a);
-                    r.j4(q, b);
-                    if ((sd >> 4) == type) enc = sd & 0xF, nv = a, bl = b;
-                }
-                if (bl < 0) return COVT_ERR_BAD_HEADER;
-                if (type > ST_PRESENT && type <= ST_DICTIONARY) prop_stream(p, type, d, nv, bl, enc);
-                d += bl;
-            }
-            if (d > len) return COVT_ERR_TRUNCATED;
-            if (kind == 2) {
-                p.name_off = name_off;
-                p.name_len = name_len;
-                p.type = gend_prop_type(dtype);
-                p.ctype = ctype;
-                pe(p);
-            }
-        }
-        pe.layer_end(0);
-        o = (int32_t)d;
-        ++layer;
-    }
-    return COVT_OK;
-}
-
-struct PropCountEmit {
+struct PropCountEmit {  // (visitors of the container walks: the property records)
+    static constexpr bool kStreams = false, kProps = true;
     int64_t n = 0;
     __device__ void operator()(const PropRaw&) { ++n; }
-    __device__ void layer_begin() {}
+    __device__ void layer_begin(int32_t = 0, int32_t = 0) {}
     __device__ void layer_end(int64_t) {}
 };
 struct PropRecEmit {
+    static constexpr bool kStreams = false, kProps = true;
     PropRaw* recs;    // this tile's first record
     int32_t* rtile;   // (null: the tile's slots, no tile column)
     int32_t t;
@@ -2274,7 +1734,7 @@ struct PropRecEmit {
         }
         ++n;
     }
-    __device__ void layer_begin() { k0 = n; }
+    __device__ void layer_begin(int32_t = 0, int32_t = 0) { k0 = n; }
     __device__ void layer_end(int64_t data_start) {  // Gen C: data offsets relative to the layer's data start
         if (!data_start) return;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -2293,7 +1753,7 @@ struct PropRecEmit {
 // a tile's property records: Gen C through the fast walk first (the serial walk on a fallback)
 template <class PE>
 __device__ __forceinline__ int prop_walk_tile(Rd<true>& r, PE& e, PropTab& tab, int32_t format) {
-    if (format != COVT_FORMAT_GENC) return prop_walk_gend(r, e);
+    if (format != COVT_FORMAT_GENC) return walk_gend(r, e);
     FastGenc f;
     f.t = r.t;
     f.len = (int32_t)r.len;
@@ -2306,7 +1766,7 @@ __device__ __forceinline__ int prop_walk_tile(Rd<true>& r, PE& e, PropTab& tab, 
     const int st = prop_walk_genc_fast(f, r, e, tab);
     if (st != kFastFallback) return st;
     e = fresh;
-    return prop_walk_genc(r, e, tab);
+    return walk_genc(r, e, tab);
 }
 
 // one wave per tile (tiles the Id / Geometry walk failed contribute nothing).  EMIT false: count the
@@ -2316,7 +1776,8 @@ __device__ __forceinline__ int prop_walk_tile(Rd<true>& r, PE& e, PropTab& tab, 
 constexpr int kPropSlots = 256;
 constexpr size_t kPropSlotBytes = (size_t)2 << 30;  // slot memory a plan may take (10k tiles: 328 MB)
 // The two walks read the same metadata as the Id / Geometry walk, which accepted the tile, so they cannot
-// fail on it; if one does anyway (a divergence between the walkers) the count walk raises `diverged` and
+// fail on it (the serial walks are one grammar; the speculative and the serial walk remain two walkers); if
+// one does anyway (a divergence between the walkers) the count walk raises `diverged` and
 // the plan fails with COVT_ERR_BAD_HEADER instead of dropping the tile's property columns, and the emit
 // walk never writes past the records its count walk found (pcb[t + 1] - pcb[t]).
 template <bool EMIT>

@@ -4,7 +4,6 @@
 #ifndef COVT_PROPS_PLAN_H
 #define COVT_PROPS_PLAN_H
 
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "covt.h"
@@ -18,7 +17,7 @@ struct PropRaw {
     int64_t s_off[4];
     int32_t s_nv[4], s_bl[4], s_enc[4];
 };
-__host__ __device__ inline PropRaw prop_init(int32_t layer, int32_t column, int32_t nf) {
+COVT_HD inline PropRaw prop_init(int32_t layer, int32_t column, int32_t nf) {
     PropRaw p{};
     p.layer = layer;
     p.column = column;
@@ -30,8 +29,8 @@ __host__ __device__ inline PropRaw prop_init(int32_t layer, int32_t column, int3
 }
 // (constant indices only: a record indexed by a run-time role lives in scratch on the GPU, where the
 // property walk kept its record -- 144 bytes per lane of private memory)
-__host__ __device__ inline void prop_stream(PropRaw& p, int role, int64_t off, int32_t nv, int32_t bl, int32_t enc) {
-#pragma unroll
+COVT_HD inline void prop_stream(PropRaw& p, int role, int64_t off, int32_t nv, int32_t bl, int32_t enc) {
+    COVT_UNROLL
     for (int r = 0; r < 4; ++r) {
         if (r != role) continue;
         p.s_off[r] = off;
@@ -41,10 +40,10 @@ __host__ __device__ inline void prop_stream(PropRaw& p, int role, int64_t off, i
     }
 }
 // Gen C ColumnDataType (evaluation/file/ColumnDataType.java) / Gen D (converter/ColumnDataType.java)
-__host__ __device__ inline int genc_prop_type(int dt) {
+COVT_HD inline int genc_prop_type(int dt) {
     return dt == 0 ? COVT_PROP_STRING : dt == 1 ? COVT_PROP_FLOAT : dt == 3 ? COVT_PROP_INT64 : dt == 5 ? COVT_PROP_BOOLEAN : -1;
 }
-__host__ __device__ inline int gend_prop_type(int dt) {
+COVT_HD inline int gend_prop_type(int dt) {
     return dt == 0 ? COVT_PROP_BOOLEAN : dt == 3 ? COVT_PROP_INT64 : dt == 5 ? COVT_PROP_FLOAT : dt == 7 ? COVT_PROP_STRING : -1;
 }
 
@@ -59,7 +58,7 @@ struct PropStreams {
     int64_t count[3];                     // output elements of each
     int64_t in_bytes;                     // stream bytes + bytes read in place (floats, the owner's dictionary)
 };
-__host__ __device__ inline void prop_streams(const PropRaw& q, int id_mode, PropStreams& ps) {
+COVT_HD inline void prop_streams(const PropRaw& q, int id_mode, PropStreams& ps) {
     uint16_t fl = 0;
     const int32_t nf = q.nf > 0 ? q.nf : 0, nb = (int32_t)(((int64_t)nf + 7) / 8);
     const bool early_unsup = q.type < 0 || q.s_off[1] < 0 || (q.type != COVT_PROP_BOOLEAN && q.s_off[0] < 0) ||
@@ -126,7 +125,7 @@ __host__ __device__ inline void prop_streams(const PropRaw& q, int id_mode, Prop
 
 // covt_prop_info of a (sub)column before the layout (stream indices, output offsets filled later; the
 // FLOAT data and STRING dictionary input offsets parked in out_off[1] / out_off[3])
-__host__ __device__ inline covt_prop_info prop_info_of(const PropRaw& q, int32_t t, int64_t tile_off) {
+COVT_HD inline covt_prop_info prop_info_of(const PropRaw& q, int32_t t, int64_t tile_off) {
     covt_prop_info pi{};
     pi.tile = t;
     pi.layer = q.layer;
@@ -152,8 +151,8 @@ __host__ __device__ inline covt_prop_info prop_info_of(const PropRaw& q, int32_t
 }
 
 // the property output layout: bytes of a (sub)column's validity, values and (the owner's) dictionary
-__host__ __device__ inline int64_t prop_align16(int64_t x) { return (x + 15) & ~(int64_t)15; }
-__host__ __device__ inline void prop_layout_sizes(const covt_prop_info& pi, bool owner, int64_t (&sz)[4]) {
+COVT_HD inline int64_t prop_align16(int64_t x) { return (x + 15) & ~(int64_t)15; }
+COVT_HD inline void prop_layout_sizes(const covt_prop_info& pi, bool owner, int64_t (&sz)[4]) {
     const int64_t n = pi.n_features > 0 ? pi.n_features : 0, nb = (n + 7) / 8;
     const int64_t vbytes = pi.type == COVT_PROP_BOOLEAN ? nb : pi.type == COVT_PROP_INT64 ? 8 * n : 4 * n;
     sz[0] = prop_align16(nb);
@@ -163,7 +162,7 @@ __host__ __device__ inline void prop_layout_sizes(const covt_prop_info& pi, bool
     sz[3] = own ? prop_align16(pi.dict_bytes) : 0;
 }
 // the largest-first materialization order key (features + dictionary entries; ties in tile order)
-__host__ __device__ inline uint64_t prop_order_key(const covt_prop_info& pi) {
+COVT_HD inline uint64_t prop_order_key(const covt_prop_info& pi) {
     return (1ull << 40) - (uint64_t)((int64_t)pi.n_features + pi.n_dict);
 }
 

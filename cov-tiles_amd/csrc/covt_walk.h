@@ -3,10 +3,24 @@
 #ifndef COVT_WALK_H
 #define COVT_WALK_H
 
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "covt.h"
+
+// host/device qualifiers that vanish without HIP, so g++ compiles the plain-C++ headers built on this one
+// (covt_props_plan.h, covt_container.h) for their stand-alone checks
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#include <hip/hip_runtime.h>
+#define COVT_HD __host__ __device__
+#define COVT_HDI __host__ __device__ __forceinline__
+#define COVT_UNROLL _Pragma("unroll")
+#define COVT_UNROLL1 _Pragma("unroll 1")
+#else
+#define COVT_HD
+#define COVT_HDI inline
+#define COVT_UNROLL
+#define COVT_UNROLL1
+#endif
 
 // ---- wire enums --------------------------------------------------
 enum StreamType { ST_PRESENT = 0, ST_DATA = 1, ST_LENGTH = 2, ST_DICTIONARY = 3, ST_GEOMETRY_TYPES = 4,
@@ -21,13 +35,13 @@ struct RawStream {
 };
 
 // 32 - Integer.numberOfLeadingZeros(extent), CovtParser.java:77
-__host__ __device__ inline int nbits_of_extent(uint64_t extent) {
+COVT_HD inline int nbits_of_extent(uint64_t extent) {
     const uint32_t e = (uint32_t)extent;
     return e ? 32 - __builtin_clz(e) : 0;
 }
 
 // CovtParser dispatch: decodeGeometryColumn (:392-511) and decodedIds (:552-572)
-__host__ __device__ inline void choose_op(const RawStream& s, int id_mode, int& op, int64_t& nvals, int& elem, int64_t& out_elems) {
+COVT_HD inline void choose_op(const RawStream& s, int id_mode, int& op, int64_t& nvals, int& elem, int64_t& out_elems) {
     op = COVT_OP_NONE;
     nvals = s.nv;
     elem = 4;
@@ -68,7 +82,7 @@ __host__ __device__ inline void choose_op(const RawStream& s, int id_mode, int& 
 }
 
 // decode kernel family of an op (launch grouping of both plans)
-__host__ __device__ constexpr int covt_op_family(int op) {
+COVT_HD constexpr int covt_op_family(int op) {
     return (op >= COVT_OP_FPF_ZZ_DELTA_I32 && op <= COVT_OP_FPF_DELTA_MORTON) ? COVT_FAMILY_FASTPFOR
            : ((op >= COVT_OP_VARINT_I32 && op <= COVT_OP_VARINT_DELTA_MORTON) ||
               (op >= COVT_OP_VARINT_U64 && op <= COVT_OP_VARINT_ZZ_DELTA_I64) ||

@@ -55,7 +55,7 @@ def test_roundtrip_variants(oracle, decodable_tiles, optimized, allow_fpf, with_
 
 
 def test_product_gend_plan_matches_oracle_walk(covt, oracle, decodable_tiles):
-    """libcovt's Gen D walker (covt_host.cpp walk_gend) agrees with the oracle's on converted tiles, Id /
+    """libcovt's Gen D walker (covt_container.h walk_gend, on the host) agrees with the oracle's on converted tiles, Id /
     Geometry streams and property records alike."""
     tiles = [RT.genc_to_gend(t)[0] for _, t in decodable_tiles[::3]]
     plan = covt.Plan.from_tiles(tiles, covt.FORMAT_GEND, 0, covt.PLAN_PROPERTIES)

@@ -456,6 +456,30 @@ def test_properties_gend(covt, gpu_available, decodable_tiles, optimized):
     _assert_same_materialization(covt, hp, dp)
 
 
+@pytest.mark.parametrize("walk", [0, 4], ids=["wave", "lanes4"])
+def test_valid_tiles_the_fast_walk_declines(covt, gpu_available, decodable_tiles, walk):
+    """The serial walkers (covt_container.h's grammar in the wave and lane layouts) on valid Gen C tiles: a tile
+    whose version byte 0x01 is written as the 5-byte varint 81 80 80 80 00 still reads as version 1, but the
+    speculative walk takes no varint over 4 bytes (FastGenc::uv4) and hands the tile to the serial walk.  Three
+    fixtures and a merge of five, each beside its unmodified original, without and with property columns: the
+    host plan's records, decode, geometry and property records, every tile accepted."""
+    omt = [t for k, t in decodable_tiles if k.startswith("omt/")]
+    tiles = []
+    for t in omt[:3] + [_merge_genc(omt[3:8])]:
+        assert t[0] == 1
+        tiles += [t, b"\x81\x80\x80\x80\x00" + t[1:]]
+    for flags in (0, covt.PLAN_PROPERTIES):
+        hp = _host_plan(covt, tiles, covt.FORMAT_GENC, 0, device_walk=walk, flags=flags)
+        assert (hp.tile_status == 0).all()
+        dp = _device_plan(covt, hp, covt.FORMAT_GENC, 0)
+        assert (dp.host_copy()[2] == 0).all()
+        _assert_same_plan(hp, dp)
+        _assert_same_decode(covt, hp, dp)
+        _assert_same_geometry(hp, dp)
+        if flags:
+            _assert_same_properties(hp, dp)
+
+
 def test_properties_split(covt, gpu_available, decodable_tiles, golden_streams):
     """Property plans with the split rule forced (long property RLE streams cut into group chunks too):
     the same plan, and the Id / Geometry streams still match the golden digests."""
