@@ -169,6 +169,15 @@ MEASURES_INFO_DTYPE = np.dtype([("tile", np.int32), ("layer", np.int32), ("n_fea
 MEASURES_TOO_LARGE = 0x1
 assert (MEASURES_DESC_DTYPE.itemsize == 24 and MEASURES_RESULT_DTYPE.itemsize == 8
         and MEASURES_INFO_DTYPE.itemsize == 32)
+# feature selection (include/covt.h "Feature selection")
+SELECT_DESC_DTYPE = np.dtype([("off", np.int64), ("byte_cap", np.int64), ("n_features", np.int32), ("flags", np.int32)])
+SELECT_RESULT_DTYPE = np.dtype([("status", np.int32), ("n_selected", np.int32), ("n_bytes", np.int64)])
+SELECT_INFO_DTYPE = np.dtype([("tile", np.int32), ("layer", np.int32), ("n_features", np.int32),
+                              ("desc_index", np.int32), ("off", np.int64), ("byte_cap", np.int64),
+                              ("flags", np.int32), ("reserved", np.int32)])
+SELECT_TOO_LARGE = 0x1
+SELECT_WINDOW, SELECT_MIN_SIZE, SELECT_KEEP_EMPTY = 0x1, 0x2, 0x4
+assert SELECT_DESC_DTYPE.itemsize == 24 and SELECT_RESULT_DTYPE.itemsize == 16 and SELECT_INFO_DTYPE.itemsize == 40
 # georeferenced geometry (include/covt.h "Georeferenced geometry")
 CRS_TILE, CRS_WEB_MERCATOR, CRS_CRS84 = 0, 1, 2
 GEO_IDENTITY, GEO_AFFINE, GEO_AFFINE_LAT = 0, 1, 2
@@ -197,6 +206,33 @@ class PlanOptions(C.Structure):
 
     def __repr__(self):
         return "PlanOptions(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f, _ in self._fields_[1:])
+
+
+class SelectPred(C.Structure):
+    """covt_select_pred (include/covt.h "Feature selection"): which features a selection keeps.  ``window`` =
+    (xmin, ymin, xmax, ymax) in the space of the bounding boxes keeps the features whose box meets it;
+    ``min_area`` / ``min_length`` (tile pixels) keep those that reach either, and everything without extent;
+    ``keep_empty`` keeps the features without a coordinate.  ``SelectPred()`` keeps every non-empty feature."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("window", C.c_double * 4), ("min_area", C.c_double),
+                ("min_length", C.c_double)]
+
+    def __init__(self, window=None, min_area=None, min_length=None, keep_empty: bool = False):
+        super().__init__()
+        lib().covt_select_pred_init(C.byref(self))
+        if window is not None:
+            self.flags |= SELECT_WINDOW
+            self.window = (C.c_double * 4)(*[float(v) for v in window])
+        if min_area is not None or min_length is not None:
+            self.flags |= SELECT_MIN_SIZE
+            # (a minimum left out never admits a feature: nothing reaches +inf)
+            self.min_area = float("inf") if min_area is None else float(min_area)
+            self.min_length = float("inf") if min_length is None else float(min_length)
+        if keep_empty:
+            self.flags |= SELECT_KEEP_EMPTY
+
+    def __repr__(self):
+        return "SelectPred(flags=%#x, window=%r, min_area=%r, min_length=%r)" % (
+            self.flags, tuple(self.window), self.min_area, self.min_length)
 
 
 STREAM_INFO_DTYPE = np.dtype([(n, np.int32 if t is C.c_int32 else np.int64) for n, t in StreamInfo._fields_])
@@ -238,12 +274,13 @@ _SIGNATURES = {
     **_sig(None, [_vp], "covt_plan_options_init", "covt_plan_destroy", "covt_device_plan_destroy"),
     **_sig(_i64, [_vp], "covt_plan_num_streams", "covt_plan_output_bytes", "covt_plan_num_descs",
            "covt_plan_num_geometry_columns", "covt_plan_assembly_bytes", "covt_plan_wkb_bytes", "covt_plan_bbox_bytes",
-           "covt_plan_measures_bytes",
+           "covt_plan_measures_bytes", "covt_plan_select_bytes",
            "covt_plan_num_property_columns", "covt_plan_property_bytes"),
     **_sig(_int, [_vp, _i64p, _i64p, _i64p], "covt_plan_totals", "covt_device_plan_totals"),
     **_sig(_int, [_vp, _vp], "covt_plan_streams", "covt_plan_descs", "covt_plan_geometry_columns",
            "covt_plan_geometry_descs", "covt_plan_wkb_columns", "covt_plan_wkb_descs", "covt_plan_bbox_columns",
-           "covt_plan_bbox_descs", "covt_plan_measures_columns", "covt_plan_measures_descs", "covt_plan_property_columns", "covt_plan_property_descs"),
+           "covt_plan_bbox_descs", "covt_plan_measures_columns", "covt_plan_measures_descs", "covt_plan_select_columns",
+           "covt_plan_select_descs", "covt_plan_property_columns", "covt_plan_property_descs"),
     **_sig(_int, [_vp, _i64p], "covt_plan_desc_streams", "covt_plan_family_counts", "covt_device_plan_family_counts"),
     "covt_plan_tile_status": (_int, [_vp, _i32p]),
     "covt_plan_release_device": (_int, [_vp]),
@@ -260,6 +297,11 @@ _SIGNATURES = {
     "covt_geometry_wkb_device": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "covt_geometry_bbox_device": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "covt_geometry_measures_device": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    # feature selection
+    "covt_select_pred_init": (None, [_vp]),
+    "covt_select_predicate_device": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "covt_geometry_select_device": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "covt_plan_select_host": (_int, [_vp, _u8p, _u64, _i32, _vp, _vp, _vp, _vp]),
     # georeferenced geometry
     "covt_geo_transform": (_int, [_i32, _i32, _i32, _i32, _i32, _vp]),
     "covt_plan_geometry_extents": (_int, [_vp, _vp]),
@@ -274,18 +316,20 @@ _SIGNATURES = {
     "covt_device_plan_pool_trim": (_int, [_int, _u64]),
     **_sig(_i64, [_vp], "covt_device_plan_num_streams", "covt_device_plan_num_descs", "covt_device_plan_output_bytes",
            "covt_device_plan_num_geometry_columns", "covt_device_plan_assembly_bytes", "covt_device_plan_wkb_bytes",
-           "covt_device_plan_bbox_bytes", "covt_device_plan_measures_bytes", "covt_device_plan_num_property_columns", "covt_device_plan_property_bytes"),
+           "covt_device_plan_bbox_bytes", "covt_device_plan_measures_bytes", "covt_device_plan_select_bytes",
+           "covt_device_plan_num_property_columns", "covt_device_plan_property_bytes"),
     **_sig(_vp, [_vp], "covt_device_plan_descs_device", "covt_device_plan_streams_device",
            "covt_device_plan_tile_status_device", "covt_device_plan_order_device",
            "covt_device_plan_geometry_descs_device", "covt_device_plan_wkb_descs_device",
-           "covt_device_plan_bbox_descs_device", "covt_device_plan_measures_descs_device",
+           "covt_device_plan_bbox_descs_device", "covt_device_plan_measures_descs_device", "covt_device_plan_select_descs_device",
            "covt_device_plan_property_descs_device"),
     "covt_device_plan_copy": (_int, [_vp, _vp, _vp, _i32p]),
     **_sig(_int, [_vp, _vp, _vp], "covt_device_plan_geometry_copy", "covt_device_plan_wkb_copy",
-           "covt_device_plan_bbox_copy", "covt_device_plan_measures_copy", "covt_device_plan_property_copy"),
+           "covt_device_plan_bbox_copy", "covt_device_plan_measures_copy", "covt_device_plan_select_copy",
+           "covt_device_plan_property_copy"),
     "covt_device_plan_geometry": (_int, [_vp, _vp]),
     "covt_device_plan_decode": (_int, [_vp, _vp, _vp, _vp, _vp]),
-    **_sig(_int, [_vp] * 6, "covt_device_plan_assemble", "covt_device_plan_bbox"),
+    **_sig(_int, [_vp] * 6, "covt_device_plan_assemble", "covt_device_plan_bbox", "covt_device_plan_select"),
     **_sig(_int, [_vp] * 7, "covt_device_plan_materialize", "covt_device_plan_measures"),
     "covt_device_plan_wkb": (_int, [_vp] * 8),
 }
@@ -585,6 +629,9 @@ _PRODUCTS = {
     "measures": _Product("num_geometry_columns", "measures_bytes", "mdescs", "measures", MEASURES_INFO_DTYPE,
                          MEASURES_DESC_DTYPE, MEASURES_DESC_DTYPE.itemsize, MEASURES_RESULT_DTYPE, ("int32", 2), False,
                          True, ("d_mdesc", "d_measures", "d_mres")),
+    "select": _Product("num_geometry_columns", "select_bytes", "sdescs", "select", SELECT_INFO_DTYPE, SELECT_DESC_DTYPE,
+                       SELECT_DESC_DTYPE.itemsize, SELECT_RESULT_DTYPE, ("int64", 2), False, True,
+                       ("d_sdesc", "d_select", "d_sres")),
     "property": _Product("num_property_columns", "property_bytes", "pdescs", "props", PROP_INFO_DTYPE, PROP_DESC_DTYPE,
                          PROP_DESC_DTYPE.itemsize, PROP_RESULT_DTYPE, ("int32", 2), True, False,
                          ("d_pdesc", "d_props", "d_pres")),
@@ -674,6 +721,13 @@ class Plan:
         if self.num_geometry_columns:
             L.covt_plan_measures_columns(h, self.measures.ctypes.data)
             L.covt_plan_measures_descs(h, self.mdescs.ctypes.data)
+        # feature selection (include/covt.h "Feature selection"): one column per geometry column
+        self.select_bytes = int(L.covt_plan_select_bytes(h))
+        self.select = np.zeros(self.num_geometry_columns, dtype=SELECT_INFO_DTYPE)
+        self.sdescs = np.zeros(self.num_geometry_columns, dtype=SELECT_DESC_DTYPE)
+        if self.num_geometry_columns:
+            L.covt_plan_select_columns(h, self.select.ctypes.data)
+            L.covt_plan_select_descs(h, self.sdescs.ctypes.data)
         # property columns (include/covt.h "Property columns"; plans made with PLAN_PROPERTIES)
         self.num_property_columns = int(L.covt_plan_num_property_columns(h))
         self.property_bytes = int(L.covt_plan_property_bytes(h))
@@ -803,6 +857,31 @@ class Plan:
         o, n = int(m["off"]), int(m["n_features"])
         return MeasuresColumn(buf[o:o + 8 * n].view(np.float64), buf[o + 8 * n:o + 16 * n].view(np.float64),
                               buf[o + 16 * n:o + 20 * n].view(np.int32))
+
+    def select_host(self, pred: "SelectPred", crs=None, tile_zxy=None):
+        """H2D + decode + geometry assembly + WKB and bounding boxes (in `crs`, given the tiles' z, x, y) +
+        measures if `pred` has a size cut + predicate + select + D2H (covt_plan_select_host).
+        Returns (uint8 select buffer, results[num_geometry_columns] in tile order); see select_column."""
+        buf = np.zeros(max(self.select_bytes, 1), dtype=np.uint8)
+        res = np.zeros(max(self.num_geometry_columns, 1), dtype=SELECT_RESULT_DTYPE)
+        zxy = _zxy(tile_zxy, self.n_tiles) if tile_zxy is not None else None
+        _raise(lib().covt_plan_select_host(self._h, _ptr(self.blob, C.c_uint8), self.blob.size,
+                                           CRS_TILE if crs is None else crs,
+                                           zxy.ctypes.data if zxy is not None else None, C.byref(pred),
+                                           buf.ctypes.data, res.ctypes.data), "covt_plan_select_host")
+        return buf[:self.select_bytes], res[:self.num_geometry_columns]
+
+    def select_column(self, buf: np.ndarray, sres: np.ndarray, c: int) -> "SelectedColumn":
+        """Column c (tile order) of a select buffer -> SelectedColumn (raises on its status)."""
+        q, r = self.select[c], sres[c]
+        _raise(int(r["status"]), "select column %d (tile %d, layer %d)" % (c, q["tile"], q["layer"]))
+        o, n, k = int(q["off"]), int(q["n_features"]), int(r["n_selected"])
+        a16 = lambda x: (x + 15) & ~15  # noqa: E731  (covt_select_plan.h: every member padded to 16 bytes)
+        sel = o + a16(n)
+        offs = sel + a16(4 * n)
+        data = offs + a16(4 * (n + 1))
+        return SelectedColumn(buf[sel:sel + 4 * k].view(np.int32),
+                              WkbColumn(buf[offs:offs + 4 * (k + 1)].view(np.int32), buf[data:data + int(r["n_bytes"])]))
 
     def properties_host(self):
         """H2D + decode + property materialization + D2H (covt_plan_properties_host).
@@ -1027,6 +1106,39 @@ class DeviceBatch:
         """(measures bytes, results in tile order) copied to the host (after measures())."""
         return self._results("measures")
 
+    def select_mask(self, c: int):
+        """The keep mask of column c (tile order): a torch uint8 view of n_features bytes of the select buffer,
+        which select_predicate() writes and a caller may write instead (any non-zero byte keeps a feature)."""
+        self._buffers("select")
+        q = self.plan.select[c]
+        return self.d_select[int(q["off"]):int(q["off"]) + int(q["n_features"])]
+
+    def select_predicate(self, pred: "SelectPred", stream=None):
+        """Enqueue the predicate pass: every column's keep mask from its bounding boxes and, with a size cut,
+        its measures (after bbox() and measures() on the same stream); the window is in the boxes' space."""
+        for kind in ("bbox", "measures", "select"):
+            self._buffers(kind)
+        _raise(lib().covt_select_predicate_device(self.d_bdesc.data_ptr(), self.d_bbox.data_ptr(),
+                                                  self.d_bres.data_ptr(), self.d_mdesc.data_ptr(),
+                                                  self.d_measures.data_ptr(), self.d_mres.data_ptr(),
+                                                  self.d_sdesc.data_ptr(), self.plan.num_geometry_columns,
+                                                  C.byref(pred), self.d_select.data_ptr(),
+                                                  _stream(stream, self.device)), "covt_select_predicate_device")
+
+    def select(self, stream=None):
+        """Enqueue the selection: every column's selection vector and compacted WKB from its keep mask (after
+        wkb() and select_predicate(), or the caller's own masks, on the same stream)."""
+        self._buffers("wkb")
+        self._buffers("select")
+        _raise(lib().covt_geometry_select_device(self.d_wdesc.data_ptr(), self.d_wkb.data_ptr(), self.d_wres.data_ptr(),
+                                                 self.d_sdesc.data_ptr(), self.plan.num_geometry_columns,
+                                                 self.d_select.data_ptr(), self.d_sres.data_ptr(),
+                                                 _stream(stream, self.device)), "covt_geometry_select_device")
+
+    def select_results(self):
+        """(select bytes, results in tile order) copied to the host (after select()); see Plan.select_column."""
+        return self._results("select")
+
     def materialize_properties(self, stream=None):
         """Enqueue the property-column materialization (after decode() on the same stream)."""
         self._buffers("property")
@@ -1171,6 +1283,7 @@ class DevicePlan:
         self.wkb_bytes = lib().covt_device_plan_wkb_bytes(self._h)
         self.bbox_bytes = lib().covt_device_plan_bbox_bytes(self._h)
         self.measures_bytes = lib().covt_device_plan_measures_bytes(self._h)
+        self.select_bytes = lib().covt_device_plan_select_bytes(self._h)
         return self.num_geometry_columns
 
     def geometry_copy(self):
@@ -1253,6 +1366,24 @@ class DevicePlan:
         _raise(lib().covt_device_plan_measures(self._h, d_out.data_ptr(), d_asm.data_ptr(), d_gres.data_ptr(),
                                                d_measures.data_ptr(), d_mres.data_ptr(),
                                                _stream(stream, self.device)), "covt_device_plan_measures")
+
+
+    def select_copy(self):
+        """(select records in tile order, descriptors in launch order) as host arrays (Plan.select /
+        Plan.sdescs)."""
+        return self._copy("select", "covt_device_plan_select_copy")
+
+    def alloc_select(self):
+        """(select buffer, results) on the device, sized for this plan's geometry columns."""
+        return self._alloc("select")
+
+    def select(self, d_wkb, d_wres, d_select, d_sres, stream=None):
+        """Enqueue the selection over this plan's descriptors (after wkb() and whatever wrote the masks into
+        d_select on the same stream)."""
+        self.geometry(stream)
+        _raise(lib().covt_device_plan_select(self._h, d_wkb.data_ptr(), d_wres.data_ptr(), d_select.data_ptr(),
+                                             d_sres.data_ptr(), _stream(stream, self.device)),
+               "covt_device_plan_select")
 
 
 class DeviceSubset:
@@ -1384,6 +1515,18 @@ class MeasuresColumn:
 
 
 @dataclass
+class SelectedColumn:
+    """The kept features of one geometry column (include/covt.h "Feature selection"): index, the int32 feature
+    numbers in increasing order, and wkb, their WKB values as a column of their own.  The ids, boxes, measures and
+    property values of the kept features are array[index]."""
+    index: np.ndarray
+    wkb: WkbColumn
+
+    def __len__(self) -> int:
+        return int(self.index.size)
+
+
+@dataclass
 class PropertyColumn:
     """One materialized property (sub)column (include/covt.h "Property columns"): Arrow-style validity
     bitmap (LSB first) + values at feature positions (BOOLEAN: bitmap; INT64: int64; FLOAT: float32;
@@ -1430,6 +1573,7 @@ class LayerColumns:
     bbox: Optional[BboxColumn] = None  # their bounding boxes, the bbox covering column beside wkb
     crs: int = CRS_TILE  # the CRS of wkb and bbox (geometry.vertexBuffer stays in tile pixels)
     measures: Optional["MeasuresColumn"] = None  # their area, length and num_coords, in tile pixels whatever the crs
+    selected: Optional["SelectedColumn"] = None  # decode_covt(select=...): the features the predicate keeps
 
 
 _GEOM_FIELD = {GEOMETRY_TYPES: "geometryTypes", GEOMETRY_OFFSETS: "geometryOffsets", PART_OFFSETS: "partOffsets",
@@ -1457,10 +1601,13 @@ def split_layers(plan: Plan, out: np.ndarray, res: np.ndarray, tile: int = 0) ->
 class CovtParser:
     @staticmethod
     def decode_covt(covt_buffer: bytes, fmt: int = FORMAT_GENC, id_mode: int = ID_FORMAT,
-                    properties: bool = False, tile_id=None, crs: int = CRS_TILE) -> List[LayerColumns]:
+                    properties: bool = False, tile_id=None, crs: int = CRS_TILE,
+                    select: Optional[SelectPred] = None) -> List[LayerColumns]:
         """CovtParser.decodeCovt (CovtParser.java:53-133) decoded on the GPU: Id + Geometry columns, and with
         ``properties`` every property column as a PropertyColumn (LayerColumns.properties, by name).
-        ``tile_id`` = (z, x, y) and ``crs`` give every layer's wkb / bbox in that CRS (LayerColumns.crs)."""
+        ``tile_id`` = (z, x, y) and ``crs`` give every layer's wkb / bbox in that CRS (LayerColumns.crs).
+        ``select``, a SelectPred whose window is in that CRS, gives every layer the features it keeps
+        (LayerColumns.selected: their numbers and their WKB values; the other columns are array[selected.index])."""
         if crs != CRS_TILE and tile_id is None:
             raise IllegalArgumentException("a CRS other than CRS_TILE needs the tile's (z, x, y)")
         geo = (crs, [tile_id]) if crs != CRS_TILE else (None, None)
@@ -1487,6 +1634,12 @@ class CovtParser:
                 lc = by_layer.get(int(plan.measures["layer"][c]))
                 if lc is not None and int(mres["status"][c]) == OK:  # (a failed column keeps measures = None)
                     lc.measures = plan.measures_column(mbuf, mres, c)
+            if select is not None:
+                sbuf, sres = plan.select_host(select, *geo)
+                for c in range(plan.num_geometry_columns):
+                    lc = by_layer.get(int(plan.select["layer"][c]))
+                    if lc is not None and int(sres["status"][c]) == OK:  # (a failed column keeps selected = None)
+                        lc.selected = plan.select_column(sbuf, sres, c)
         if properties and plan.num_property_columns:
             buf, pres = plan.properties_host()
             by_layer = {lc.layer: lc for lc in layers}
@@ -1508,11 +1661,12 @@ def version() -> str:
 # the files whose sha256 (in this order) the Makefile compiles into covt_version() as "src:<16 hex>"
 _BUILD_SOURCES = (  # the Makefile's SRC, then its HDR, one to one
     ("csrc/covt_decode.hip", "csrc/covt_assemble.hip", "csrc/covt_props.hip", "csrc/covt_plan_device.hip",
-     "csrc/covt_wkb.hip", "csrc/covt_bbox.hip", "csrc/covt_measures.hip", "csrc/covt_host.cpp")
+     "csrc/covt_wkb.hip", "csrc/covt_bbox.hip", "csrc/covt_measures.hip", "csrc/covt_select.hip",
+     "csrc/covt_host.cpp")
     + ("../include/covt.h", "csrc/covt_internal.h", "csrc/covt_wave.h", "csrc/covt_segscan.h", "csrc/covt_walk.h",
        "csrc/covt_props_plan.h",
        "csrc/covt_scratch.h", "csrc/covt_coop.h", "csrc/covt_wkb_plan.h", "csrc/covt_bbox_plan.h",
-       "csrc/covt_measures_plan.h", "csrc/covt_geo_plan.h", "csrc/covt_arena.h", "csrc/covt_split_plan.h",
+       "csrc/covt_measures_plan.h", "csrc/covt_select_plan.h", "csrc/covt_geo_plan.h", "csrc/covt_arena.h", "csrc/covt_split_plan.h",
        "csrc/covt_container.h"))
 
 

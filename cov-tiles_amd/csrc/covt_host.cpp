@@ -27,6 +27,7 @@
 #include "covt_wkb_plan.h"
 #include "covt_bbox_plan.h"
 #include "covt_measures_plan.h"
+#include "covt_select_plan.h"
 #include "covt_geo_plan.h"
 
 namespace {
@@ -592,6 +593,9 @@ struct covt_plan {
     std::vector<covt_measures_info> minfo;   // measures columns, tile order (one per geometry column)
     std::vector<covt_measures_desc> mdescs;  // launch order (that of gdescs)
     int64_t measures_bytes = 0;
+    std::vector<covt_select_info> sinfo;   // select columns, tile order (one per geometry column)
+    std::vector<covt_select_desc> sdescs;  // launch order (that of gdescs)
+    int64_t select_bytes = 0;
     std::vector<covt_prop_info> pinfo;   // property (sub)columns, tile order
     std::vector<uint16_t> pflags;        // their COVT_PROP_* flags
     std::vector<covt_prop_desc> pdescs;  // launch order: largest first
@@ -785,6 +789,20 @@ void plan_measures(covt_plan* p) {
         [](covt_measures_info& m, const covt_measures_desc& d) {
             m.off = d.off;
             m.ring_cap = d.ring_cap;
+        });
+}
+
+// Select columns (include/covt.h "Feature selection"): slices in a buffer of their own, the compacted bytes
+// sized by the column's WKB capacity (covt_select_plan.h).
+void plan_select(covt_plan* p) {
+    p->select_bytes = plan_geometry_product(
+        p, p->sinfo, p->sdescs,
+        [](const covt_geom_info& g, int64_t off, covt_select_desc& d) {
+            return select_column_layout(g.n_features, g.part_cap, g.ring_cap, g.coord_cap, (uint32_t)g.flags, off, d);
+        },
+        [](covt_select_info& r, const covt_select_desc& d) {
+            r.off = d.off;
+            r.byte_cap = d.byte_cap;
         });
 }
 
@@ -1437,6 +1455,7 @@ int covt_plan_create_opts(const uint8_t* bytes, const uint64_t* tile_offsets, co
     plan_wkb(p);
     plan_bbox(p);
     plan_measures(p);
+    plan_select(p);
     plan_property_layout(p);
     *out = p;
     return COVT_OK;
@@ -1921,6 +1940,75 @@ int covt_plan_bbox_projected_host(const covt_plan* p, const uint8_t* bytes, uint
                                  return covt_geometry_bbox_projected_device(d.gdesc, d.asm_buf, d.gres, bdesc, n, buf, bres,
                                                                             g.dev.as<covt_geo_xform>(), g.kinds, s);
                              });
+}
+
+int64_t covt_plan_select_bytes(const covt_plan* p) { return p ? p->select_bytes : 0; }
+int covt_plan_select_columns(const covt_plan* p, covt_select_info* out) { return copy_records(p ? &p->sinfo : nullptr, out); }
+int covt_plan_select_descs(const covt_plan* p, covt_select_desc* out) { return copy_records(p ? &p->sdescs : nullptr, out); }
+
+}  // extern "C"
+
+namespace {
+
+// a product the select pipeline computes on the way and keeps on the device: descriptors, buffer, results
+template <class Desc, class Res>
+struct DevProduct {
+    DevMem desc, buf, res;
+    int make(const std::vector<Desc>& descs, int64_t bytes, hipStream_t s) {
+        const size_t n = descs.size();
+        if (hipMalloc(&desc.p, std::max<size_t>(n, 1) * sizeof(Desc)) != hipSuccess ||
+            hipMalloc(&buf.p, (size_t)std::max<int64_t>(bytes, 16)) != hipSuccess ||
+            hipMalloc(&res.p, std::max<size_t>(n, 1) * sizeof(Res)) != hipSuccess)
+            return COVT_ERR_DEVICE;
+        if (n && hipMemcpyAsync(desc.p, descs.data(), n * sizeof(Desc), hipMemcpyHostToDevice, s) != hipSuccess)
+            return COVT_ERR_DEVICE;
+        return COVT_OK;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+// decode, assembly, WKB and bounding boxes in `crs`, measures if the predicate reads them, predicate, select
+int covt_plan_select_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, int32_t crs,
+                          const int32_t* tile_zxy, const covt_select_pred* pred, uint8_t* host_select,
+                          covt_select_result* host_sres) {
+    if (!p || !select_pred_valid(pred)) return COVT_ERR_INVALID_ARG;
+    GeoTable g;  // (this and the intermediate products outlive the pipeline's synchronize)
+    if (const int st = g.make(p, crs, tile_zxy)) return st;
+    DevProduct<covt_wkb_desc, covt_wkb_result> w;
+    DevProduct<covt_bbox_desc, covt_bbox_result> b;
+    DevProduct<covt_measures_desc, covt_measures_result> m;
+    return plan_product_host(
+        p, bytes, n_bytes, p->sinfo, p->sdescs, p->select_bytes, host_select, host_sres, true,
+        [&](const PlanDev& d, const covt_select_desc* sdesc, int64_t n, uint8_t* buf, covt_select_result* sres,
+            hipStream_t s) {
+            const bool size = (pred->flags & COVT_SELECT_MIN_SIZE) != 0;
+            int st = g.upload(s);
+            if (st == COVT_OK) st = w.make(p->wdescs, p->wkb_bytes, s);
+            if (st == COVT_OK) st = b.make(p->bdescs, p->bbox_bytes, s);
+            if (st == COVT_OK && size) st = m.make(p->mdescs, p->measures_bytes, s);
+            const covt_geo_xform* xf = g.dev.as<covt_geo_xform>();
+            if (st == COVT_OK)
+                st = covt_geometry_wkb_projected_device(d.out, d.gdesc, d.asm_buf, d.gres, w.desc.as<covt_wkb_desc>(), n,
+                                                        w.buf.as<uint8_t>(), w.res.as<covt_wkb_result>(), xf, g.kinds, s);
+            if (st == COVT_OK)
+                st = covt_geometry_bbox_projected_device(d.gdesc, d.asm_buf, d.gres, b.desc.as<covt_bbox_desc>(), n,
+                                                         b.buf.as<uint8_t>(), b.res.as<covt_bbox_result>(), xf, g.kinds, s);
+            if (st == COVT_OK && size)
+                st = covt_geometry_measures_device(d.out, d.gdesc, d.asm_buf, d.gres, m.desc.as<covt_measures_desc>(), n,
+                                                   m.buf.as<uint8_t>(), m.res.as<covt_measures_result>(), s);
+            if (st == COVT_OK)
+                st = covt_select_predicate_device(b.desc.as<covt_bbox_desc>(), b.buf.as<uint8_t>(),
+                                                  b.res.as<covt_bbox_result>(), m.desc.as<covt_measures_desc>(),
+                                                  m.buf.as<uint8_t>(), m.res.as<covt_measures_result>(), sdesc, n, pred,
+                                                  buf, s);
+            if (st == COVT_OK)
+                st = covt_geometry_select_device(w.desc.as<covt_wkb_desc>(), w.buf.as<uint8_t>(),
+                                                 w.res.as<covt_wkb_result>(), sdesc, n, buf, sres, s);
+            return st;
+        });
 }
 
 int64_t covt_plan_num_property_columns(const covt_plan* p) { return p ? (int64_t)p->pinfo.size() : 0; }

@@ -42,6 +42,7 @@
 #include "covt_wkb_plan.h"
 #include "covt_bbox_plan.h"
 #include "covt_measures_plan.h"
+#include "covt_select_plan.h"
 
 struct covt_device_plan {
     int dev = 0;
@@ -66,6 +67,9 @@ struct covt_device_plan {
     int64_t measures_bytes = 0;    // measures columns (likewise)
     covt_measures_info* d_minfo = nullptr;
     covt_measures_desc* d_mdesc = nullptr;
+    int64_t select_bytes = 0;      // select columns (likewise)
+    covt_select_info* d_sinfo = nullptr;
+    covt_select_desc* d_sdesc = nullptr;
     void* prop_arena = nullptr;    // property columns (COVT_PLAN_PROPERTIES): records, infos, descriptors
     void* scratch = nullptr;       // creation-time scratch (the property walk's record slots), freed on the way
     int64_t n_props = 0, prop_bytes = 0;
@@ -2165,6 +2169,17 @@ struct MeasuresProduct {  // covt_measures_plan.h
         m.ring_cap = d.ring_cap;
     }
 };
+struct SelectProduct {  // covt_select_plan.h
+    using Info = covt_select_info;
+    using Desc = covt_select_desc;
+    static __device__ int64_t layout(const covt_geom_info& g, int64_t off, Desc& d) {
+        return select_column_layout(g.n_features, g.part_cap, g.ring_cap, g.coord_cap, (uint32_t)g.flags, off, d);
+    }
+    static __device__ void fill(Info& r, const Desc& d) {
+        r.off = d.off;
+        r.byte_cap = d.byte_cap;
+    }
+};
 template <class P>
 __global__ void product_col_bytes(const covt_geom_info* __restrict__ ginfo, int64_t nc, int64_t* __restrict__ bytes) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2783,6 +2798,7 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     const ProductSlice<WkbProduct> a_wkb(L, m);
     const ProductSlice<BboxProduct> a_bbox(L, m);
     const ProductSlice<MeasuresProduct> a_measures(L, m);
+    const ProductSlice<SelectProduct> a_select(L, m);
     // the arena is the plan's only on success: a failed build frees it (a retry allocates afresh)
     StreamFree arena{nullptr, s};
     HIP_TRY(plan_malloc(&arena.q, L.bytes(), p->dev, s));
@@ -2793,7 +2809,7 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     uint32_t* v1 = a_v1.at(g);
     uint8_t* cscan = a_cs.at(g);
     HIP_TRY(hipMemsetAsync(colbytes, 0, (m + 1) * 8, s));
-    int64_t asm_bytes = 0, wkb_bytes = 0, bbox_bytes = 0, measures_bytes = 0;
+    int64_t asm_bytes = 0, wkb_bytes = 0, bbox_bytes = 0, measures_bytes = 0, select_bytes = 0;
     if (nc > 0) {
         geom_columns<<<(int)((ns + 255) / 256), 256, 0, s>>>(p->d_info, ns, p->format, gst, gpos, p->d_ginfo, colbytes);
         HIP_TRY(hipGetLastError());
@@ -2812,6 +2828,8 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
         st = plan_product(a_bbox, g, m, nc, p->d_ginfo, cscan, cscan_tmp, s, p->d_binfo, p->d_bdesc, &bbox_bytes);
     if (st == COVT_OK)
         st = plan_product(a_measures, g, m, nc, p->d_ginfo, cscan, cscan_tmp, s, p->d_minfo, p->d_mdesc, &measures_bytes);
+    if (st == COVT_OK)
+        st = plan_product(a_select, g, m, nc, p->d_ginfo, cscan, cscan_tmp, s, p->d_sinfo, p->d_sdesc, &select_bytes);
     if (st) return st;
     if (nc > 0) {
         HIP_TRY(hipMemcpyAsync(&asm_bytes, coloff + nc, 8, hipMemcpyDeviceToHost, s));
@@ -2825,6 +2843,7 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     p->wkb_bytes = wkb_bytes;
     p->bbox_bytes = bbox_bytes;
     p->measures_bytes = measures_bytes;
+    p->select_bytes = select_bytes;
     p->geo_built = true;
     return COVT_OK;
 }
@@ -2905,6 +2924,22 @@ int covt_device_plan_measures(covt_device_plan* p, const uint8_t* d_decoded, con
     if (st) return st;
     return covt_geometry_measures_device(d_decoded, p->d_gdesc, d_asm, d_gres, p->d_mdesc, p->n_geo, d_measures, d_mres,
                                          hip_stream);
+}
+
+int64_t covt_device_plan_select_bytes(const covt_device_plan* p) { return p && p->geo_built ? p->select_bytes : 0; }
+const covt_select_desc* covt_device_plan_select_descs_device(const covt_device_plan* p) {
+    return p && p->geo_built ? p->d_sdesc : nullptr;
+}
+int covt_device_plan_select_copy(const covt_device_plan* p, covt_select_info* infos, covt_select_desc* descs) {
+    if (!p || !p->geo_built) return COVT_ERR_INVALID_ARG;
+    return copy_to_host(p->n_geo, infos, p->d_sinfo, descs, p->d_sdesc);
+}
+int covt_device_plan_select(covt_device_plan* p, const uint8_t* d_wkb, const covt_wkb_result* d_wres, uint8_t* d_select,
+                            covt_select_result* d_sres, void* hip_stream) {
+    if (!p) return COVT_ERR_INVALID_ARG;
+    const int st = covt_device_plan_geometry(p, hip_stream);
+    if (st) return st;
+    return covt_geometry_select_device(p->d_wdesc, d_wkb, d_wres, p->d_sdesc, p->n_geo, d_select, d_sres, hip_stream);
 }
 
 int covt_device_plan_assemble(covt_device_plan* p, const uint8_t* d_decoded, const covt_stream_result* d_res,

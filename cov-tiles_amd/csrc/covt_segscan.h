@@ -1,5 +1,5 @@
 // covt_segscan.h -- what the per-column geometry products share on the device (covt_bbox.hip, covt_measures.hip;
-// covt_wkb.hip uses the precheck and the launch sizing): the clamped view of an assembled column, the status
+// covt_wkb.hip uses the precheck and the launch sizing, covt_select.hip those and the 64-ary search): the clamped view of an assembled column, the status
 // before any work, the workgroups per column, and the segmented inclusive reduction over a column's items.
 //
 // The reduction.  A column's items (coordinates) fall into consecutive segments (features, rings), segment s
@@ -114,14 +114,20 @@ __device__ __forceinline__ GeomCol geom_col(const covt_geom_desc& gd, const covt
     return c;
 }
 
-// the column's status before any work: the assembly's, then the layout's (too_large, off_ok: the product's
-// own descriptor; n_features: what it was planned for)
+// a product column's status before any work: that of the pass it reads (`upstream`), then the layout's
+// (too_large, off_ok: the descriptors' flags and offsets; n_ok: planned for the rows its input has)
+__device__ __forceinline__ int32_t product_precheck(int32_t upstream, bool too_large, bool off_ok, bool n_ok) {
+    if (upstream != COVT_OK) return upstream;
+    if (too_large || !off_ok) return COVT_ERR_INVALID_ARG;
+    return n_ok ? COVT_OK : COVT_ERR_INVALID_ARG;
+}
+
+// the same for a product of the assembly (too_large, off_ok: the product's own descriptor; n_features: what it
+// was planned for)
 __device__ __forceinline__ int32_t geom_product_precheck(const covt_geom_desc& gd, const covt_geom_result& gr,
                                                          bool too_large, bool off_ok, int32_t n_features) {
-    if (gr.status != COVT_OK) return gr.status;
-    if (((uint32_t)gd.flags & COVT_GEOM_TOO_LARGE) || too_large || !off_ok) return COVT_ERR_INVALID_ARG;
     const int32_t n = gd.in_off[0] >= 0 ? gd.in_len[0] : 0;  // the features the assembly walked
-    return n_features == n ? COVT_OK : COVT_ERR_INVALID_ARG;
+    return product_precheck(gr.status, ((uint32_t)gd.flags & COVT_GEOM_TOO_LARGE) || too_large, off_ok, n_features == n);
 }
 
 // the first i in [0, n] with start(i) >= x (start nondecreasing over [0, n)): the wave probes 64 evenly

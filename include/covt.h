@@ -675,6 +675,127 @@ int covt_plan_bbox_projected_host(const covt_plan* plan, const uint8_t* bytes, u
                                   const int32_t* tile_zxy, uint8_t* host_bbox, covt_bbox_result* host_bres);
 
 /* ---------------------------------------------------------------------------
+ * Feature selection: filtering the rows of a geometry column where the data is.  From a keep mask per feature
+ * the pass writes the selection vector and the compacted WKB column (an Arrow `binary` column of the kept
+ * values); a small predicate pass writes that mask from the bounding boxes and the measures (the viewport query
+ * "features whose box meets this window", the per-zoom size cut "drop what this zoom cannot show"), or the
+ * caller writes it.  Per geometry column one slice (16-byte aligned start) in the select buffer, every member
+ * starting 16-byte aligned:
+ *
+ *   mask[n_features] uint8 | sel[n_features] int32 | offsets[n_features + 1] int32 | bytes[byte_cap]
+ *
+ * byte_cap is the column's WKB byte_cap: the output never exceeds the input, so there is no capacity status.
+ * The input is the column's WKB column (wkb_offsets, wkb_bytes, covt_wkb_result).  With K = { f : mask[f] != 0 }
+ * (any non-zero byte keeps a feature) and k_0 < k_1 < ... its members:
+ *
+ *   sel[j] = k_j
+ *   offsets[0] = 0, offsets[j + 1] = offsets[j] + (wkb_offsets[k_j + 1] - wkb_offsets[k_j])
+ *   bytes[offsets[j] .. offsets[j + 1]) = WKB value k_j, unchanged
+ *   covt_select_result: n_selected = |K|, n_bytes = offsets[n_selected]
+ *
+ * Not written: sel[j] for j >= n_selected, offsets[j] for j > n_selected, bytes past n_bytes, and the mask (the
+ * pass's input).  Every output element is written exactly once and no atomics are used, so the same input
+ * gives the same bytes every time.  The fixed-width companions (ids, boxes, measures, property values) of the
+ * kept features are array[sel[0 .. n_selected)].
+ * Statuses: a column whose WKB result is not COVT_OK gets that status, n_selected 0, n_bytes 0 and nothing else
+ * of its slice written (COVT_GEOM_TOO_LARGE arrives this way as COVT_ERR_INVALID_ARG); a descriptor flagged
+ * COVT_SELECT_TOO_LARGE (set exactly where COVT_WKB_TOO_LARGE is) or whose n_features or byte_cap is not the WKB
+ * descriptor's -> COVT_ERR_INVALID_ARG, likewise.  wkb_offsets no WKB pass writes (not nondecreasing inside
+ * [0, covt_wkb_result.n_bytes]) are read clamped to that range, so no access leaves the two slices; if the kept
+ * lengths then sum past n_bytes the column gets COVT_ERR_COUNT_MISMATCH (n_selected 0, n_bytes 0, sel and
+ * offsets unspecified, no byte of `bytes` written).
+ *
+ * The predicate.  For feature f, with the column's bounding-box arrays xmin, ymin, xmax, ymax and its measures
+ * area, length:
+ *   xmin[f] is NaN (the feature has no coordinate): mask[f] = (flags & COVT_SELECT_KEEP_EMPTY) ? 1 : 0, and no
+ *     other test applies;
+ *   otherwise mask[f] = W && S, where
+ *   W = true without COVT_SELECT_WINDOW, else xmin[f] <= window[2] && xmax[f] >= window[0] &&
+ *       ymin[f] <= window[3] && ymax[f] >= window[1]   (window = xmin, ymin, xmax, ymax; closed intervals) &&
+ *       window[0] <= window[2] && window[1] <= window[3]   (an inverted window selects nothing, also of a box
+ *       that spans both its ends);
+ *   S = true without COVT_SELECT_MIN_SIZE, else area[f] >= min_area || length[f] >= min_length ||
+ *       (area[f] == 0.0 && length[f] == 0.0)   (features without extent, points for instance, are not judged
+ *       by size).
+ * Plain IEEE comparisons, so the mask is bit-exact against the same expressions anywhere.  The window is in
+ * whatever space the bounding-box buffer was computed in (tile pixels, or the CRS of the projected pass); the
+ * measures, and so min_area and min_length, are always tile pixels.  A column whose bounding-box result, or
+ * with COVT_SELECT_MIN_SIZE its measures result, is not COVT_OK, or whose bounding-box / measures descriptor
+ * does not have the select descriptor's n_features, gets an all-zero mask; the caller sees those statuses in
+ * the bounding-box and measures results.
+ * A NaN in window, min_area or min_length, an unknown flag bit or a wrong `size` makes a call return
+ * COVT_ERR_INVALID_ARG.
+ * Out of scope: compacted copies of the fixed-width columns (sel indexes them), clipping to the window,
+ * predicates over property values beyond a caller-written mask, any spatial index.
+ * ------------------------------------------------------------------------- */
+#define COVT_SELECT_TOO_LARGE 0x1 /* covt_select_desc.flags: set exactly where COVT_WKB_TOO_LARGE is */
+
+#define COVT_SELECT_WINDOW 0x1u     /* covt_select_pred.flags: keep features whose box meets `window` */
+#define COVT_SELECT_MIN_SIZE 0x2u   /* ... whose area or length reaches min_area / min_length (or has no extent) */
+#define COVT_SELECT_KEEP_EMPTY 0x4u /* ... and the features without a coordinate */
+
+/* One device-resident select column entry (24 bytes), parallel to covt_geom_desc (launch order). */
+typedef struct covt_select_desc {
+    int64_t off;      /* byte offset of the column's slice in the select buffer (16-byte aligned) */
+    int64_t byte_cap; /* bytes the slice's `bytes` member holds (= covt_wkb_desc.byte_cap) */
+    int32_t n_features, flags;
+} covt_select_desc;
+
+/* Per-column select result written by the kernels (16 bytes). */
+typedef struct covt_select_result {
+    int32_t status, n_selected; /* n_selected, n_bytes: 0 unless status is COVT_OK */
+    int64_t n_bytes;
+} covt_select_result;
+
+/* Host-visible select column record of a plan, in tile order (40 bytes); column c belongs to geometry column c
+ * (covt_geom_info). */
+typedef struct covt_select_info {
+    int32_t tile, layer, n_features, desc_index; /* desc_index: row in the launch-ordered descriptors */
+    int64_t off, byte_cap;
+    int32_t flags, reserved;
+} covt_select_info;
+
+/* The predicate of covt_select_predicate_device (56 bytes). */
+typedef struct covt_select_pred {
+    uint32_t size, flags; /* size: sizeof(covt_select_pred), set by covt_select_pred_init */
+    double window[4];     /* xmin, ymin, xmax, ymax, in the space of the bounding-box buffer */
+    double min_area, min_length; /* tile pixels */
+} covt_select_pred;
+void covt_select_pred_init(covt_select_pred* pred); /* size set, no flags, window and minima 0 */
+
+int64_t covt_plan_select_bytes(const covt_plan* plan); /* size of the select buffer */
+int covt_plan_select_columns(const covt_plan* plan, covt_select_info* out); /* tile order, num_geometry_columns */
+int covt_plan_select_descs(const covt_plan* plan, covt_select_desc* out);   /* launch order (= covt_plan_geometry_descs) */
+
+/* The masks of every column on `hip_stream`, after the bounding-box pass (and with COVT_SELECT_MIN_SIZE the
+ * measures pass) on the same stream: d_bdesc / d_bbox / d_bres and d_mdesc / d_measures / d_mres those passes'
+ * descriptors, buffers and results (the measures' three may be null without COVT_SELECT_MIN_SIZE), d_sdesc the
+ * select descriptors (same order), `pred` in host memory (read before the call returns), d_select the select
+ * buffer of covt_plan_select_bytes bytes, 16-byte aligned.  Asynchronous, no scratch, capturable. */
+int covt_select_predicate_device(const covt_bbox_desc* d_bdesc, const uint8_t* d_bbox, const covt_bbox_result* d_bres,
+                                 const covt_measures_desc* d_mdesc, const uint8_t* d_measures,
+                                 const covt_measures_result* d_mres, const covt_select_desc* d_sdesc,
+                                 int64_t n_columns, const covt_select_pred* pred, uint8_t* d_select, void* hip_stream);
+
+/* Selection vectors and compacted WKB of every column on `hip_stream`, after the WKB pass and whatever wrote
+ * the masks on the same stream (a caller may write its own masks into the slices, from a property column for
+ * instance): d_wdesc / d_wkb / d_wres the WKB pass's descriptors, buffer and results, d_sdesc the select
+ * descriptors (same order), d_select the select buffer (16-byte aligned), d_sres n_columns results (same
+ * order).  A scan of (kept count, kept bytes), then a gather copy over the output bytes.  Asynchronous, no
+ * scratch, capturable. */
+int covt_geometry_select_device(const covt_wkb_desc* d_wdesc, const uint8_t* d_wkb, const covt_wkb_result* d_wres,
+                                const covt_select_desc* d_sdesc, int64_t n_columns, uint8_t* d_select,
+                                covt_select_result* d_sres, void* hip_stream);
+
+/* Convenience: H2D + decode + assembly + WKB and bounding boxes in `crs` (tile_zxy as covt_plan_geo_transforms;
+ * it may be null for COVT_CRS_TILE) + measures with COVT_SELECT_MIN_SIZE + predicate + select + D2H of the whole
+ * plan on the current device.  host_select: covt_plan_select_bytes bytes; host_sres: one result per column in
+ * tile order. */
+int covt_plan_select_host(const covt_plan* plan, const uint8_t* bytes, uint64_t n_bytes, int32_t crs,
+                          const int32_t* tile_zxy, const covt_select_pred* pred, uint8_t* host_select,
+                          covt_select_result* host_sres);
+
+/* ---------------------------------------------------------------------------
  * Property columns: the GPU replacement for
  * CovtParser.decodePropertyColumn (CovtParser.java:276-354) and getStringDictionary (:367-377).
  * A plan created with COVT_PLAN_PROPERTIES also plans every property column: its present / data /
@@ -884,6 +1005,17 @@ int covt_device_plan_measures_copy(const covt_device_plan* plan, covt_measures_i
 int covt_device_plan_measures(covt_device_plan* plan, const uint8_t* d_decoded, const uint8_t* d_asm,
                               const covt_geom_result* d_gres, uint8_t* d_measures, covt_measures_result* d_mres,
                               void* hip_stream);
+/* Select columns from a device plan: the records and descriptors of covt_plan_select_columns /
+ * covt_plan_select_descs, built on the device next to the measures records (covt_device_plan_geometry; the host
+ * plan's exactly); 0 / NULL before that call. */
+int64_t covt_device_plan_select_bytes(const covt_device_plan* plan);
+const covt_select_desc* covt_device_plan_select_descs_device(const covt_device_plan* plan);
+int covt_device_plan_select_copy(const covt_device_plan* plan, covt_select_info* infos, covt_select_desc* descs);
+/* covt_geometry_select_device over the plan's descriptors, after covt_device_plan_wkb and whatever wrote the
+ * masks on the same stream: d_select covt_device_plan_select_bytes bytes, d_sres one result per column in
+ * launch order (column c's at its covt_select_info.desc_index). */
+int covt_device_plan_select(covt_device_plan* plan, const uint8_t* d_wkb, const covt_wkb_result* d_wres,
+                            uint8_t* d_select, covt_select_result* d_sres, void* hip_stream);
 /* Property columns from a device plan made with COVT_PLAN_PROPERTIES in opts->flags: the records,
  * output layout and largest-first descriptors of covt_plan_property_columns / covt_plan_property_descs,
  * built on the device with the plan (the host plan's exactly); a plan without the flag has none. */
