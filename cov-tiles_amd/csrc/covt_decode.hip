@@ -1457,6 +1457,232 @@ __device__ __forceinline__ uint32_t xget(const Words& W, uint32_t xs, int k, uin
     const uint64_t m = k == 32 ? 0xffffffffull : ((1ull << k) - 1ull);
     return (uint32_t)(((lo | (hi << 32)) >> off) & m);
 }
+
+// ---- The pieces both FastPFOR decoders are built from (run_fastpfor: a per-block walk with prefetch;
+// run_fastpfor_stream: batched headers over a ring of packed words).  Word indices are 32-bit throughout
+// (byte_length is an int32_t: a stream holds < 2^29 words); only the directory cursor is 64-bit.
+
+// The stream head: truncation, then L = W[0] rounded down to whole blocks; W[1] rides along (one scalar-cache
+// line, one round trip; the input is padded past every stream).  Sets c.err.
+struct FpfStream {
+    Words W;
+    int32_t nw;       // the stream's words
+    uint32_t bsel;    // a stream word from the 4-byte grid: one v_perm_b32
+    uintptr_t s_end;  // the address past the stream's last word
+    int32_t L;        // the values held in pages
+    uint32_t head1;   // W[1], the first page's whereMeta
+};
+__device__ __forceinline__ FpfStream fpf_stream_head(Ctx& c) {
+    FpfStream s;
+    s.W = Words{c.sb, c.byte_length / 4};
+    s.nw = s.W.nw;
+    s.bsel = be_sel((uint32_t)((uintptr_t)c.sb & 3u));
+    s.s_end = (uintptr_t)c.sb + 4u * (uint32_t)s.nw;
+    s.L = 0;
+    s.head1 = 0u;
+    if (c.byte_length > c.avail) { c.err = COVT_ERR_TRUNCATED; }
+    if (!c.err && s.nw > 0) {
+        const uint32_t head0 = s.W.uniform(0);
+        s.head1 = s.W.uniform(1);
+        s.L = (int32_t)head0;
+        if (s.L < 0) c.err = COVT_ERR_BAD_HEADER;
+        s.L -= s.L % kFpfBlock;
+        if (!c.err && s.L > c.n) c.err = COVT_ERR_COUNT_MISMATCH;
+    }
+    return s;
+}
+
+// 1 KiB of stream words from word w on the 16-byte grid, byte-swapped into dst[]:
+// dst[m] = W(base + m) for m < 255, base = w - (0..3) returned; words at or past the stream's end
+// (nw) read as 0, as JavaFastPFOR's reads past its int[] do.  One 16-byte load per lane, by the
+// lanes whose 16 bytes start before the stream's last word ends (like win_load: a short stream's
+// window would otherwise fetch up to 1 KiB past it).  Issued and finished separately, so other
+// loads can be in flight between.
+struct FpfWords {
+    const uint8_t* sb;
+    int32_t nw;
+    uintptr_t s_end;
+    struct Raw {
+        uint4 r;
+        int32_t base;
+        uint32_t sh;
+    };
+    __device__ __forceinline__ Raw issue(int32_t w) const {
+        const uintptr_t addr = (uintptr_t)sb + 4u * (uint32_t)w;
+        const uintptr_t a16 = addr & ~(uintptr_t)15;
+        const uint32_t o = (uint32_t)(addr & 15u);
+        // lanes past the stream repeat the last granule (their words are zeroed by store): an
+        // unmasked load, so the compiler's vmcnt waits stay partial (a masked one drains every load)
+        const uint32_t lmax = s_end > a16 ? (uint32_t)((s_end - 1 - a16) >> 4) : 0u;
+        Raw q;
+        q.r = ld128_off((const g_u8*)a16, 16u * min((uint32_t)lane_id(), lmax));
+        q.base = uni(w - (int32_t)(o >> 2));
+        q.sh = o & 3u;
+        return q;
+    }
+    __device__ __forceinline__ int32_t store(uint32_t* dst, const Raw& q) const {
+        const int l = lane_id();
+        const uint32_t nx = lane_next(q.r.x);
+        const uint32_t sel = be_sel(q.sh);
+        const int32_t wl = q.base + 4 * l;  // stream word of dst[4 l]
+        uint4 wv;
+        wv.x = wl < nw ? be_word(q.r.y, q.r.x, sel) : 0u;
+        wv.y = wl + 1 < nw ? be_word(q.r.z, q.r.y, sel) : 0u;
+        wv.z = wl + 2 < nw ? be_word(q.r.w, q.r.z, sel) : 0u;
+        wv.w = wl + 3 < nw ? be_word(nx, q.r.w, sel) : 0u;
+        wave_sync();
+        ((uint4*)dst)[l] = wv;
+        wave_sync();
+        return q.base;
+    }
+    __device__ __forceinline__ int32_t load(uint32_t* dst, int32_t w) const { return store(dst, issue(w)); }
+};
+
+// The page's bytesize word, from its whereMeta word p0 (the first page's: head1).  false: c.err set.
+__device__ __forceinline__ bool fpf_page_meta(Ctx& c, const FpfStream& s, int32_t p0, int32_t& ie) {
+    if (p0 >= s.nw) { c.err = COVT_ERR_TRUNCATED; return false; }
+    const int64_t ie0 = (int64_t)p0 + (int32_t)(p0 == 1 ? s.head1 : s.W.uniform(p0));
+    if (ie0 < 0 || ie0 >= s.nw) { c.err = COVT_ERR_TRUNCATED; return false; }
+    ie = (int32_t)ie0;
+    return true;
+}
+
+// The directory's word reader (fpf_directory): from the meta window (cbuf: words [mw0, mw0 + 255)), or --
+// past it -- from 1 KiB windows of words staged in `spill`
+struct FpfDirWords {
+    const FpfWords& ld;
+    const uint32_t* cbuf;
+    int32_t mw0;
+    uint32_t* spill;
+    int32_t dbase = INT32_MIN / 2;
+    __device__ __forceinline__ uint32_t operator()(int64_t w64) {  // (w64 < nw: fpf_directory's bound)
+        const int32_t w = (int32_t)w64;
+        if (w >= mw0 && w < mw0 + 255) return uniu(cbuf[w - mw0]);
+        if (w < dbase || w >= dbase + 255) dbase = ld.load(spill, w);
+        return uniu(spill[w - dbase]);
+    }
+};
+
+// The fields of a block header word (container bytes cur, cur + 1, cur + 2 in bits 0.., 8.., 16..).
+// exceptions: index maxbits - b; 1 = the implicit 1 << b, 2..32 = dataTobePacked[idx] (a block without
+// exceptions gets 1, a valid index its exception code never reads)
+struct FpfFields {
+    int32_t b, ce, idx;  // bit width, exception count, maxbits - b
+    int32_t bcoff;       // container offset of the exception positions
+    int32_t next;        // container offset of the next block header
+};
+__device__ __forceinline__ FpfFields fpf_fields(uint32_t hw, int32_t cur) {
+    FpfFields f;
+    f.b = (int32_t)(int8_t)(hw & 0xffu);
+    f.ce = (int32_t)((hw >> 8) & 0xffu);
+    const int32_t hasx = f.ce > 0 ? 1 : 0;
+    f.idx = hasx ? (int32_t)(int8_t)((hw >> 16) & 0xffu) - f.b : 1;
+    f.bcoff = cur + 2 + hasx;
+    f.next = f.bcoff + f.ce;
+    return f;
+}
+// the header word at byte j of the staged container chunk
+__device__ __forceinline__ uint32_t fpf_header_word(const uint32_t* cbuf, int32_t j) {
+    return uniu(__builtin_amdgcn_alignbyte(cbuf[(j >> 2) + 1], cbuf[j >> 2], (uint32_t)j & 3u));
+}
+
+// Unpack: lane l -> values 4l..4l+3 of miniblock l/8; packed word i of the block at words[w0 + i]
+// (aligned, byte-swapped).  WRAP: words[] is the 512-word ring and the block passes its end.
+template <bool WRAP>
+__device__ __forceinline__ void fpf_unpack(const uint32_t* words, int32_t w0, int32_t b, uint32_t (&v)[4]) {
+    const int l = lane_id();
+    const uint32_t mask = b == 32 ? 0xffffffffu : ((1u << b) - 1u);
+    uint32_t bit = __umul24((uint32_t)(l & 7) * 4u, (uint32_t)b);
+    const int32_t wb = (int32_t)__umul24((uint32_t)(l >> 3), (uint32_t)b) + w0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int32_t wi = wb + (int32_t)(bit >> 5);
+        const uint32_t lo = words[WRAP ? wi & 511 : wi], hi = words[WRAP ? (wi + 1) & 511 : wi + 1];
+        v[k] = __builtin_amdgcn_alignbit(hi, lo, bit & 31u) & mask;
+        bit += (uint32_t)b;
+    }
+}
+
+// Value i of dataTobePacked[k] (start word xs): bits [xbit, xbit + k) of the word returned and the next.
+// (a 24-bit multiply: full rate, v_mul_lo_u32 is quarter rate; k <= 32, i < 2^24)
+__device__ __forceinline__ int32_t fpf_xword(int32_t k, uint32_t xs, uint32_t i, uint32_t& xbit) {
+    const uint32_t bit = __umul24(i, (uint32_t)k);
+    xbit = bit & 31u;
+    return (int32_t)(xs + (bit >> 5));
+}
+
+// Patch: out[pos] |= (index == 1 ? 1 : exceptvalue) << b for the block's ce exceptions, through the
+// patch[] scatter, then read back into the lane's four values.  k: the exception index (uniform), xs: its
+// array's start word (k >= 2), xcur: the array's cursor at this block.
+//   xpair(wi, el, lo, hi)  lane e's exception words wi, wi + 1 (el: the lane has an exception), swapped,
+//                          0 past the stream
+//   pos(q)                 the position of exception 64 q + lane
+template <class XPair, class Pos>
+__device__ __forceinline__ void fpf_patch(WaveSmem& sm, const Words& W, int32_t b, int32_t ce, int32_t k, uint32_t xs,
+                                          uint32_t xcur, XPair&& xpair, Pos&& pos, uint32_t (&v)[4]) {
+    const int l = lane_id();
+    const bool el = l < ce;
+    const uint32_t pos0 = pos(0);  // (every lane: an unmasked read)
+    uint32_t ex = 1u;
+    if (k != 1) {  // uniform
+        uint32_t xbit, lo, hi;
+        const int32_t wi = fpf_xword(k, xs, xcur + (uint32_t)l, xbit);
+        xpair(wi, el, lo, hi);
+        // bits [xbit, xbit + k) of hi:lo (xbit < 32, k <= 32)
+        const uint32_t m = k == 32 ? 0xffffffffu : ((1u << k) - 1u);
+        ex = __builtin_amdgcn_alignbit(hi, lo, xbit) & m;
+    }
+    // lanes without an exception OR 0 into their own slot: no branch, no conflict
+    atomicOr(&sm.u.f.patch[el ? pos0 : (uint32_t)(4 * l)], el ? ex << (b & 31) : 0u);
+    if (ce > 64) {  // rare: more than 64 exceptions in the block
+        for (int q = 1; q < 4; ++q) {
+            const int32_t e = l + 64 * q;
+            if (e < ce) {
+                const uint32_t ex2 = k == 1 ? 1u : xget(W, xs, k, xcur + (uint32_t)e);
+                atomicOr(&sm.u.f.patch[pos(q)], ex2 << (b & 31));
+            }
+        }
+    }
+    wave_sync();
+    const uint4 pt = ((const uint4*)sm.u.f.patch)[l];
+    v[0] |= pt.x;
+    v[1] |= pt.y;
+    v[2] |= pt.z;
+    v[3] |= pt.w;
+}
+
+// After the pages, for the range holding the stream's last value: the VariableByte tail over words [p, nw)
+// -- from the last page's meta window when the window holds it (words (4 vpos & ~15) / 4 .. nw - 1 staged in
+// cbuf from word mw0; cbuf lies past the varint window and most of its terminator list, so the window's
+// first load reads it before anything is overwritten) -- then the values the codec did not produce, which
+// stay 0 in Java's decompressedValues[] and are transformed too (`fill`), then the x,y op's count check.
+// sink(values, first value index, count): 1 value per lane.
+template <int OP, class Sink>
+__device__ __forceinline__ void fpf_tail_fill(Ctx& c, const FpfStream& s, int32_t p, int32_t mw0, bool fill, Sink&& sink) {
+    int32_t decoded = s.L;
+    if (!c.err && p < s.nw) {
+        int32_t vpos = 4 * p;
+        const int32_t base = s.L;
+        Win w;
+        w.valid = false;
+        const bool tail_in = s.L > 0 && ((vpos & ~15) >> 2) >= mw0 && s.nw - mw0 <= 255;
+        const int32_t got = varint_take<MODE_WORDREV, VAL_VB>(
+            *c.sm, c.sb, w, vpos, 4 * s.nw, c.n - s.L, true, c.err,
+            [&](const uint32_t (&lo)[1], const uint32_t (&hi)[1], int32_t vb, int32_t, int32_t count) {
+                sink(lo, (int64_t)base + vb, count);
+            },
+            0, nullptr, 0, tail_in ? c.sm->u.f.cbuf : nullptr, mw0);
+        decoded = s.L + got;
+    }
+    if (!c.err) {
+        for (int32_t b = decoded; fill && b < c.n; b += 64) {
+            const uint32_t vv[1] = {0};
+            sink(vv, (int64_t)b, c.n - b < 64 ? c.n - b : 64);
+        }
+        if (OP == COVT_OP_FPF_ZZ_DELTA_XY && (c.n & 1)) c.err = COVT_ERR_COUNT_MISMATCH;
+    }
+}
+
 // One FastPFOR block header walked out of the byte container (FastPFOR.decodePage loop body).
 struct FpfHdr {
     int32_t b, ce, idx;  // bit width, exception count, maxbits - b
@@ -1534,6 +1760,7 @@ struct FpfSkip {
     // directory (so the second pass neither re-walks earlier pages' directories nor this one's)
     int32_t pdone = -1, p_page, bytesize, ie_end;
     int xs, xz;
+    bool xin;  // (from the 64-bit directory end; ie_end is clamped to the stream)
 };
 template <int OP>
 __device__ __forceinline__ void run_fastpfor(Ctx& c, int32_t v0 = 0, int32_t v1 = INT32_MAX, Carry cr0 = Carry{0, 0},
@@ -1541,69 +1768,24 @@ __device__ __forceinline__ void run_fastpfor(Ctx& c, int32_t v0 = 0, int32_t v1 
                              Carry* fin = nullptr) {
     WaveSmem& sm = *c.sm;
     const int l = lane_id();
-    const Words W{c.sb, c.byte_length / 4};
-    const int64_t nw = W.nw;
+    const FpfStream S = fpf_stream_head(c);
+    const Words& W = S.W;
+    const int32_t nw32 = S.nw;
     const uint32_t sbmis = (uint32_t)((uintptr_t)c.sb & 15);  // stream base misalignment (uniform)
-    const uint32_t bsel = be_sel(sbmis & 3u);  // a stream word from the 4-byte grid: one v_perm_b32
+    const uint32_t bsel = S.bsel;
+    const uintptr_t s_end = S.s_end;
+    const int32_t L = S.L;
+    const FpfWords ld{c.sb, nw32, s_end};
     Carry cr = cr0;
     uint32_t ax = 0, ay = 0;                  // sum_only: per-lane sums
     const bool has_end = v1 >= c.n;           // this range holds the stream's last value
-    int32_t decoded = 0;
-    int32_t L = 0;
-    int64_t p = 1;
+    int32_t p = 1;
     int xs_v = 0, xz_v = -1, xc_v = 0;  // lane k: dataTobePacked[k] start word, size, values consumed
     FpfPre pre;                          // the first block's prefetch (its packed words: at the page start)
-    int64_t mw0 = 0;                     // stream word of cbuf[0] (the meta window)
+    int32_t mw0 = 0;                     // stream word of cbuf[0] (the meta window)
     bool xin = false;                    // the page's metadata fits the meta window
-    if (c.byte_length > c.avail) { c.err = COVT_ERR_TRUNCATED; }
-    if (!c.err && nw > 0) {
-        // W[0] (L) and W[1] (the first page's whereMeta) share one scalar-cache line: one round trip
-        const uint32_t head0 = W.uniform(0), head1 = W.uniform(1);  // (the input is padded past every stream)
-        L = (int32_t)head0;
-        if (L < 0) c.err = COVT_ERR_BAD_HEADER;
-        L -= L % kFpfBlock;
-        if (!c.err && L > c.n) c.err = COVT_ERR_COUNT_MISMATCH;
+    if (!c.err && nw32 > 0) {
         int32_t done = 0;
-        // 1 KiB of stream words from word w on the 16-byte grid, byte-swapped into dst[]:
-        // dst[m] = W(base + m) for m < 255, base = w - (0..3) returned; words at or past the stream's end
-        // (nw) read as 0, as JavaFastPFOR's reads past its int[] do.  One 16-byte load per lane, by the
-        // lanes whose 16 bytes start before the stream's last word ends (like win_load: a short stream's
-        // window would otherwise fetch up to 1 KiB past it).  Issued and finished separately, so other
-        // loads can be in flight between.
-        const uintptr_t s_end = (uintptr_t)(c.sb + 4 * nw);
-        struct WordsRaw {
-            uint4 r;
-            int64_t base;
-            uint32_t sh;
-        };
-        auto words_issue = [&](int64_t w) -> WordsRaw {
-            const uintptr_t addr = (uintptr_t)(c.sb + 4 * w);
-            const uintptr_t a16 = addr & ~(uintptr_t)15;
-            const uint32_t o = (uint32_t)(addr & 15u);
-            // lanes past the stream repeat the last granule (their words are zeroed by words_store): an
-            // unmasked load, so the compiler's vmcnt waits stay partial (a masked one drains every load)
-            const uint32_t lmax = s_end > a16 ? (uint32_t)((s_end - 1 - a16) >> 4) : 0u;
-            WordsRaw q;
-            q.r = ld128_off((const g_u8*)a16, 16u * min((uint32_t)l, lmax));
-            q.base = uni64(w - (int64_t)(o >> 2));
-            q.sh = o & 3u;
-            return q;
-        };
-        auto words_store = [&](uint32_t* dst, const WordsRaw& q) -> int64_t {
-            const uint32_t nx = lane_next(q.r.x);
-            const uint32_t sel = be_sel(q.sh);
-            const int64_t wl = q.base + 4 * l;  // stream word of dst[4 l]
-            uint4 wv;
-            wv.x = wl < nw ? be_word(q.r.y, q.r.x, sel) : 0u;
-            wv.y = wl + 1 < nw ? be_word(q.r.z, q.r.y, sel) : 0u;
-            wv.z = wl + 2 < nw ? be_word(q.r.w, q.r.z, sel) : 0u;
-            wv.w = wl + 3 < nw ? be_word(nx, q.r.w, sel) : 0u;
-            wave_sync();
-            ((uint4*)dst)[l] = wv;
-            wave_sync();
-            return q.base;
-        };
-        auto load_words = [&](uint32_t* dst, int64_t w) -> int64_t { return words_store(dst, words_issue(w)); };
         while (!c.err && done < L) {
             done = uni(done);
             const bool cached = skip && skip->pdone >= 0;
@@ -1613,10 +1795,9 @@ __device__ __forceinline__ void run_fastpfor(Ctx& c, int32_t v0 = 0, int32_t v1 
                 continue;
             }
             const int32_t thissize = uni((L - done) < kFpfPage ? (L - done) : kFpfPage);
-            const int64_t p0 = uni64(p);
-            if (p0 >= nw) { c.err = COVT_ERR_TRUNCATED; break; }
-            int64_t ie = p0 + (int32_t)(p0 == 1 ? head1 : W.uniform(p0));  // the page's bytesize word
-            if (ie < 0 || ie >= nw) { c.err = COVT_ERR_TRUNCATED; break; }
+            const int32_t p0 = uni(p);
+            int32_t ie;  // the page's bytesize word
+            if (!fpf_page_meta(c, S, p0, ie)) break;
             // One round trip for the page's metadata and its first block: the 1 KiB meta window from the
             // bytesize word (bytesize, the byte container, and for a small page the exception directory and
             // arrays too: 74 % of the bench batch's pages have <= 1 KiB of metadata) is staged in cbuf, and
@@ -1624,64 +1805,52 @@ __device__ __forceinline__ void run_fastpfor(Ctx& c, int32_t v0 = 0, int32_t v1 
             // yet known: every lane up to the stream's end) in flight beside it.
             // (issued for every page, also one decoded from a later block (a split chunk's first page, which
             // requests its first block again): a load under a branch makes the compiler drain every load)
-            const WordsRaw mq = words_issue(ie);
+            const FpfWords::Raw mq = ld.issue(ie);
             const bool spec = v0 <= done && v1 > done;  // the range starts at this page's first block
             {
                 const uintptr_t a16 = ((uintptr_t)c.sb + 4u * (uint32_t)(p0 + 1)) & ~(uintptr_t)15;
                 const uint32_t lmax = s_end > a16 ? (uint32_t)((s_end - 1 - a16) >> 4) : 0u;
                 pre.raw = ld128_off((const g_u8*)a16, 16u * min((uint32_t)l, lmax));
             }
-            mw0 = words_store(sm.u.f.cbuf, mq);
-            auto mword = [&](int64_t w) -> uint32_t { return uniu(sm.u.f.cbuf[w - mw0]); };
-            const int32_t bytesize = (int32_t)mword(ie++);  // (ie - mw0 <= 3)
-            if (bytesize < 0 || bytesize > kFpfBcCap) { c.err = COVT_ERR_BAD_HEADER; break; }
+            mw0 = ld.store(sm.u.f.cbuf, mq);
+            const int32_t bytesize = (int32_t)uniu(sm.u.f.cbuf[ie - mw0]);  // (ie - mw0 <= 3)
+            FpfContainer ct;
+            if ((c.err = fpf_page_container(bytesize, (int64_t)ie + 1, nw32, ct)) != 0) break;
             xc_v = 0;
-            const int64_t bcw = (bytesize + 3) / 4;
-            const int64_t bc = ie;
-            if (bc + bcw >= nw) { c.err = COVT_ERR_TRUNCATED; break; }
-            ie += bcw;
+            const int32_t bc = (int32_t)ct.bc;
             if (cached && done == skip->pdone) {
                 ie = skip->ie_end;
                 xs_v = skip->xs;
                 xz_v = skip->xz;
+                xin = skip->xin;
             } else {
-                // exception-array directory (bitmap, then size + packed words per set bit): from the meta
-                // window, or -- past it -- from 1 KiB LDS windows of words in stage; the arrays'
-                // start/size/cursor live in lanes 2..32 of VGPRs
-                int64_t dbase = INT64_MIN / 2;
-                auto dword = [&](int64_t w) -> uint32_t {
-                    if (w >= mw0 && w < mw0 + 255) return mword(w);
-                    if (w < dbase || w >= dbase + 255) dbase = load_words(sm.u.f.stage, w);
-                    return uniu(sm.u.f.stage[w - dbase]);
-                };
-                uint32_t bm = dword(ie++) & ~1u;  // bit k-1 set: dataTobePacked[k] present (k >= 2)
+                // exception-array directory: from the meta window, or -- past it -- from 1 KiB LDS windows of
+                // words in stage; the arrays' start/size/cursor live in lanes 2..32 of VGPRs.  Its cursor in
+                // 64-bit arithmetic (array sizes up to 2^31 - 1 move it far past the stream: caught by the
+                // next read's bound, or by the next page's), its end clamped to nw after
+                int64_t ie64 = ct.bc + ct.bclen / 4;
+                FpfDirWords dword{ld, sm.u.f.cbuf, mw0, sm.u.f.stage};
                 xs_v = 0;
                 xz_v = -1;
-                while (bm) {
-                    const int32_t k = __builtin_ctz(bm) + 1;
-                    bm &= bm - 1;
-                    if (ie >= nw) { c.err = COVT_ERR_TRUNCATED; break; }
-                    const int32_t size = (int32_t)dword(ie++);
-                    if (size < 0) { c.err = COVT_ERR_BAD_HEADER; break; }
-                    const int64_t groups = ((int64_t)size + 31) / 32;
-                    xs_v = l == k ? (int)(uint32_t)ie : xs_v;
+                c.err = fpf_directory(dword, nw32, ie64, [&](int32_t k, int64_t start, int32_t size) {
+                    xs_v = l == k ? (int)(uint32_t)start : xs_v;
                     xz_v = l == k ? size : xz_v;
-                    ie += groups * k;
-                    ie -= ((groups * 32 - size) * k) / 32;
-                }
+                });
                 if (c.err) break;
+                // the whole metadata section (container, directory, exception arrays) inside the meta window:
+                // the container walk never reloads it and exception values are read from it (no global loads)
+                xin = ie64 - mw0 <= 255;
+                ie = (int32_t)(ie64 < nw32 ? ie64 : (int64_t)nw32);  // (>= nw: the next page, or the tail, stops)
                 if (skip && v0 >= done && v0 < done + thissize) {  // the chunk's first page: kept for pass two
                     skip->pdone = done;
-                    skip->p_page = (int32_t)p0;
+                    skip->p_page = p0;
                     skip->bytesize = bytesize;
-                    skip->ie_end = (int32_t)ie;
+                    skip->ie_end = ie;
                     skip->xs = xs_v;
                     skip->xz = xz_v;
+                    skip->xin = xin;
                 }
             }
-            // the whole metadata section (container, directory, exception arrays) inside the meta window:
-            // the container walk never reloads it and exception values are read from it (no global loads)
-            xin = ie - mw0 <= 255;
             // lane 0 stands for "no exception array" in the header walk: an unbounded size (its cursor counts
             // the other blocks' exceptions, never read as one)
             xz_v = l == 0 ? INT32_MAX : xz_v;
@@ -1690,12 +1859,11 @@ __device__ __forceinline__ void run_fastpfor(Ctx& c, int32_t v0 = 0, int32_t v1 
             // blocks of this page holding values of [v0, v1)
             const int32_t jb0 = v0 > done ? min((v0 - done) / kFpfBlock, nblocks_page) : 0;
             const int32_t nblocks = v1 <= done ? 0 : uni(min(nblocks_page, (int32_t)(((int64_t)v1 - done + kFpfBlock - 1) / kFpfBlock)));
-            const int32_t nw32 = (int32_t)nw;
-            const int32_t bclen = uni((int32_t)(bcw * 4));
+            const int32_t bclen = uni(ct.bclen);
             const uint8_t* cb8 = (const uint8_t*)sm.u.f.cbuf;
-            int32_t cbase = (int32_t)(4 * (mw0 - bc));  // (the meta window holds the container's start)
+            int32_t cbase = 4 * (mw0 - bc);  // (the meta window holds the container's start)
             auto chunk_load = [&](int32_t at) {  // container bytes [cbase, cbase + 1020), cbase in (at - 16, at]
-                cbase = (int32_t)(4 * (load_words(sm.u.f.cbuf, bc + (at >> 2)) - bc));
+                cbase = 4 * (ld.load(sm.u.f.cbuf, bc + (at >> 2)) - bc);
             };
             // One block header (FastPFOR.decodePage loop body): all checks merged into one uniform test.
             // The chunk is (re)loaded so that the header and up to 255 exception positions are inside.
@@ -1703,15 +1871,8 @@ __device__ __forceinline__ void run_fastpfor(Ctx& c, int32_t v0 = 0, int32_t v1 
                 cur = uni(cur);
                 cbase = uni(cbase);
                 if (!xin && (uint32_t)(cur - cbase) > (uint32_t)(1020 - 260)) chunk_load(cur);
-                const int32_t j = cur - cbase;
-                const uint32_t hw =
-                    uniu(__builtin_amdgcn_alignbyte(sm.u.f.cbuf[(j >> 2) + 1], sm.u.f.cbuf[j >> 2], (uint32_t)j & 3u));
-                const int32_t b = (int32_t)(int8_t)(hw & 0xffu);
-                const int32_t ce = (int32_t)((hw >> 8) & 0xffu);
-                const int32_t hasx = ce > 0 ? 1 : 0;
-                // exceptions: index maxbits - b; 1 = the implicit 1 << b, 2..32 = dataTobePacked[idx] (a block
-                // without exceptions gets 1, a valid index its exception code never reads)
-                const int32_t idx = hasx ? (int32_t)(int8_t)((hw >> 16) & 0xffu) - b : 1;
+                const FpfFields f = fpf_fields(fpf_header_word(sm.u.f.cbuf, cur - cbase), cur);
+                const int32_t b = f.b, ce = f.ce, idx = f.idx;
                 const int32_t k = (uint32_t)(idx - 2) <= 30u ? idx : 0;  // lane 0: no array
                 const int32_t xsz = __builtin_amdgcn_readlane(xz_v, k);
                 const int32_t xc = __builtin_amdgcn_readlane(xc_v, k);
@@ -1719,21 +1880,14 @@ __device__ __forceinline__ void run_fastpfor(Ctx& c, int32_t v0 = 0, int32_t v1 
                 h.ce = ce;
                 h.idx = idx;
                 h.xcur = (uint32_t)xc;  // (read only for idx >= 2)
-                h.bcoff = cur + 2 + hasx;
-                h.next = h.bcoff + ce;
+                h.bcoff = f.bcoff;
+                h.next = f.next;
                 xc_v += l == k ? ce : 0;
                 // every check at once as the largest of differences that must not be positive (all operands
                 // far below 2^30): the bit width in [0, 32], the header and its exception positions inside
                 // the container, the index in [1, 32], the array holding ce more values
                 const int32_t worst = max(max(max(b - 32, -b), h.next - bclen), max(max(idx - 32, 1 - idx), xc + ce - xsz));
                 return worst > 0 ? COVT_ERR_BAD_HEADER : COVT_OK;
-            };
-            // (32-bit: a stream holds < 2^29 words)
-            auto xword = [&](int32_t k, uint32_t xs, uint32_t i, uint32_t& xbit) -> int32_t {
-                // 24-bit multiplies (full rate; v_mul_lo_u32 is quarter rate): k <= 32, i < 2^16
-                const uint32_t bit = __umul24(i & 31u, (uint32_t)k);
-                xbit = bit & 31u;
-                return (int32_t)(xs + __umul24(i >> 5, (uint32_t)k) + (bit >> 5));
             };
             auto prefetch = [&](const FpfHdr& hv, int32_t pkv, FpfPre& pr, int slot, bool raw = true) {
                 FpfHdr h;
@@ -1758,7 +1912,7 @@ __device__ __forceinline__ void run_fastpfor(Ctx& c, int32_t v0 = 0, int32_t v1 
                 const int32_t k = h.idx;
                 const uint32_t xs = k >= 2 ? (uint32_t)__builtin_amdgcn_readlane(xs_v, k) : 0u;
                 uint32_t xb;
-                const int32_t wx = xword(k >= 2 ? k : 2, xs, h.xcur + (uint32_t)l, xb);
+                const int32_t wx = fpf_xword(k >= 2 ? k : 2, xs, h.xcur + (uint32_t)l, xb);
                 const uint32_t xon = (uint32_t)(k >= 2) & (uint32_t)(l < h.ce) & (uint32_t)(wx < nw32);
                 // (a page whose metadata fits the meta window reads its exception words from LDS when the
                 // block is patched: no load here.  Reading them here into pr.x* would make the compiler drain
@@ -1794,15 +1948,10 @@ __device__ __forceinline__ void run_fastpfor(Ctx& c, int32_t v0 = 0, int32_t v1 
                     int32_t cur = 0, pkk = pk;
                     for (int32_t j = 0; j < jb0; ++j) {
                         if (!xin && (uint32_t)(cur - cbase) > (uint32_t)(1020 - 8)) chunk_load(cur);
-                        const int32_t jj = cur - cbase;
-                        const uint32_t hw = uniu(__builtin_amdgcn_alignbyte(sm.u.f.cbuf[(jj >> 2) + 1],
-                                                                            sm.u.f.cbuf[jj >> 2], (uint32_t)jj & 3u));
-                        const int32_t b = (int32_t)(int8_t)(hw & 0xffu);
-                        const int32_t ce = (int32_t)((hw >> 8) & 0xffu);
-                        const int32_t idx = (int32_t)(int8_t)((hw >> 16) & 0xffu) - b;
-                        pkk += 8 * b;
-                        xc_v += (ce > 0 && idx >= 2 && idx <= 32 && l == idx) ? ce : 0;
-                        cur += ce > 0 ? 3 + ce : 2;
+                        const FpfFields f = fpf_fields(fpf_header_word(sm.u.f.cbuf, cur - cbase), cur);
+                        pkk += 8 * f.b;
+                        xc_v += (f.idx >= 2 && f.idx <= 32 && l == f.idx) ? f.ce : 0;  // (ce == 0: idx 1)
+                        cur = f.next;
                         if (cur > bclen) { c.err = COVT_ERR_BAD_HEADER; break; }
                     }
                     cur0 = uni(cur);
@@ -1869,61 +2018,28 @@ __device__ __forceinline__ void run_fastpfor(Ctx& c, int32_t v0 = 0, int32_t v1 
                 COVT_PHASE(c, 2);
                 // unpack: lane l -> values 4l..4l+3 of miniblock l/8
                 uint32_t v[4];
-                {
-                    const uint32_t mask = b == 32 ? 0xffffffffu : ((1u << b) - 1u);
-                    uint32_t bit = __umul24((uint32_t)(l & 7) * 4u, (uint32_t)b);
-                    const int32_t wb = (int32_t)__umul24((uint32_t)(l >> 3), (uint32_t)b) + qoff;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int32_t wi = wb + (int32_t)(bit >> 5);
-                        const uint32_t lo = sm.u.f.stage[wi], hi = sm.u.f.stage[wi + 1];
-                        v[k] = __builtin_amdgcn_alignbit(hi, lo, bit & 31u) & mask;
-                        bit += (uint32_t)b;
-                    }
-                }
+                fpf_unpack<false>(sm.u.f.stage, qoff, b, v);
                 COVT_PHASE(c, 3);
 #if defined(COVT_ABL_NOEXC)  // ablation build: exceptions not applied
                 if (false) {
 #else
-                if (hc.ce > 0) {  // out[pos] |= (index == 1 ? 1 : exceptvalue) << b
+                if (hc.ce > 0) {
 #endif
                     const int32_t k = hc.idx;
                     const uint32_t xs = k >= 2 ? (uint32_t)__builtin_amdgcn_readlane(xs_v, k) : 0u;
-                    const bool el = l < hc.ce;
-                    uint32_t ex = 1u;
-                    if (k != 1) {  // uniform
-                        uint32_t xbit;
-                        const int32_t wi = xword(k, xs, hc.xcur + (uint32_t)l, xbit);
-                        uint32_t lo, hi;
-                        if (xin) {  // meta window: words already swapped, 0 past the stream
-                            const int32_t m = el ? wi - (int32_t)mw0 : 0;
-                            lo = sm.u.f.cbuf[m];
-                            hi = sm.u.f.cbuf[m + 1];
-                        } else {
-                            lo = wi < nw32 ? be_word(pc.x1, pc.x0, bsel) : 0u;  // words past the stream read as 0
-                            hi = wi + 1 < nw32 ? be_word(pc.x2, pc.x1, bsel) : 0u;
-                        }
-                        // bits [xbit, xbit + k) of hi:lo (xbit < 32, k <= 32)
-                        const uint32_t m = k == 32 ? 0xffffffffu : ((1u << k) - 1u);
-                        ex = __builtin_amdgcn_alignbit(hi, lo, xbit) & m;
-                    }
-                    // lanes without an exception OR 0 into their own slot: no branch, no conflict
-                    atomicOr(&sm.u.f.patch[el ? pc.pos : (uint32_t)(4 * l)], el ? ex << (b & 31) : 0u);
-                    if (hc.ce > 64) {  // rare: more than 64 exceptions in the block
-                        for (int q = 1; q < 4; ++q) {
-                            const int32_t e = l + 64 * q;
-                            if (e < hc.ce) {
-                                const uint32_t ex = k == 1 ? 1u : xget(W, xs, k, hc.xcur + (uint32_t)e);
-                                atomicOr(&sm.u.f.patch[sm.u.f.posx[slot][64 * (q - 1) + l]], ex << (b & 31));
+                    fpf_patch(
+                        sm, W, b, hc.ce, k, xs, hc.xcur,
+                        [&](int32_t wi, bool el, uint32_t& lo, uint32_t& hi) {
+                            if (xin) {  // meta window: words already swapped, 0 past the stream
+                                const int32_t m = el ? wi - mw0 : 0;
+                                lo = sm.u.f.cbuf[m];
+                                hi = sm.u.f.cbuf[m + 1];
+                            } else {  // the prefetched registers
+                                lo = wi < nw32 ? be_word(pc.x1, pc.x0, bsel) : 0u;  // words past the stream read as 0
+                                hi = wi + 1 < nw32 ? be_word(pc.x2, pc.x1, bsel) : 0u;
                             }
-                        }
-                    }
-                    wave_sync();
-                    const uint4 pt = ((const uint4*)sm.u.f.patch)[l];
-                    v[0] |= pt.x;
-                    v[1] |= pt.y;
-                    v[2] |= pt.z;
-                    v[3] |= pt.w;
+                        },
+                        [&](int q) -> uint32_t { return q == 0 ? pc.pos : sm.u.f.posx[slot][64 * (q - 1) + l]; }, v);
                 }
                 COVT_PHASE(c, 4);
 #if defined(COVT_ABL_NOSTORE)  // ablation build: every block's output to the same 1 KiB (L2-resident)
@@ -1957,34 +2073,12 @@ __device__ __forceinline__ void run_fastpfor(Ctx& c, int32_t v0 = 0, int32_t v1 
             p = ie;
             if (done >= v1) break;  // the range ends in this page
         }
-        decoded = L;
-        // VariableByte tail over words [p, nw): from the last page's meta window when the window holds it
-        // (words (4 vpos & ~15) / 4 .. nw - 1 staged in cbuf; cbuf lies past the varint window and most of
-        // its terminator list, so the window's first load reads it before anything is overwritten)
-        if (!c.err && has_end && p < nw) {
-            int32_t vpos = (int32_t)(4 * p);
-            const int32_t base = L;
-            Win w;
-            w.valid = false;
-            const bool tail_in = L > 0 && ((int64_t)(vpos & ~15) >> 2) >= mw0 && nw - mw0 <= 255;
-            const int32_t got = varint_take<MODE_WORDREV, VAL_VB>(
-                sm, c.sb, w, vpos, (int32_t)(4 * nw), c.n - L, true, c.err,
-                [&](const uint32_t (&lo)[1], const uint32_t (&hi)[1], int32_t vb, int32_t, int32_t count) {
-                    if (sum_only) sum_values<OP, 1>(lo, (int64_t)base + vb, count, ax, ay);
-                    else sink_values<OP, 1>(lo, (int64_t)base + vb, 0, count, c.nb, c.out, cr);
-                },
-                0, nullptr, 0, tail_in ? sm.u.f.cbuf : nullptr, (int32_t)mw0);
-            decoded = L + got;
-        }
     }
-    // values the codec did not produce stay 0 in Java's decompressedValues[]: transform them too
-    if (!c.err && has_end) {
-        for (int32_t b = decoded; !sum_only && b < c.n; b += 64) {
-            uint32_t vv[1] = {0};
-            sink_values<OP, 1>(vv, b, 0, c.n - b < 64 ? c.n - b : 64, c.nb, c.out, cr);
-        }
-        if (OP == COVT_OP_FPF_ZZ_DELTA_XY && (c.n & 1)) c.err = COVT_ERR_COUNT_MISMATCH;
-    }
+    if (has_end)  // (a sum-only pass has nothing to fill: zeros add nothing)
+        fpf_tail_fill<OP>(c, S, p, mw0, !sum_only, [&](const uint32_t (&vals)[1], int64_t base, int32_t count) {
+            if (sum_only) sum_values<OP, 1>(vals, base, count, ax, ay);
+            else sink_values<OP, 1>(vals, base, 0, count, c.nb, c.out, cr);
+        });
     COVT_PHASE(c, 7);
     c.consumed = c.byte_length;
     if (sum_only) {
@@ -2012,67 +2106,29 @@ template <int OP>
 __device__ __forceinline__ void run_fastpfor_stream(Ctx& c) {
     WaveSmem& sm = *c.sm;
     const int l = lane_id();
-    const Words W{c.sb, c.byte_length / 4};
-    const int32_t nw32 = W.nw;  // (32-bit word indices: a stream holds < 2^29 words)
-    const uint32_t bsel = be_sel((uint32_t)((uintptr_t)c.sb & 3u));  // a stream word from the 4-byte grid
+    const FpfStream S = fpf_stream_head(c);
+    const Words& W = S.W;
+    const int32_t nw32 = S.nw;
+    const uint32_t bsel = S.bsel;
+    const uintptr_t s_end = S.s_end;
+    const int32_t L = S.L;
+    const FpfWords ld{c.sb, nw32, s_end};
     Carry cr{0u, 0u};
-    int32_t decoded = 0;
-    int32_t L = 0;
     int32_t p = 1;
     int xs_v = 0, xz_v = -1, xc_v = 0;  // lane k: dataTobePacked[k] start word, size, values consumed
     int32_t mw0 = 0;                     // stream word of cbuf[0] (the meta window)
-    if (c.byte_length > c.avail) { c.err = COVT_ERR_TRUNCATED; }
     if (!c.err && nw32 > 0) {
-        const uint32_t head0 = W.uniform(0), head1 = W.uniform(1);
-        L = (int32_t)head0;
-        if (L < 0) c.err = COVT_ERR_BAD_HEADER;
-        L -= L % kFpfBlock;
-        if (!c.err && L > c.n) c.err = COVT_ERR_COUNT_MISMATCH;
         int32_t done = 0;
-        const uintptr_t s_end = (uintptr_t)c.sb + 4u * (uint32_t)nw32;
-        struct WordsRaw {
-            uint4 r;
-            int32_t base;
-            uint32_t sh;
-        };
-        auto words_issue = [&](int32_t w) -> WordsRaw {
-            const uintptr_t addr = (uintptr_t)c.sb + 4u * (uint32_t)w;
-            const uintptr_t a16 = addr & ~(uintptr_t)15;
-            const uint32_t o = (uint32_t)(addr & 15u);
-            const uint32_t lmax = s_end > a16 ? (uint32_t)((s_end - 1 - a16) >> 4) : 0u;
-            WordsRaw q;
-            q.r = ld128_off((const g_u8*)a16, 16u * min((uint32_t)l, lmax));
-            q.base = uni(w - (int32_t)(o >> 2));
-            q.sh = o & 3u;
-            return q;
-        };
-        auto words_store = [&](uint32_t* dst, const WordsRaw& q) -> int32_t {
-            const uint32_t nx = lane_next(q.r.x);
-            const uint32_t sel = be_sel(q.sh);
-            const int32_t wl = q.base + 4 * l;
-            uint4 wv;
-            wv.x = wl < nw32 ? be_word(q.r.y, q.r.x, sel) : 0u;
-            wv.y = wl + 1 < nw32 ? be_word(q.r.z, q.r.y, sel) : 0u;
-            wv.z = wl + 2 < nw32 ? be_word(q.r.w, q.r.z, sel) : 0u;
-            wv.w = wl + 3 < nw32 ? be_word(nx, q.r.w, sel) : 0u;
-            wave_sync();
-            ((uint4*)dst)[l] = wv;
-            wave_sync();
-            return q.base;
-        };
-        auto load_words = [&](uint32_t* dst, int32_t w) -> int32_t { return words_store(dst, words_issue(w)); };
         while (!c.err && done < L) {
             done = uni(done);
             const int32_t thissize = uni((L - done) < kFpfPage ? (L - done) : kFpfPage);
             const int32_t p0 = uni(p);
-            if (p0 >= nw32) { c.err = COVT_ERR_TRUNCATED; break; }
-            const int64_t ie0 = (int64_t)p0 + (int32_t)(p0 == 1 ? head1 : W.uniform(p0));  // the page's bytesize word
-            if (ie0 < 0 || ie0 >= nw32) { c.err = COVT_ERR_TRUNCATED; break; }
-            int32_t ie = (int32_t)ie0;
+            int32_t ie;  // the page's bytesize word
+            if (!fpf_page_meta(c, S, p0, ie)) break;
             // one round trip: the meta window (bytesize, byte container, small pages' directory and exception
             // arrays) and the first window of packed words, requested together (meta first: its wait does not
             // wait for the packed words)
-            const WordsRaw mq = words_issue(ie);
+            const FpfWords::Raw mq = ld.issue(ie);
             const uintptr_t pa = (uintptr_t)c.sb + 4u * (uint32_t)(p0 + 1);
             const uintptr_t A0 = pa & ~(uintptr_t)127;
             // last 16-byte granule of the stream relative to A0: lanes past it repeat it (unmasked loads)
@@ -2083,53 +2139,33 @@ __device__ __forceinline__ void run_fastpfor_stream(Ctx& c) {
             int32_t kst = 0;       // windows staged
             int32_t vend = wbase;  // stream words below vend are staged
             uint32_t prev63 = 0u;  // lane 63's last raw dword of the last staged window
-            mw0 = words_store(sm.u.f.cbuf, mq);
-            auto mword = [&](int32_t w) -> uint32_t { return uniu(sm.u.f.cbuf[w - mw0]); };
-            const int32_t bytesize = (int32_t)mword(ie++);
-            if (bytesize < 0 || bytesize > kFpfBcCap) { c.err = COVT_ERR_BAD_HEADER; break; }
+            mw0 = ld.store(sm.u.f.cbuf, mq);
+            FpfContainer ct;
+            c.err = fpf_page_container((int32_t)uniu(sm.u.f.cbuf[ie - mw0]), (int64_t)ie + 1, nw32, ct);
+            if (c.err) break;
             xc_v = 0;
-            const int32_t bcw = (bytesize + 3) / 4;
-            const int32_t bc = ie;
-            if (bc + bcw >= nw32) { c.err = COVT_ERR_TRUNCATED; break; }
-            ie += bcw;
+            const int32_t bc = (int32_t)ct.bc;
             // the directory in 64-bit arithmetic (array sizes up to 2^31 - 1 move the cursor far past the
             // stream: caught by the next read's bound, or by the next page's), its end clamped to nw after
-            int64_t ie64 = ie;
-            {
-                int32_t dbase = INT32_MIN / 2;
-                auto dword = [&](int32_t w) -> uint32_t {
-                    if (w >= mw0 && w < mw0 + 255) return mword(w);
-                    // (the ring is free until the first window is staged)
-                    if (w < dbase || w >= dbase + 255) dbase = load_words(sm.u.f.ring, w);
-                    return uniu(sm.u.f.ring[w - dbase]);
-                };
-                uint32_t bm = dword((int32_t)ie64++) & ~1u;
-                xs_v = 0;
-                xz_v = -1;
-                while (bm) {
-                    const int32_t k = __builtin_ctz(bm) + 1;
-                    bm &= bm - 1;
-                    if (ie64 >= nw32) { c.err = COVT_ERR_TRUNCATED; break; }
-                    const int32_t size = (int32_t)dword((int32_t)ie64++);
-                    if (size < 0) { c.err = COVT_ERR_BAD_HEADER; break; }
-                    const int64_t groups = ((int64_t)size + 31) / 32;
-                    xs_v = l == k ? (int)(uint32_t)ie64 : xs_v;
-                    xz_v = l == k ? size : xz_v;
-                    ie64 += groups * k;
-                    ie64 -= ((groups * 32 - size) * k) / 32;
-                }
-                if (c.err) break;
-            }
+            int64_t ie64 = ct.bc + ct.bclen / 4;
+            FpfDirWords dword{ld, sm.u.f.cbuf, mw0, sm.u.f.ring};  // (the ring is free until the first window is staged)
+            xs_v = 0;
+            xz_v = -1;
+            c.err = fpf_directory(dword, nw32, ie64, [&](int32_t k, int64_t start, int32_t size) {
+                xs_v = l == k ? (int)(uint32_t)start : xs_v;
+                xz_v = l == k ? size : xz_v;
+            });
+            if (c.err) break;
             const bool xin = ie64 - mw0 <= 255;  // the page's whole metadata sits in the meta window
             ie = (int32_t)(ie64 < nw32 ? ie64 : (int64_t)nw32);  // (>= nw: the next page, or the tail, stops)
             COVT_PHASE(c, 0);
             const int32_t nblocks = uni(thissize / kFpfBlock);
-            const int32_t bclen = uni((int32_t)(bcw * 4));
+            const int32_t bclen = uni(ct.bclen);
             const uint8_t* cb8 = (const uint8_t*)sm.u.f.cbuf;
             const g_u8* cbyte = (const g_u8*)(c.sb + 4u * (uint32_t)bc);  // container byte q: cbyte[q ^ 3]
-            int32_t cbase = (int32_t)(4 * (mw0 - bc));
+            int32_t cbase = 4 * (mw0 - bc);
             auto chunk_load = [&](int32_t at) {  // container bytes [cbase, cbase + 1020), cbase in (at - 16, at]
-                cbase = (int32_t)(4 * (load_words(sm.u.f.cbuf, bc + (at >> 2)) - bc));
+                cbase = 4 * (ld.load(sm.u.f.cbuf, bc + (at >> 2)) - bc);
             };
             // the next window of packed words: staged into the ring, the one after it requested
             bool fin = false;           // the current batch is the page's last (or fails)
@@ -2187,11 +2223,8 @@ __device__ __forceinline__ void run_fastpfor_stream(Ctx& c) {
                         nbat = g;
                         break;
                     }
-                    const int32_t q = cur - cbase;
-                    const uint32_t hw =
-                        uniu(__builtin_amdgcn_alignbyte(sm.u.f.cbuf[(q >> 2) + 1], sm.u.f.cbuf[q >> 2], (uint32_t)q & 3u));
-                    const int32_t ce = (int32_t)((hw >> 8) & 0xffu);
-                    const int32_t nx = cur + (ce > 0 ? 3 + ce : 2);
+                    const uint32_t hw = fpf_header_word(sm.u.f.cbuf, cur - cbase);
+                    const int32_t nx = fpf_fields(hw, cur).next;
                     if (!xin && g > 0 && nx - cbase > 1020) {  // its positions are past the chunk: a new batch
                         nbat = g;
                         break;
@@ -2209,10 +2242,9 @@ __device__ __forceinline__ void run_fastpfor_stream(Ctx& c) {
                 // (2) lane-parallel: fields, exception cursors (a prefix sum per exception width present),
                 // packed-word offsets, checks
                 const bool in = l < nbat;
-                const int32_t b_v = (int32_t)(int8_t)(hw_v & 0xffu);
-                const int32_t ce_v = (int32_t)((hw_v >> 8) & 0xffu);
+                const FpfFields f_l = fpf_fields(hw_v, cur_v);
+                const int32_t b_v = f_l.b, ce_v = f_l.ce, idx_v = f_l.idx;
                 const bool hasx = ce_v > 0;
-                const int32_t idx_v = hasx ? (int32_t)(int8_t)((hw_v >> 16) & 0xffu) - b_v : 1;
                 const bool arr_k = hasx && idx_v >= 2 && idx_v <= 32;  // exceptions from dataTobePacked[idx]
                 const bool arr = in && arr_k;
                 int32_t xcur_v = 0;
@@ -2303,7 +2335,7 @@ __device__ __forceinline__ void run_fastpfor_stream(Ctx& c) {
                 }
                 const uint32_t f_v = (uint32_t)(b_v & 0xff) | ((uint32_t)ce_v << 8) | ((uint32_t)(idx_v & 0xff) << 16) |
                                      ((uint32_t)xo_v << 24);
-                const int32_t bo_v = cur_v + (hasx ? 3 : 2);
+                const int32_t bo_v = f_l.bcoff;
                 auto rec = [&](int32_t g, Hdr& h) {
                     const uint32_t f = uniu((uint32_t)__builtin_amdgcn_readlane((int32_t)f_v, g));
                     h.b = (int32_t)(f & 0xffu);
@@ -2334,75 +2366,38 @@ __device__ __forceinline__ void run_fastpfor_stream(Ctx& c) {
                     // unpack: lane l -> values 4l..4l+3 of miniblock l/8, words from the ring
                     uint32_t v[4];
                     {
-                        const uint32_t mask = b == 32 ? 0xffffffffu : ((1u << b) - 1u);
-                        uint32_t bit = __umul24((uint32_t)(l & 7) * 4u, (uint32_t)b);
                         const int32_t r0 = (hc.pk - wbase) & 511;
-                        const int32_t wb = (int32_t)__umul24((uint32_t)(l >> 3), (uint32_t)b) + r0;
-                        if (r0 + 8 * b <= 511) {
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                const int32_t wi = wb + (int32_t)(bit >> 5);
-                                const uint32_t lo = sm.u.f.ring[wi], hi = sm.u.f.ring[wi + 1];
-                                v[k] = __builtin_amdgcn_alignbit(hi, lo, bit & 31u) & mask;
-                                bit += (uint32_t)b;
-                            }
-                        } else {  // the block wraps around the ring's end
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                const int32_t wi = wb + (int32_t)(bit >> 5);
-                                const uint32_t lo = sm.u.f.ring[wi & 511], hi = sm.u.f.ring[(wi + 1) & 511];
-                                v[k] = __builtin_amdgcn_alignbit(hi, lo, bit & 31u) & mask;
-                                bit += (uint32_t)b;
-                            }
-                        }
+                        if (r0 + 8 * b <= 511) fpf_unpack<false>(sm.u.f.ring, r0, b, v);
+                        else fpf_unpack<true>(sm.u.f.ring, r0, b, v);  // the block wraps around the ring's end
                     }
                     COVT_PHASE(c, 4);
-                    if (hc.ce > 0) {  // out[pos] |= (index == 1 ? 1 : exceptvalue) << b
-                        const int32_t k = hc.idx;
-                        const bool el = l < hc.ce;
-                        // exception e = lane: its position (container byte bcoff + e, inside the chunk: batch rule)
-                        const uint32_t pos = cb8[min(max(hc.bcoff - cbase + l, 0), 4 * 260 - 1)];
-                        uint32_t ex = 1u;
-                        if (k != 1) {  // uniform; k in [2, 32] (checked)
-                            const uint32_t xs = (uint32_t)__builtin_amdgcn_readlane(xs_v, k);
-                            // value i = xcur + e of dataTobePacked[k]: bits [i k, i k + k) of its words
-                            const uint32_t bb = __umul24(hc.xcur + (uint32_t)l, (uint32_t)k);
-                            const uint32_t xbit = bb & 31u;
-                            uint32_t lo, hi;
-                            if (xin) {  // meta window: words already swapped, 0 past the stream
-                                const int32_t m = el ? (int32_t)(xs + (bb >> 5)) - mw0 : 0;
-                                lo = sm.u.f.cbuf[m];
-                                hi = sm.u.f.cbuf[m + 1];
-                            } else if (hc.xo != 255) {  // the batch's gathered words
-                                const int32_t m = el ? hc.xo + (int32_t)(bb >> 5) - (int32_t)(__umul24(hc.xcur, (uint32_t)k) >> 5) : 0;
-                                lo = sm.u.f.xw[m];
-                                hi = sm.u.f.xw[m + 1];
-                            } else {  // (past xw: from memory)
-                                const int32_t wi = (int32_t)(xs + (bb >> 5));
-                                lo = el && wi < nw32 ? W(wi) : 0u;
-                                hi = el && wi + 1 < nw32 ? W(wi + 1) : 0u;
-                            }
-                            const uint32_t m = k == 32 ? 0xffffffffu : ((1u << k) - 1u);
-                            ex = __builtin_amdgcn_alignbit(hi, lo, xbit) & m;
-                        }
-                        atomicOr(&sm.u.f.patch[el ? pos : (uint32_t)(4 * l)], el ? ex << (b & 31) : 0u);
-                        if (hc.ce > 64) {  // rare: more than 64 exceptions in the block (positions from memory)
-                            const uint32_t xs = k >= 2 ? (uint32_t)__builtin_amdgcn_readlane(xs_v, k) : 0u;
-                            for (int q = 1; q < 4; ++q) {
-                                const int32_t e = l + 64 * q;
-                                if (e < hc.ce) {
-                                    const uint32_t ex2 = k == 1 ? 1u : xget(W, xs, k, hc.xcur + (uint32_t)e);
-                                    const uint32_t ps = cbyte[(hc.bcoff + e) ^ 3];
-                                    atomicOr(&sm.u.f.patch[ps], ex2 << (b & 31));
+                    if (hc.ce > 0) {
+                        const int32_t k = hc.idx;  // (1, or in [2, 32]: checked)
+                        const uint32_t xs = k >= 2 ? (uint32_t)__builtin_amdgcn_readlane(xs_v, k) : 0u;
+                        fpf_patch(
+                            sm, W, b, hc.ce, k, xs, hc.xcur,
+                            [&](int32_t wi, bool el, uint32_t& lo, uint32_t& hi) {
+                                if (xin) {  // meta window: words already swapped, 0 past the stream
+                                    const int32_t m = el ? wi - mw0 : 0;
+                                    lo = sm.u.f.cbuf[m];
+                                    hi = sm.u.f.cbuf[m + 1];
+                                } else if (hc.xo != 255) {  // the batch's gathered words (from the block's first)
+                                    const int32_t w0 = (int32_t)(xs + (__umul24(hc.xcur, (uint32_t)k) >> 5));
+                                    const int32_t m = el ? hc.xo + wi - w0 : 0;
+                                    lo = sm.u.f.xw[m];
+                                    hi = sm.u.f.xw[m + 1];
+                                } else {  // (past xw: from memory)
+                                    lo = el && wi < nw32 ? W(wi) : 0u;
+                                    hi = el && wi + 1 < nw32 ? W(wi + 1) : 0u;
                                 }
-                            }
-                        }
-                        wave_sync();
-                        const uint4 pt = ((const uint4*)sm.u.f.patch)[l];
-                        v[0] |= pt.x;
-                        v[1] |= pt.y;
-                        v[2] |= pt.z;
-                        v[3] |= pt.w;
+                            },
+                            // exception e = lane: container byte bcoff + e, inside the chunk (batch rule); e >= 64
+                            // (rare): from memory
+                            [&](int q) -> uint32_t {
+                                return q == 0 ? cb8[min(max(hc.bcoff - cbase + l, 0), 4 * 260 - 1)]
+                                              : cbyte[(hc.bcoff + l + 64 * q) ^ 3];
+                            },
+                            v);
                     }
                     COVT_PHASE(c, 5);
                     sink_values<OP, 4>(v, (int64_t)done + (int64_t)(jbat + g) * kFpfBlock, 0, kFpfBlock, c.nb, c.out, cr);
@@ -2418,31 +2413,10 @@ __device__ __forceinline__ void run_fastpfor_stream(Ctx& c) {
             done += thissize;
             p = ie;
         }
-        decoded = L;
-        // VariableByte tail over words [p, nw): from the last page's meta window when it holds them
-        if (!c.err && p < nw32) {
-            int32_t vpos = (int32_t)(4 * p);
-            const int32_t base = L;
-            Win w;
-            w.valid = false;
-            const bool tail_in = L > 0 && ((vpos & ~15) >> 2) >= mw0 && nw32 - mw0 <= 255;
-            const int32_t got = varint_take<MODE_WORDREV, VAL_VB>(
-                sm, c.sb, w, vpos, 4 * nw32, c.n - L, true, c.err,
-                [&](const uint32_t (&lo)[1], const uint32_t (&hi)[1], int32_t vb, int32_t, int32_t count) {
-                    sink_values<OP, 1>(lo, (int64_t)base + vb, 0, count, c.nb, c.out, cr);
-                },
-                0, nullptr, 0, tail_in ? sm.u.f.cbuf : nullptr, (int32_t)mw0);
-            decoded = L + got;
-        }
     }
-    // values the codec did not produce stay 0 in Java's decompressedValues[]: transform them too
-    if (!c.err) {
-        for (int32_t b = decoded; b < c.n; b += 64) {
-            uint32_t vv[1] = {0};
-            sink_values<OP, 1>(vv, b, 0, c.n - b < 64 ? c.n - b : 64, c.nb, c.out, cr);
-        }
-        if (OP == COVT_OP_FPF_ZZ_DELTA_XY && (c.n & 1)) c.err = COVT_ERR_COUNT_MISMATCH;
-    }
+    fpf_tail_fill<OP>(c, S, p, mw0, true, [&](const uint32_t (&vals)[1], int64_t base, int32_t count) {
+        sink_values<OP, 1>(vals, base, 0, count, c.nb, c.out, cr);
+    });
     COVT_PHASE(c, 7);
     c.consumed = c.byte_length;
 }

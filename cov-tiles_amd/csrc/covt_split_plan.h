@@ -201,8 +201,11 @@ COVT_SPLIT_HD inline int64_t split_grow_factor(int64_t total_cost, int32_t grow)
 
 // ---- The FastPFOR framing (JavaFastPFOR FastPFOR.decodePage, read exactly as run_fastpfor's pre-walk does) ----
 // Both planners walk a split stream's page directories and block headers for the chunks' start states and
-// must agree byte for byte.  They keep their own loops and cursor storage and share the parse below, a
-// template over a reader R of the stream's nw = byte_length / 4 words:
+// must agree byte for byte with each other and with the kernels.  The page grammar is stated once, here:
+// fpf_page_container and fpf_directory are the functions the two FastPFOR decoders of covt_decode.hip parse
+// a page with (their word reader: the LDS windows; their array callback: lane k's start and size), and
+// fpf_page_dir is the same two with no callback.  The planners keep their own loops and cursor storage over
+// fpf_page_dir and fpf_block_step, templates over a reader R of the stream's nw = byte_length / 4 words:
 //   uint32_t R::word(int64_t i)     big-endian word i
 //   uint64_t R::bytes8(int64_t i)   stream bytes [4 i, 4 i + 8), byte m in bits [8 m, 8 m + 8)
 // Nothing here reads a word outside [0, nw) (tests/split_plan feeds it every prefix of random words).
@@ -229,29 +232,53 @@ struct FpfPage {
     int64_t pk;     // the first block's packed word
     int64_t next;   // the word after the page's exception arrays
 };
+// The byte container of the page whose bytesize word reads `bytesize` and is followed by word `at`.
+// Returns COVT_OK, COVT_ERR_BAD_HEADER (a size outside [0, kFpfBcCap]) or COVT_ERR_TRUNCATED (the container
+// and the bitmap word after it do not fit the stream).
+struct FpfContainer {
+    int64_t bc;     // the container's first word
+    int32_t bclen;  // its bytes (whole words); the directory's bitmap word: bc + bclen / 4
+};
+COVT_SPLIT_HD inline int32_t fpf_page_container(int32_t bytesize, int64_t at, int64_t nw, FpfContainer& ct) {
+    if (bytesize < 0 || bytesize > kFpfBcCap) return COVT_ERR_BAD_HEADER;
+    const int64_t bcw = (bytesize + 3) / 4;
+    if (at + bcw >= nw) return COVT_ERR_TRUNCATED;
+    ct.bc = at;
+    ct.bclen = (int32_t)(bcw * 4);
+    return COVT_OK;
+}
+// The exception-array directory from its bitmap word ie (< nw) on: bit k - 1 set: dataTobePacked[k] present
+// (k >= 2), as its size word and then its values, 32 of them packed into k words.  word(i): big-endian word
+// i < nw; array(k, start, size): array k's first word and its values.  ie: left after the last array (it may
+// lie far past nw).  Returns COVT_OK, COVT_ERR_TRUNCATED (a size word at or past nw) or COVT_ERR_BAD_HEADER
+// (a negative size).
+template <class Word, class Array>
+COVT_SPLIT_HD inline int32_t fpf_directory(Word&& word, int64_t nw, int64_t& ie, Array&& array) {
+    uint32_t bm = word(ie++) & ~1u;
+    while (bm) {
+        const int32_t k = __builtin_ctz(bm) + 1;
+        bm &= bm - 1;
+        if (ie >= nw) return COVT_ERR_TRUNCATED;
+        const int32_t size = (int32_t)word(ie++);
+        if (size < 0) return COVT_ERR_BAD_HEADER;
+        const int64_t groups = ((int64_t)size + 31) / 32;
+        array(k, ie, size);
+        ie += groups * k - ((groups * 32 - size) * k) / 32;
+    }
+    return COVT_OK;
+}
 // the page whose whereMeta word is p0; false: the framing cannot be followed
 template <class R>
 COVT_SPLIT_HD inline bool fpf_page_dir(R& rd, int64_t nw, int64_t p0, FpfPage& pg) {
     if (p0 >= nw) return false;
     int64_t ie = p0 + (int32_t)rd.word(p0);
     if (ie < 0 || ie >= nw) return false;
-    const int32_t bytesize = (int32_t)rd.word(ie++);
-    if (bytesize < 0 || bytesize > kFpfBcCap) return false;
-    const int64_t bcw = (bytesize + 3) / 4;
-    pg.bc = ie;
-    if (pg.bc + bcw >= nw) return false;
-    ie += bcw;
-    uint32_t bm = rd.word(ie++) & ~1u;  // (bc + bcw < nw)
-    while (bm) {
-        const int32_t k = __builtin_ctz(bm) + 1;
-        bm &= bm - 1;
-        if (ie >= nw) return false;
-        const int32_t size = (int32_t)rd.word(ie++);
-        if (size < 0) return false;
-        const int64_t groups = ((int64_t)size + 31) / 32;
-        ie += groups * k - ((groups * 32 - size) * k) / 32;
-    }
-    pg.bclen = (int32_t)(bcw * 4);
+    FpfContainer ct;
+    if (fpf_page_container((int32_t)rd.word(ie), ie + 1, nw, ct) != COVT_OK) return false;
+    ie = ct.bc + ct.bclen / 4;
+    if (fpf_directory([&](int64_t i) { return rd.word(i); }, nw, ie, [](int32_t, int64_t, int32_t) {}) != COVT_OK) return false;
+    pg.bc = ct.bc;
+    pg.bclen = ct.bclen;
     pg.pk = p0 + 1;
     pg.next = ie;
     return true;
