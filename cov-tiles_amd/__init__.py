@@ -178,6 +178,16 @@ SELECT_INFO_DTYPE = np.dtype([("tile", np.int32), ("layer", np.int32), ("n_featu
 SELECT_TOO_LARGE = 0x1
 SELECT_WINDOW, SELECT_MIN_SIZE, SELECT_KEEP_EMPTY = 0x1, 0x2, 0x4
 assert SELECT_DESC_DTYPE.itemsize == 24 and SELECT_RESULT_DTYPE.itemsize == 16 and SELECT_INFO_DTYPE.itemsize == 40
+# geometry simplification (include/covt.h "Geometry simplification")
+SIMPLIFY_DESC_DTYPE = np.dtype([("off", np.int64), ("n_features", np.int32), ("flags", np.int32),
+                                ("part_cap", np.int32), ("ring_cap", np.int32), ("coord_cap", np.int32),
+                                ("reserved", np.int32)])
+SIMPLIFY_INFO_DTYPE = np.dtype([("tile", np.int32), ("layer", np.int32), ("n_features", np.int32),
+                                ("desc_index", np.int32), ("off", np.int64), ("flags", np.int32),
+                                ("part_cap", np.int32), ("ring_cap", np.int32), ("coord_cap", np.int32)])
+SIMPLIFY_TOO_LARGE = 0x1
+SIMPLIFY_MAX_SHIFT = 30
+assert SIMPLIFY_DESC_DTYPE.itemsize == 32 and SIMPLIFY_INFO_DTYPE.itemsize == 40
 # georeferenced geometry (include/covt.h "Georeferenced geometry")
 CRS_TILE, CRS_WEB_MERCATOR, CRS_CRS84 = 0, 1, 2
 GEO_IDENTITY, GEO_AFFINE, GEO_AFFINE_LAT = 0, 1, 2
@@ -274,13 +284,14 @@ _SIGNATURES = {
     **_sig(None, [_vp], "covt_plan_options_init", "covt_plan_destroy", "covt_device_plan_destroy"),
     **_sig(_i64, [_vp], "covt_plan_num_streams", "covt_plan_output_bytes", "covt_plan_num_descs",
            "covt_plan_num_geometry_columns", "covt_plan_assembly_bytes", "covt_plan_wkb_bytes", "covt_plan_bbox_bytes",
-           "covt_plan_measures_bytes", "covt_plan_select_bytes",
+           "covt_plan_measures_bytes", "covt_plan_select_bytes", "covt_plan_simplify_bytes",
            "covt_plan_num_property_columns", "covt_plan_property_bytes"),
     **_sig(_int, [_vp, _i64p, _i64p, _i64p], "covt_plan_totals", "covt_device_plan_totals"),
     **_sig(_int, [_vp, _vp], "covt_plan_streams", "covt_plan_descs", "covt_plan_geometry_columns",
            "covt_plan_geometry_descs", "covt_plan_wkb_columns", "covt_plan_wkb_descs", "covt_plan_bbox_columns",
            "covt_plan_bbox_descs", "covt_plan_measures_columns", "covt_plan_measures_descs", "covt_plan_select_columns",
-           "covt_plan_select_descs", "covt_plan_property_columns", "covt_plan_property_descs"),
+           "covt_plan_select_descs", "covt_plan_simplify_columns", "covt_plan_simplify_descs",
+           "covt_plan_simplified_geometry_descs", "covt_plan_property_columns", "covt_plan_property_descs"),
     **_sig(_int, [_vp, _i64p], "covt_plan_desc_streams", "covt_plan_family_counts", "covt_device_plan_family_counts"),
     "covt_plan_tile_status": (_int, [_vp, _i32p]),
     "covt_plan_release_device": (_int, [_vp]),
@@ -302,6 +313,12 @@ _SIGNATURES = {
     "covt_select_predicate_device": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "covt_geometry_select_device": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "covt_plan_select_host": (_int, [_vp, _u8p, _u64, _i32, _vp, _vp, _vp, _vp]),
+    # geometry simplification
+    "covt_plan_simplify_shifts": (_int, [_vp, _vp, _vp]),
+    "covt_geometry_simplify_device": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "covt_plan_simplify_host": (_int, [_vp, _u8p, _u64, _i32, _vp, _vp, _vp]),
+    "covt_plan_set_simplify": (_int, [_vp, _i32, _i32, _vp]),
+    "covt_device_plan_simplify": (_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     # georeferenced geometry
     "covt_geo_transform": (_int, [_i32, _i32, _i32, _i32, _i32, _vp]),
     "covt_plan_geometry_extents": (_int, [_vp, _vp]),
@@ -317,16 +334,17 @@ _SIGNATURES = {
     **_sig(_i64, [_vp], "covt_device_plan_num_streams", "covt_device_plan_num_descs", "covt_device_plan_output_bytes",
            "covt_device_plan_num_geometry_columns", "covt_device_plan_assembly_bytes", "covt_device_plan_wkb_bytes",
            "covt_device_plan_bbox_bytes", "covt_device_plan_measures_bytes", "covt_device_plan_select_bytes",
-           "covt_device_plan_num_property_columns", "covt_device_plan_property_bytes"),
+           "covt_device_plan_simplify_bytes", "covt_device_plan_num_property_columns", "covt_device_plan_property_bytes"),
     **_sig(_vp, [_vp], "covt_device_plan_descs_device", "covt_device_plan_streams_device",
            "covt_device_plan_tile_status_device", "covt_device_plan_order_device",
            "covt_device_plan_geometry_descs_device", "covt_device_plan_wkb_descs_device",
            "covt_device_plan_bbox_descs_device", "covt_device_plan_measures_descs_device", "covt_device_plan_select_descs_device",
+           "covt_device_plan_simplify_descs_device", "covt_device_plan_simplified_geometry_descs_device",
            "covt_device_plan_property_descs_device"),
     "covt_device_plan_copy": (_int, [_vp, _vp, _vp, _i32p]),
     **_sig(_int, [_vp, _vp, _vp], "covt_device_plan_geometry_copy", "covt_device_plan_wkb_copy",
            "covt_device_plan_bbox_copy", "covt_device_plan_measures_copy", "covt_device_plan_select_copy",
-           "covt_device_plan_property_copy"),
+           "covt_device_plan_simplify_copy", "covt_device_plan_property_copy"),
     "covt_device_plan_geometry": (_int, [_vp, _vp]),
     "covt_device_plan_decode": (_int, [_vp, _vp, _vp, _vp, _vp]),
     **_sig(_int, [_vp] * 6, "covt_device_plan_assemble", "covt_device_plan_bbox", "covt_device_plan_select"),
@@ -632,6 +650,9 @@ _PRODUCTS = {
     "select": _Product("num_geometry_columns", "select_bytes", "sdescs", "select", SELECT_INFO_DTYPE, SELECT_DESC_DTYPE,
                        SELECT_DESC_DTYPE.itemsize, SELECT_RESULT_DTYPE, ("int64", 2), False, True,
                        ("d_sdesc", "d_select", "d_sres")),
+    "simplify": _Product("num_geometry_columns", "simplify_bytes", "spdescs", "simplify", SIMPLIFY_INFO_DTYPE,
+                         SIMPLIFY_DESC_DTYPE, SIMPLIFY_DESC_DTYPE.itemsize, GEOM_RESULT_DTYPE, ("int32", 4), False, True,
+                         ("d_spdesc", "d_simplify", "d_sgres")),
     "property": _Product("num_property_columns", "property_bytes", "pdescs", "props", PROP_INFO_DTYPE, PROP_DESC_DTYPE,
                          PROP_DESC_DTYPE.itemsize, PROP_RESULT_DTYPE, ("int32", 2), True, False,
                          ("d_pdesc", "d_props", "d_pres")),
@@ -728,6 +749,16 @@ class Plan:
         if self.num_geometry_columns:
             L.covt_plan_select_columns(h, self.select.ctypes.data)
             L.covt_plan_select_descs(h, self.sdescs.ctypes.data)
+        # geometry simplification (include/covt.h "Geometry simplification"): one column per geometry column,
+        # and the geometry descriptors that name the simplified columns
+        self.simplify_bytes = int(L.covt_plan_simplify_bytes(h))
+        self.simplify = np.zeros(self.num_geometry_columns, dtype=SIMPLIFY_INFO_DTYPE)
+        self.spdescs = np.zeros(self.num_geometry_columns, dtype=SIMPLIFY_DESC_DTYPE)
+        self.sgdescs = np.zeros(self.num_geometry_columns * C.sizeof(GeomDesc), dtype=np.uint8)
+        if self.num_geometry_columns:
+            L.covt_plan_simplify_columns(h, self.simplify.ctypes.data)
+            L.covt_plan_simplify_descs(h, self.spdescs.ctypes.data)
+            L.covt_plan_simplified_geometry_descs(h, self.sgdescs.ctypes.data)
         # property columns (include/covt.h "Property columns"; plans made with PLAN_PROPERTIES)
         self.num_property_columns = int(L.covt_plan_num_property_columns(h))
         self.property_bytes = int(L.covt_plan_property_bytes(h))
@@ -882,6 +913,58 @@ class Plan:
         data = offs + a16(4 * (n + 1))
         return SelectedColumn(buf[sel:sel + 4 * k].view(np.int32),
                               WkbColumn(buf[offs:offs + 4 * (k + 1)].view(np.int32), buf[data:data + int(r["n_bytes"])]))
+
+    def _tile_shifts(self, shift):
+        """(uniform shift, per-tile int32 array or None) of a `shift` argument: an int or one per tile."""
+        if np.ndim(shift) == 0:
+            return int(shift), None
+        ts = np.ascontiguousarray(shift, dtype=np.int32)
+        if ts.shape != (self.n_tiles,):
+            raise IllegalArgumentException("shift must be an int or hold one entry per tile")
+        return 0, ts
+
+    def simplify_shifts(self, tile_shift) -> np.ndarray:
+        """covt_plan_simplify_shifts: per-tile shifts -> per-column shifts in launch order (int32)."""
+        _, ts = self._tile_shifts(np.asarray(tile_shift).reshape(-1))
+        out = np.zeros(self.num_geometry_columns, dtype=np.int32)
+        _raise(lib().covt_plan_simplify_shifts(self._h, ts.ctypes.data, out.ctypes.data), "covt_plan_simplify_shifts")
+        return out
+
+    def simplify_host(self, shift):
+        """H2D + decode + geometry assembly + simplification + D2H (covt_plan_simplify_host).  shift: the grid
+        is 2^shift tile pixels; an int, or one per tile.  Returns (uint8 simplify buffer, geometry
+        results[num_geometry_columns] in tile order); see simplified_arrays."""
+        s, ts = self._tile_shifts(shift)
+        buf = np.zeros(max(self.simplify_bytes, 1), dtype=np.uint8)
+        res = np.zeros(max(self.num_geometry_columns, 1), dtype=GEOM_RESULT_DTYPE)
+        _raise(lib().covt_plan_simplify_host(self._h, _ptr(self.blob, C.c_uint8), self.blob.size, s,
+                                             ts.ctypes.data if ts is not None else None, buf.ctypes.data,
+                                             res.ctypes.data), "covt_plan_simplify_host")
+        return buf[:self.simplify_bytes], res[:self.num_geometry_columns]
+
+    def simplified_arrays(self, buf: np.ndarray, gres: np.ndarray, c: int) -> "GeoArrowGeometry":
+        """Column c (tile order) of a simplify buffer -> GeoArrowGeometry (raises on its status)."""
+        q, r = self.simplify[c], gres[c]
+        _raise(int(r["status"]), "simplified column %d (tile %d, layer %d)" % (c, q["tile"], q["layer"]))
+        a16 = lambda x: (x + 15) & ~15  # noqa: E731  (covt_simplify_plan.h: every member padded to 16 bytes)
+        n = int(q["n_features"])
+        geo = int(q["off"])
+        part = geo + a16(4 * (n + 1))
+        ring = part + a16(4 * (int(q["part_cap"]) + 1))
+        xy = ring + a16(4 * (int(q["ring_cap"]) + 1))
+        seg = lambda o, k: buf[o:o + 4 * k].view(np.int32)  # noqa: E731
+        return GeoArrowGeometry(seg(geo, n + 1), seg(part, int(r["num_parts"]) + 1), seg(ring, int(r["num_rings"]) + 1),
+                                seg(xy, 2 * int(r["num_coords"])).reshape(-1, 2))
+
+    def set_simplify(self, shift):
+        """covt_plan_set_simplify: while set (an int, or one shift per tile), wkb_host, bbox_host, measures_host
+        and select_host read the simplified column; None unsets it (the default)."""
+        if shift is None:
+            _raise(lib().covt_plan_set_simplify(self._h, 0, 0, None), "covt_plan_set_simplify")
+            return
+        s, ts = self._tile_shifts(shift)
+        _raise(lib().covt_plan_set_simplify(self._h, 1, s, ts.ctypes.data if ts is not None else None),
+               "covt_plan_set_simplify")
 
     def properties_host(self):
         """H2D + decode + property materialization + D2H (covt_plan_properties_host).
@@ -1048,20 +1131,56 @@ class DeviceBatch:
             self._xf_host = table.copy()
         return self.d_xf.data_ptr(), int(kinds)
 
-    def wkb(self, stream=None, xf=None):
-        """Enqueue the WKB serialization of every assembled geometry column (after assemble() on the
-        same stream).  xf: the (table, kinds) pair of Plan.geo_transforms -> coordinates in its CRS."""
+    def simplify(self, shift, stream=None):
+        """Enqueue the geometry simplification of every assembled column (after assemble() on the same stream):
+        the grid is 2^shift tile pixels; shift an int, or one per tile."""
+        import torch
+
         self._buffers("geometry")
+        self._buffers("simplify")
+        s, ts = self.plan._tile_shifts(shift)
+        d_shift = None
+        if ts is not None:  # (kept on the batch: the launch reads it on the stream)
+            self.d_shift = d_shift = torch.from_numpy(self.plan.simplify_shifts(ts)).to(self.device)
+        if getattr(self, "d_sgdesc", None) is None:
+            self.d_sgdesc = torch.from_numpy(self.plan.sgdescs).to(self.device) if self.plan.num_geometry_columns else \
+                torch.zeros(C.sizeof(GeomDesc), dtype=torch.uint8, device=self.device)
+        _raise(lib().covt_geometry_simplify_device(
+            self.d_out.data_ptr(), self.d_gdesc.data_ptr(), self.d_asm.data_ptr(), self.d_gres.data_ptr(),
+            self.d_spdesc.data_ptr(), self.plan.num_geometry_columns, s,
+            d_shift.data_ptr() if d_shift is not None and d_shift.numel() else None, self.d_simplify.data_ptr(),
+            self.d_sgres.data_ptr(), _stream(stream, self.device)), "covt_geometry_simplify_device")
+
+    def simplify_results(self):
+        """(simplify bytes, geometry results in tile order) copied to the host (after simplify()); see
+        Plan.simplified_arrays."""
+        return self._results("simplify")
+
+    def _column_source(self, simplified: bool):
+        """(geometry descriptors, column buffer, geometry results) a product reads: the assembly's, or with
+        `simplified` the retargeted descriptors, the simplify buffer and its results (after simplify())."""
+        self._buffers("geometry")
+        if not simplified:
+            return self.d_gdesc.data_ptr(), self.d_asm.data_ptr(), self.d_gres.data_ptr()
+        if getattr(self, "d_sgdesc", None) is None:
+            raise IllegalArgumentException("simplified=True needs simplify() first")
+        return self.d_sgdesc.data_ptr(), self.d_simplify.data_ptr(), self.d_sgres.data_ptr()
+
+    def wkb(self, stream=None, xf=None, simplified: bool = False):
+        """Enqueue the WKB serialization of every assembled geometry column (after assemble() on the
+        same stream).  xf: the (table, kinds) pair of Plan.geo_transforms -> coordinates in its CRS.
+        simplified: of the simplified column (after simplify() on the same stream)."""
+        gdesc, col, gres = self._column_source(simplified)
         self._buffers("wkb")
         if xf is not None:
             d_xf, kinds = self._xf(xf)
             _raise(lib().covt_geometry_wkb_projected_device(
-                self.d_out.data_ptr(), self.d_gdesc.data_ptr(), self.d_asm.data_ptr(), self.d_gres.data_ptr(),
+                self.d_out.data_ptr(), gdesc, col, gres,
                 self.d_wdesc.data_ptr(), self.plan.num_geometry_columns, self.d_wkb.data_ptr(), self.d_wres.data_ptr(),
                 d_xf, kinds, _stream(stream, self.device)), "covt_geometry_wkb_projected_device")
             return
-        _raise(lib().covt_geometry_wkb_device(self.d_out.data_ptr(), self.d_gdesc.data_ptr(), self.d_asm.data_ptr(),
-                                              self.d_gres.data_ptr(), self.d_wdesc.data_ptr(),
+        _raise(lib().covt_geometry_wkb_device(self.d_out.data_ptr(), gdesc, col,
+                                              gres, self.d_wdesc.data_ptr(),
                                               self.plan.num_geometry_columns, self.d_wkb.data_ptr(),
                                               self.d_wres.data_ptr(), _stream(stream, self.device)),
                "covt_geometry_wkb_device")
@@ -1070,19 +1189,20 @@ class DeviceBatch:
         """(WKB bytes, WKB results in tile order) copied to the host (after wkb())."""
         return self._results("wkb")
 
-    def bbox(self, stream=None, xf=None):
+    def bbox(self, stream=None, xf=None, simplified: bool = False):
         """Enqueue the bounding boxes of every assembled geometry column (after assemble() on the same
-        stream).  xf: the (table, kinds) pair of Plan.geo_transforms -> boxes in its CRS."""
-        self._buffers("geometry")
+        stream).  xf: the (table, kinds) pair of Plan.geo_transforms -> boxes in its CRS.
+        simplified: of the simplified column (after simplify() on the same stream)."""
+        gdesc, col, gres = self._column_source(simplified)
         self._buffers("bbox")
         if xf is not None:
             d_xf, kinds = self._xf(xf)
             _raise(lib().covt_geometry_bbox_projected_device(
-                self.d_gdesc.data_ptr(), self.d_asm.data_ptr(), self.d_gres.data_ptr(), self.d_bdesc.data_ptr(),
+                gdesc, col, gres, self.d_bdesc.data_ptr(),
                 self.plan.num_geometry_columns, self.d_bbox.data_ptr(), self.d_bres.data_ptr(), d_xf, kinds,
                 _stream(stream, self.device)), "covt_geometry_bbox_projected_device")
             return
-        _raise(lib().covt_geometry_bbox_device(self.d_gdesc.data_ptr(), self.d_asm.data_ptr(), self.d_gres.data_ptr(),
+        _raise(lib().covt_geometry_bbox_device(gdesc, col, gres,
                                                self.d_bdesc.data_ptr(), self.plan.num_geometry_columns,
                                                self.d_bbox.data_ptr(), self.d_bres.data_ptr(),
                                                _stream(stream, self.device)), "covt_geometry_bbox_device")
@@ -1091,13 +1211,13 @@ class DeviceBatch:
         """(bounding-box bytes, results in tile order) copied to the host (after bbox())."""
         return self._results("bbox")
 
-    def measures(self, stream=None):
+    def measures(self, stream=None, simplified: bool = False):
         """Enqueue the measures (area, length, num_coords) of every assembled geometry column (after
-        assemble() on the same stream)."""
-        self._buffers("geometry")
+        assemble() on the same stream).  simplified: of the simplified column (after simplify())."""
+        gdesc, col, gres = self._column_source(simplified)
         self._buffers("measures")
-        _raise(lib().covt_geometry_measures_device(self.d_out.data_ptr(), self.d_gdesc.data_ptr(),
-                                                   self.d_asm.data_ptr(), self.d_gres.data_ptr(),
+        _raise(lib().covt_geometry_measures_device(self.d_out.data_ptr(), gdesc,
+                                                   col, gres,
                                                    self.d_mdesc.data_ptr(), self.plan.num_geometry_columns,
                                                    self.d_measures.data_ptr(), self.d_mres.data_ptr(),
                                                    _stream(stream, self.device)), "covt_geometry_measures_device")
@@ -1284,6 +1404,7 @@ class DevicePlan:
         self.bbox_bytes = lib().covt_device_plan_bbox_bytes(self._h)
         self.measures_bytes = lib().covt_device_plan_measures_bytes(self._h)
         self.select_bytes = lib().covt_device_plan_select_bytes(self._h)
+        self.simplify_bytes = lib().covt_device_plan_simplify_bytes(self._h)
         return self.num_geometry_columns
 
     def geometry_copy(self):
@@ -1384,6 +1505,31 @@ class DevicePlan:
         _raise(lib().covt_device_plan_select(self._h, d_wkb.data_ptr(), d_wres.data_ptr(), d_select.data_ptr(),
                                              d_sres.data_ptr(), _stream(stream, self.device)),
                "covt_device_plan_select")
+
+    def simplify_copy(self):
+        """(simplify records in tile order, descriptors in launch order) as host arrays (Plan.simplify /
+        Plan.spdescs)."""
+        return self._copy("simplify", "covt_device_plan_simplify_copy")
+
+    def alloc_simplify(self):
+        """(simplify buffer, geometry results) on the device, sized for this plan's geometry columns."""
+        return self._alloc("simplify")
+
+    def simplify(self, d_out, d_asm, d_gres, shift: int, d_simplify, d_sgres, stream=None, d_shift=None):
+        """Enqueue the simplification over this plan's descriptors (after assemble() on the same stream); d_out
+        is the decode output, which holds the GeometryTypes.  d_shift: an int32 device tensor with one shift per
+        column in launch order, instead of `shift` for all.  The products read the result through
+        simplified_geometry_descs_device()."""
+        self.geometry(stream)
+        _raise(lib().covt_device_plan_simplify(self._h, d_out.data_ptr(), d_asm.data_ptr(), d_gres.data_ptr(), int(shift),
+                                               d_shift.data_ptr() if d_shift is not None else None,
+                                               d_simplify.data_ptr(), d_sgres.data_ptr(), _stream(stream, self.device)),
+               "covt_device_plan_simplify")
+
+    def simplified_geometry_descs_device(self) -> int:
+        """Device address of the geometry descriptors that name the simplified columns (launch order)."""
+        self.geometry()
+        return lib().covt_device_plan_simplified_geometry_descs_device(self._h)
 
 
 class DeviceSubset:
@@ -1574,6 +1720,7 @@ class LayerColumns:
     crs: int = CRS_TILE  # the CRS of wkb and bbox (geometry.vertexBuffer stays in tile pixels)
     measures: Optional["MeasuresColumn"] = None  # their area, length and num_coords, in tile pixels whatever the crs
     selected: Optional["SelectedColumn"] = None  # decode_covt(select=...): the features the predicate keeps
+    simplified: Optional["GeoArrowGeometry"] = None  # decode_covt(simplify=shift): the simplified column
 
 
 _GEOM_FIELD = {GEOMETRY_TYPES: "geometryTypes", GEOMETRY_OFFSETS: "geometryOffsets", PART_OFFSETS: "partOffsets",
@@ -1602,12 +1749,14 @@ class CovtParser:
     @staticmethod
     def decode_covt(covt_buffer: bytes, fmt: int = FORMAT_GENC, id_mode: int = ID_FORMAT,
                     properties: bool = False, tile_id=None, crs: int = CRS_TILE,
-                    select: Optional[SelectPred] = None) -> List[LayerColumns]:
+                    select: Optional[SelectPred] = None, simplify: Optional[int] = None) -> List[LayerColumns]:
         """CovtParser.decodeCovt (CovtParser.java:53-133) decoded on the GPU: Id + Geometry columns, and with
         ``properties`` every property column as a PropertyColumn (LayerColumns.properties, by name).
         ``tile_id`` = (z, x, y) and ``crs`` give every layer's wkb / bbox in that CRS (LayerColumns.crs).
         ``select``, a SelectPred whose window is in that CRS, gives every layer the features it keeps
-        (LayerColumns.selected: their numbers and their WKB values; the other columns are array[selected.index])."""
+        (LayerColumns.selected: their numbers and their WKB values; the other columns are array[selected.index]).
+        ``simplify``, a shift, gives every layer's wkb, bbox, measures and selected from the column simplified to
+        the grid of 2^shift tile pixels, and that column as LayerColumns.simplified; None: no simplification."""
         if crs != CRS_TILE and tile_id is None:
             raise IllegalArgumentException("a CRS other than CRS_TILE needs the tile's (z, x, y)")
         geo = (crs, [tile_id]) if crs != CRS_TILE else (None, None)
@@ -1618,8 +1767,15 @@ class CovtParser:
         for lc in layers:
             lc.crs = crs
         if plan.num_geometry_columns:
-            wbuf, wres = plan.wkb_host(*geo)
             by_layer = {lc.layer: lc for lc in layers}
+            if simplify is not None:
+                plan.set_simplify(int(simplify))  # (the host products below read the simplified column)
+                sbuf, sgres = plan.simplify_host(int(simplify))
+                for c in range(plan.num_geometry_columns):
+                    lc = by_layer.get(int(plan.simplify["layer"][c]))
+                    if lc is not None and int(sgres["status"][c]) == OK:  # (a failed column keeps simplified = None)
+                        lc.simplified = plan.simplified_arrays(sbuf, sgres, c)
+            wbuf, wres = plan.wkb_host(*geo)
             for c in range(plan.num_geometry_columns):
                 lc = by_layer.get(int(plan.wkb["layer"][c]))
                 if lc is not None and int(wres["status"][c]) == OK:  # (a failed column keeps wkb = None)
@@ -1662,11 +1818,11 @@ def version() -> str:
 _BUILD_SOURCES = (  # the Makefile's SRC, then its HDR, one to one
     ("csrc/covt_decode.hip", "csrc/covt_assemble.hip", "csrc/covt_props.hip", "csrc/covt_plan_device.hip",
      "csrc/covt_wkb.hip", "csrc/covt_bbox.hip", "csrc/covt_measures.hip", "csrc/covt_select.hip",
-     "csrc/covt_host.cpp")
+     "csrc/covt_simplify.hip", "csrc/covt_host.cpp")
     + ("../include/covt.h", "csrc/covt_internal.h", "csrc/covt_wave.h", "csrc/covt_segscan.h", "csrc/covt_walk.h",
        "csrc/covt_props_plan.h",
        "csrc/covt_scratch.h", "csrc/covt_coop.h", "csrc/covt_wkb_plan.h", "csrc/covt_bbox_plan.h",
-       "csrc/covt_measures_plan.h", "csrc/covt_select_plan.h", "csrc/covt_geo_plan.h", "csrc/covt_arena.h", "csrc/covt_split_plan.h",
+       "csrc/covt_measures_plan.h", "csrc/covt_select_plan.h", "csrc/covt_simplify_plan.h", "csrc/covt_geo_plan.h", "csrc/covt_arena.h", "csrc/covt_split_plan.h",
        "csrc/covt_container.h"))
 
 

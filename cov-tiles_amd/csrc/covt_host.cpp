@@ -16,6 +16,7 @@
 #include <mutex>
 #include <numeric>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -28,6 +29,7 @@
 #include "covt_bbox_plan.h"
 #include "covt_measures_plan.h"
 #include "covt_select_plan.h"
+#include "covt_simplify_plan.h"
 #include "covt_geo_plan.h"
 
 namespace {
@@ -596,6 +598,12 @@ struct covt_plan {
     std::vector<covt_select_info> sinfo;   // select columns, tile order (one per geometry column)
     std::vector<covt_select_desc> sdescs;  // launch order (that of gdescs)
     int64_t select_bytes = 0;
+    std::vector<covt_simplify_info> spinfo;   // simplify columns, tile order (one per geometry column)
+    std::vector<covt_simplify_desc> spdescs;  // launch order (that of gdescs)
+    int64_t simplify_bytes = 0;
+    bool simplify_on = false;                 // covt_plan_set_simplify: the host conveniences read the simplified column
+    int32_t simplify_shift = 0;               //   its uniform shift, or
+    std::vector<int32_t> simplify_col_shift;  //   one per column in launch order (empty: uniform)
     std::vector<covt_prop_info> pinfo;   // property (sub)columns, tile order
     std::vector<uint16_t> pflags;        // their COVT_PROP_* flags
     std::vector<covt_prop_desc> pdescs;  // launch order: largest first
@@ -803,6 +811,22 @@ void plan_select(covt_plan* p) {
         [](covt_select_info& r, const covt_select_desc& d) {
             r.off = d.off;
             r.byte_cap = d.byte_cap;
+        });
+}
+
+// Simplify columns (include/covt.h "Geometry simplification"): slices in a buffer of their own, sized by the
+// geometry column's capacities (covt_simplify_plan.h).
+void plan_simplify(covt_plan* p) {
+    p->simplify_bytes = plan_geometry_product(
+        p, p->spinfo, p->spdescs,
+        [](const covt_geom_info& g, int64_t off, covt_simplify_desc& d) {
+            return simplify_column_layout(g.n_features, g.part_cap, g.ring_cap, g.coord_cap, (uint32_t)g.flags, off, d);
+        },
+        [](covt_simplify_info& r, const covt_simplify_desc& d) {
+            r.off = d.off;
+            r.part_cap = d.part_cap;
+            r.ring_cap = d.ring_cap;
+            r.coord_cap = d.coord_cap;
         });
 }
 
@@ -1456,6 +1480,7 @@ int covt_plan_create_opts(const uint8_t* bytes, const uint64_t* tile_offsets, co
     plan_bbox(p);
     plan_measures(p);
     plan_select(p);
+    plan_simplify(p);
     plan_property_layout(p);
     *out = p;
     return COVT_OK;
@@ -1751,6 +1776,9 @@ int plan_product_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes
     auto bytes_of = [](int64_t n) { return (size_t)std::max<int64_t>(n, 16); };
     auto rows_of = [](size_t n, size_t elem) { return std::max<size_t>(n, 1) * elem; };
     DevMem m_in, m_out, m_asm, m_buf, m_desc, m_res, m_gdesc, m_gres, m_pdesc, m_pres;
+    DevMem m_sbuf, m_sdesc, m_sgdesc, m_sgres, m_shift;  // covt_plan_set_simplify
+    // (the simplify product itself reads the assembled column)
+    const bool simplify = assemble_first && p->simplify_on && !std::is_same<Desc, covt_simplify_desc>::value;
     chk(hipMalloc(&m_in.p, (size_t)n_bytes + COVT_INPUT_PADDING));
     chk(hipMalloc(&m_out.p, bytes_of(p->out_bytes)));
     if (assemble_first) chk(hipMalloc(&m_asm.p, bytes_of(p->asm_bytes)));
@@ -1767,6 +1795,7 @@ int plan_product_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes
     const PlanDev dev{d_in, m_out.as<uint8_t>(), m_res.as<covt_stream_result>(), m_gdesc.as<covt_geom_desc>(),
                       m_asm.as<uint8_t>(), m_gres.as<covt_geom_result>()};
     std::vector<Res> res(nc);
+    std::vector<covt_geom_desc> rg;  // covt_plan_set_simplify: the retargeted geometry descriptors
     if (st == COVT_OK) {
         if (n_bytes) chk(hipMemcpyAsync(d_in, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, s));
         chk(hipMemsetAsync(d_in + n_bytes, 0, COVT_INPUT_PADDING, s));
@@ -1781,7 +1810,31 @@ int plan_product_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes
         if (st == COVT_OK && assemble_first)
             st = covt_assemble_geometry_device(dev.out, dev.res, dev.gdesc, (int64_t)ng, m_asm.as<uint8_t>(),
                                                m_gres.as<covt_geom_result>(), s);
-        if (st == COVT_OK) st = launch(dev, m_pdesc.as<Desc>(), (int64_t)nc, m_buf.as<uint8_t>(), m_pres.as<Res>(), s);
+        // covt_plan_set_simplify: the product reads the simplified column through the retargeted descriptors
+        PlanDev use = dev;
+        if (st == COVT_OK && simplify) {
+            rg.resize(ng);
+            for (size_t k = 0; k < ng; ++k) rg[k] = simplify_retarget(p->gdescs[k], p->spdescs[k]);
+            const std::vector<int32_t>& cs = p->simplify_col_shift;
+            chk(hipMalloc(&m_sbuf.p, bytes_of(p->simplify_bytes)));
+            chk(hipMalloc(&m_sdesc.p, rows_of(ng, sizeof(covt_simplify_desc))));
+            chk(hipMalloc(&m_sgdesc.p, rows_of(ng, sizeof(covt_geom_desc))));
+            chk(hipMalloc(&m_sgres.p, rows_of(ng, sizeof(covt_geom_result))));
+            chk(hipMalloc(&m_shift.p, rows_of(ng, sizeof(int32_t))));
+            if (st == COVT_OK && ng) {
+                chk(hipMemcpyAsync(m_sdesc.p, p->spdescs.data(), ng * sizeof(covt_simplify_desc), hipMemcpyHostToDevice, s));
+                chk(hipMemcpyAsync(m_sgdesc.p, rg.data(), ng * sizeof(covt_geom_desc), hipMemcpyHostToDevice, s));
+                if (!cs.empty()) chk(hipMemcpyAsync(m_shift.p, cs.data(), ng * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            }
+            if (st == COVT_OK)
+                st = covt_geometry_simplify_device(dev.out, dev.gdesc, dev.asm_buf, dev.gres, m_sdesc.as<covt_simplify_desc>(),
+                                                   (int64_t)ng, p->simplify_shift, cs.empty() ? nullptr : m_shift.as<int32_t>(),
+                                                   m_sbuf.as<uint8_t>(), m_sgres.as<covt_geom_result>(), s);
+            use.gdesc = m_sgdesc.as<covt_geom_desc>();
+            use.asm_buf = m_sbuf.as<uint8_t>();
+            use.gres = m_sgres.as<covt_geom_result>();
+        }
+        if (st == COVT_OK) st = launch(use, m_pdesc.as<Desc>(), (int64_t)nc, m_buf.as<uint8_t>(), m_pres.as<Res>(), s);
         if (st == COVT_OK && out_bytes)
             chk(hipMemcpyAsync(host_out, m_buf.p, (size_t)out_bytes, hipMemcpyDeviceToHost, s));
         if (st == COVT_OK && nc) chk(hipMemcpyAsync(res.data(), m_pres.p, nc * sizeof(Res), hipMemcpyDeviceToHost, s));
@@ -2008,6 +2061,69 @@ int covt_plan_select_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_b
                 st = covt_geometry_select_device(w.desc.as<covt_wkb_desc>(), w.buf.as<uint8_t>(),
                                                  w.res.as<covt_wkb_result>(), sdesc, n, buf, sres, s);
             return st;
+        });
+}
+
+int64_t covt_plan_simplify_bytes(const covt_plan* p) { return p ? p->simplify_bytes : 0; }
+int covt_plan_simplify_columns(const covt_plan* p, covt_simplify_info* out) { return copy_records(p ? &p->spinfo : nullptr, out); }
+int covt_plan_simplify_descs(const covt_plan* p, covt_simplify_desc* out) { return copy_records(p ? &p->spdescs : nullptr, out); }
+
+int covt_plan_simplified_geometry_descs(const covt_plan* p, covt_geom_desc* out) {
+    if (!p || (!out && !p->gdescs.empty())) return COVT_ERR_INVALID_ARG;
+    for (size_t k = 0; k < p->gdescs.size(); ++k) out[k] = simplify_retarget(p->gdescs[k], p->spdescs[k]);
+    return COVT_OK;
+}
+
+int covt_plan_simplify_shifts(const covt_plan* p, const int32_t* tile_shift, int32_t* out) {
+    if (!p || ((!tile_shift || !out) && !p->ginfo.empty())) return COVT_ERR_INVALID_ARG;
+    for (const covt_geom_info& g : p->ginfo) out[(size_t)g.desc_index] = tile_shift[(size_t)g.tile];
+    return COVT_OK;
+}
+
+int covt_plan_set_simplify(covt_plan* p, int32_t enabled, int32_t shift, const int32_t* tile_shift) {
+    if (!p) return COVT_ERR_INVALID_ARG;
+    if (!enabled) {
+        p->simplify_on = false;
+        p->simplify_col_shift.clear();
+        return COVT_OK;
+    }
+    std::vector<int32_t> cs;
+    if (tile_shift) {
+        for (int32_t t = 0; t < p->n_tiles; ++t)
+            if (!simplify_shift_valid(tile_shift[t])) return COVT_ERR_INVALID_ARG;
+        cs.resize(p->ginfo.size());
+        if (const int st = covt_plan_simplify_shifts(p, tile_shift, cs.data())) return st;
+    } else if (!simplify_shift_valid(shift)) {
+        return COVT_ERR_INVALID_ARG;
+    }
+    p->simplify_on = true;
+    p->simplify_shift = tile_shift ? 0 : shift;
+    p->simplify_col_shift.swap(cs);
+    return COVT_OK;
+}
+
+// decode, assembly, simplify
+int covt_plan_simplify_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, int32_t shift,
+                            const int32_t* tile_shift, uint8_t* host_simplify, covt_geom_result* host_gres) {
+    if (!p || (!tile_shift && !simplify_shift_valid(shift))) return COVT_ERR_INVALID_ARG;
+    std::vector<int32_t> cs;  // (this and its device copy outlive the pipeline's synchronize)
+    DevMem d_cs;
+    if (tile_shift) {
+        cs.resize(p->ginfo.size());
+        if (const int st = covt_plan_simplify_shifts(p, tile_shift, cs.data())) return st;
+    }
+    return plan_product_host(
+        p, bytes, n_bytes, p->spinfo, p->spdescs, p->simplify_bytes, host_simplify, host_gres, true,
+        [&](const PlanDev& d, const covt_simplify_desc* sdesc, int64_t n, uint8_t* buf, covt_geom_result* gres,
+            hipStream_t s) {
+            if (tile_shift) {
+                if (hipMalloc(&d_cs.p, std::max<size_t>(cs.size(), 1) * sizeof(int32_t)) != hipSuccess) return (int)COVT_ERR_DEVICE;
+                if (!cs.empty() &&
+                    hipMemcpyAsync(d_cs.p, cs.data(), cs.size() * sizeof(int32_t), hipMemcpyHostToDevice, s) != hipSuccess)
+                    return (int)COVT_ERR_DEVICE;
+            }
+            return covt_geometry_simplify_device(d.out, d.gdesc, d.asm_buf, d.gres, sdesc, n, shift,
+                                                 tile_shift ? d_cs.as<int32_t>() : nullptr, buf, gres, s);
         });
 }
 

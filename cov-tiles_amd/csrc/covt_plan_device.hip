@@ -43,6 +43,7 @@
 #include "covt_bbox_plan.h"
 #include "covt_measures_plan.h"
 #include "covt_select_plan.h"
+#include "covt_simplify_plan.h"
 
 struct covt_device_plan {
     int dev = 0;
@@ -70,6 +71,10 @@ struct covt_device_plan {
     int64_t select_bytes = 0;      // select columns (likewise)
     covt_select_info* d_sinfo = nullptr;
     covt_select_desc* d_sdesc = nullptr;
+    int64_t simplify_bytes = 0;    // simplify columns (likewise), and the geometry descriptors that name them
+    covt_simplify_info* d_spinfo = nullptr;
+    covt_simplify_desc* d_spdesc = nullptr;
+    covt_geom_desc* d_sgdesc = nullptr;
     void* prop_arena = nullptr;    // property columns (COVT_PLAN_PROPERTIES): records, infos, descriptors
     void* scratch = nullptr;       // creation-time scratch (the property walk's record slots), freed on the way
     int64_t n_props = 0, prop_bytes = 0;
@@ -2180,6 +2185,25 @@ struct SelectProduct {  // covt_select_plan.h
         r.byte_cap = d.byte_cap;
     }
 };
+struct SimplifyProduct {  // covt_simplify_plan.h
+    using Info = covt_simplify_info;
+    using Desc = covt_simplify_desc;
+    static __device__ int64_t layout(const covt_geom_info& g, int64_t off, Desc& d) {
+        return simplify_column_layout(g.n_features, g.part_cap, g.ring_cap, g.coord_cap, (uint32_t)g.flags, off, d);
+    }
+    static __device__ void fill(Info& r, const Desc& d) {
+        r.off = d.off;
+        r.part_cap = d.part_cap;
+        r.ring_cap = d.ring_cap;
+        r.coord_cap = d.coord_cap;
+    }
+};
+// the geometry descriptors of the simplified columns (covt_plan_simplified_geometry_descs), launch order
+__global__ void simplified_descs(const covt_geom_desc* __restrict__ gdesc, const covt_simplify_desc* __restrict__ sdesc,
+                                 int64_t nc, covt_geom_desc* __restrict__ out) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < nc) out[k] = simplify_retarget(gdesc[k], sdesc[k]);
+}
 template <class P>
 __global__ void product_col_bytes(const covt_geom_info* __restrict__ ginfo, int64_t nc, int64_t* __restrict__ bytes) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2799,6 +2823,8 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     const ProductSlice<BboxProduct> a_bbox(L, m);
     const ProductSlice<MeasuresProduct> a_measures(L, m);
     const ProductSlice<SelectProduct> a_select(L, m);
+    const ProductSlice<SimplifyProduct> a_simplify(L, m);
+    const auto a_sgd = L.take<covt_geom_desc>(m);
     // the arena is the plan's only on success: a failed build frees it (a retry allocates afresh)
     StreamFree arena{nullptr, s};
     HIP_TRY(plan_malloc(&arena.q, L.bytes(), p->dev, s));
@@ -2809,7 +2835,7 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     uint32_t* v1 = a_v1.at(g);
     uint8_t* cscan = a_cs.at(g);
     HIP_TRY(hipMemsetAsync(colbytes, 0, (m + 1) * 8, s));
-    int64_t asm_bytes = 0, wkb_bytes = 0, bbox_bytes = 0, measures_bytes = 0, select_bytes = 0;
+    int64_t asm_bytes = 0, wkb_bytes = 0, bbox_bytes = 0, measures_bytes = 0, select_bytes = 0, simplify_bytes = 0;
     if (nc > 0) {
         geom_columns<<<(int)((ns + 255) / 256), 256, 0, s>>>(p->d_info, ns, p->format, gst, gpos, p->d_ginfo, colbytes);
         HIP_TRY(hipGetLastError());
@@ -2830,8 +2856,13 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
         st = plan_product(a_measures, g, m, nc, p->d_ginfo, cscan, cscan_tmp, s, p->d_minfo, p->d_mdesc, &measures_bytes);
     if (st == COVT_OK)
         st = plan_product(a_select, g, m, nc, p->d_ginfo, cscan, cscan_tmp, s, p->d_sinfo, p->d_sdesc, &select_bytes);
+    if (st == COVT_OK)
+        st = plan_product(a_simplify, g, m, nc, p->d_ginfo, cscan, cscan_tmp, s, p->d_spinfo, p->d_spdesc, &simplify_bytes);
     if (st) return st;
+    p->d_sgdesc = a_sgd.at(g);
     if (nc > 0) {
+        simplified_descs<<<(int)((nc + 255) / 256), 256, 0, s>>>(p->d_gdesc, p->d_spdesc, nc, p->d_sgdesc);
+        HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(&asm_bytes, coloff + nc, 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
     }
@@ -2844,6 +2875,7 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     p->bbox_bytes = bbox_bytes;
     p->measures_bytes = measures_bytes;
     p->select_bytes = select_bytes;
+    p->simplify_bytes = simplify_bytes;
     p->geo_built = true;
     return COVT_OK;
 }
@@ -2940,6 +2972,27 @@ int covt_device_plan_select(covt_device_plan* p, const uint8_t* d_wkb, const cov
     const int st = covt_device_plan_geometry(p, hip_stream);
     if (st) return st;
     return covt_geometry_select_device(p->d_wdesc, d_wkb, d_wres, p->d_sdesc, p->n_geo, d_select, d_sres, hip_stream);
+}
+
+int64_t covt_device_plan_simplify_bytes(const covt_device_plan* p) { return p && p->geo_built ? p->simplify_bytes : 0; }
+const covt_simplify_desc* covt_device_plan_simplify_descs_device(const covt_device_plan* p) {
+    return p && p->geo_built ? p->d_spdesc : nullptr;
+}
+const covt_geom_desc* covt_device_plan_simplified_geometry_descs_device(const covt_device_plan* p) {
+    return p && p->geo_built ? p->d_sgdesc : nullptr;
+}
+int covt_device_plan_simplify_copy(const covt_device_plan* p, covt_simplify_info* infos, covt_simplify_desc* descs) {
+    if (!p || !p->geo_built) return COVT_ERR_INVALID_ARG;
+    return copy_to_host(p->n_geo, infos, p->d_spinfo, descs, p->d_spdesc);
+}
+int covt_device_plan_simplify(covt_device_plan* p, const uint8_t* d_decoded, const uint8_t* d_asm,
+                              const covt_geom_result* d_gres, int32_t shift, const int32_t* d_shift,
+                              uint8_t* d_simplify, covt_geom_result* d_gres_out, void* hip_stream) {
+    if (!p) return COVT_ERR_INVALID_ARG;
+    const int st = covt_device_plan_geometry(p, hip_stream);
+    if (st) return st;
+    return covt_geometry_simplify_device(d_decoded, p->d_gdesc, d_asm, d_gres, p->d_spdesc, p->n_geo, shift, d_shift,
+                                         d_simplify, d_gres_out, hip_stream);
 }
 
 int covt_device_plan_assemble(covt_device_plan* p, const uint8_t* d_decoded, const covt_stream_result* d_res,

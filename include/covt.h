@@ -796,6 +796,109 @@ int covt_plan_select_host(const covt_plan* plan, const uint8_t* bytes, uint64_t 
                           covt_select_result* host_sres);
 
 /* ---------------------------------------------------------------------------
+ * Geometry simplification: a cheaper version of every feature for a lower zoom, what PostGIS ST_AsMVTGeom and
+ * tippecanoe do before they serialise: snap the coordinates to the target zoom's pixel grid (ST_SnapToGrid),
+ * drop the vertices that now repeat their predecessor (ST_RemoveRepeatedPoints), and empty the rings and lines
+ * that collapsed below what a reader accepts.  Integer arithmetic throughout, so the result is exact.
+ *
+ * Input: an assembled column (n features, P parts, R rings, V coordinates), the types t_f of its decoded
+ * GeometryTypes stream (POINT 0, LINESTRING 1, POLYGON 2, MULTIPOINT 3, MULTILINESTRING 4, MULTIPOLYGON 5) and a
+ * shift s in [0, COVT_SIMPLIFY_MAX_SHIFT]: the grid cell is 2^s tile pixels, s = source zoom - target zoom.
+ *
+ *   Snap.  snap(v) = min((((int64)v + h) >> s) << s, M) with h = s ? 2^(s-1) : 0, M = (INT32_MAX >> s) << s and
+ *     >> arithmetic (floor): round half up to the grid; a value that would round past the int32 range snaps to
+ *     the largest grid value that fits.  q_i = (snap(x_i), snap(y_i)).
+ *   Keep.  Ring r covers the coordinates [a, b), a = ring_offsets[r], b = ring_offsets[r + 1]; t is the type of
+ *     the ring's feature.  For t in {0, 3} every coordinate is kept; for any other t coordinate i is kept iff
+ *     i == a or q_i != q_{i-1}.  The rule is local, so the kept sequence has no two equal neighbours, and a
+ *     closed ring stays closed (its last kept value is q_{b-1} = q_a).  k_r is the number kept in ring r.
+ *   Collapse.  t in {1, 4}: ring r is collapsed if k_r < 2.  t in {2, 5}: collapsed if k_r < 4 (JTS WKBReader
+ *     rejects linear rings of 1 to 3 points and lines of 1 point; it accepts 0), and if the first ring of r's
+ *     part is collapsed, every ring of that part is: a hole cannot outlive its shell (so an input part whose
+ *     first ring is already empty loses its holes, also at s = 0).  k'_r = 0 for a collapsed ring, else k_r.
+ *   Output.  An assembled column of the same shape in the column's slice of the simplify buffer:
+ *     geometry_offsets[n + 1] and part_offsets[P + 1] copied, ring_offsets'[0] = 0, ring_offsets'[r + 1] =
+ *     ring_offsets'[r] + k'_r, coords' the kept q_i of the non-collapsed rings in input order, and a
+ *     covt_geom_result {status, num_parts = P, num_rings = R, num_coords = ring_offsets'[R]}.  Parts and rings
+ *     are never removed, only emptied, so feature numbering and the number of rows stay.  A feature left
+ *     without a coordinate is downstream what the other products define: num_coords 0, a NaN box, dropped by
+ *     the select predicate unless COVT_SELECT_KEEP_EMPTY is set.
+ *
+ * Per column one slice (16-byte aligned start, every member padded to 16 bytes):
+ *
+ *   geometry_offsets[n + 1] | part_offsets[part_cap + 1] | ring_offsets[ring_cap + 1] | coords[2 * coord_cap]
+ *   | scratch (a kept count per ring and per chunk of coordinates; contents unspecified)
+ *
+ * sized by one layout rule from the geometry column's capacities; the output never exceeds the input, so there
+ * is no capacity status.  covt_plan_simplified_geometry_descs gives the geometry descriptors with out_off[0..3]
+ * pointing into the simplify buffer: with that table, the simplify buffer as d_asm and the simplify results as
+ * d_gres every pass that reads an assembled column (WKB, bounding boxes, measures, their projected forms, and
+ * select after them) runs on the simplified column unchanged, with its own descriptors unchanged (capacities
+ * only shrink).
+ *
+ * The pass is idempotent; s = 0 removes only exact repeats and collapses.  Every element of the output is
+ * written exactly once; there are no atomics and no allocation, so the pass can be captured in a HIP graph as
+ * it is and its bytes do not depend on scheduling.  Not written: ring_offsets' past R + 1, part_offsets past
+ * P + 1, coords' past num_coords, the padding, and the whole slice of a failed column (its scratch included).
+ * Offsets are read clamped as every product reads them, and every destination is checked against the slice:
+ * whatever the input holds, no access leaves the slices.
+ * Statuses: a column whose assembly result is not COVT_OK gets that status (counts 0); COVT_GEOM_TOO_LARGE,
+ * COVT_SIMPLIFY_TOO_LARGE or a descriptor that does not match the geometry descriptor's capacities ->
+ * COVT_ERR_INVALID_ARG; a per-column shift outside the range -> COVT_ERR_INVALID_ARG for that column; a uniform
+ * shift outside it makes the call return COVT_ERR_INVALID_ARG.
+ * Out of scope: Douglas-Peucker or Visvalingam, removal of collinear vertices or spikes, repair of the
+ * self-intersections snapping can create, clipping, the Java binding.
+ * ------------------------------------------------------------------------- */
+#define COVT_SIMPLIFY_TOO_LARGE 0x1 /* covt_simplify_desc.flags: assembly refuses the column (COVT_GEOM_TOO_LARGE) */
+#define COVT_SIMPLIFY_MAX_SHIFT 30
+
+/* One device-resident simplify column entry (32 bytes), parallel to covt_geom_desc (launch order). */
+typedef struct covt_simplify_desc {
+    int64_t off; /* byte offset of the column's slice in the simplify buffer (16-byte aligned) */
+    int32_t n_features, flags;
+    int32_t part_cap, ring_cap, coord_cap, reserved; /* = covt_geom_desc's: what the slice was sized for */
+} covt_simplify_desc;
+
+/* Host-visible simplify column record of a plan, in tile order (40 bytes); column c belongs to geometry column
+ * c (covt_geom_info). */
+typedef struct covt_simplify_info {
+    int32_t tile, layer, n_features, desc_index; /* desc_index: row in the launch-ordered descriptors */
+    int64_t off;
+    int32_t flags, part_cap, ring_cap, coord_cap;
+} covt_simplify_info;
+
+int64_t covt_plan_simplify_bytes(const covt_plan* plan); /* size of the simplify buffer */
+int covt_plan_simplify_columns(const covt_plan* plan, covt_simplify_info* out); /* tile order, num_geometry_columns */
+int covt_plan_simplify_descs(const covt_plan* plan, covt_simplify_desc* out);   /* launch order (= covt_plan_geometry_descs) */
+/* covt_plan_geometry_descs with out_off[0..3] pointing into the simplify buffer (in_off, capacities unchanged). */
+int covt_plan_simplified_geometry_descs(const covt_plan* plan, covt_geom_desc* out);
+/* Per-tile shifts (n_tiles entries) -> per-column shifts in launch order (num_geometry_columns entries), as
+ * covt_plan_geo_transforms does for transforms.  Values are passed through; the pass checks them per column. */
+int covt_plan_simplify_shifts(const covt_plan* plan, const int32_t* tile_shift, int32_t* out);
+
+/* Simplify every assembled geometry column on `hip_stream`, after covt_assemble_geometry_device on the same
+ * stream: d_decoded the decode output (GeometryTypes are read from it), d_gdesc / d_asm / d_gres the assembly's
+ * descriptors, output and results, d_sdesc the simplify descriptors (same order), `shift` for every column or,
+ * if d_shift is not null, d_shift[c] for column c (launch order), d_simplify the simplify buffer of
+ * covt_plan_simplify_bytes bytes (16-byte aligned, not the assembly buffer), d_gres_out n_columns results (same
+ * order).  Asynchronous; allocates nothing, capturable. */
+int covt_geometry_simplify_device(const uint8_t* d_decoded, const covt_geom_desc* d_gdesc, const uint8_t* d_asm,
+                                  const covt_geom_result* d_gres, const covt_simplify_desc* d_sdesc,
+                                  int64_t n_columns, int32_t shift, const int32_t* d_shift, uint8_t* d_simplify,
+                                  covt_geom_result* d_gres_out, void* hip_stream);
+
+/* Convenience: H2D + decode + assembly + simplify + D2H of the whole plan on the current device.  `shift` for
+ * every tile or, if tile_shift is not null, tile_shift[t] for tile t.  host_simplify: covt_plan_simplify_bytes
+ * bytes; host_gres: one result per column in tile order. */
+int covt_plan_simplify_host(const covt_plan* plan, const uint8_t* bytes, uint64_t n_bytes, int32_t shift,
+                            const int32_t* tile_shift, uint8_t* host_simplify, covt_geom_result* host_gres);
+
+/* While set (enabled != 0), covt_plan_wkb_host, _bbox_host, _measures_host, _select_host and their projected
+ * forms run the simplify pass after the assembly and read the simplified column.  tile_shift (n_tiles entries,
+ * copied) may be null: `shift` for every tile.  Unset by default.  COVT_ERR_INVALID_ARG for a shift out of range. */
+int covt_plan_set_simplify(covt_plan* plan, int32_t enabled, int32_t shift, const int32_t* tile_shift);
+
+/* ---------------------------------------------------------------------------
  * Property columns: the GPU replacement for
  * CovtParser.decodePropertyColumn (CovtParser.java:276-354) and getStringDictionary (:367-377).
  * A plan created with COVT_PLAN_PROPERTIES also plans every property column: its present / data /
@@ -1016,6 +1119,19 @@ int covt_device_plan_select_copy(const covt_device_plan* plan, covt_select_info*
  * launch order (column c's at its covt_select_info.desc_index). */
 int covt_device_plan_select(covt_device_plan* plan, const uint8_t* d_wkb, const covt_wkb_result* d_wres,
                             uint8_t* d_select, covt_select_result* d_sres, void* hip_stream);
+/* Simplify columns from a device plan: the records and descriptors of covt_plan_simplify_columns /
+ * covt_plan_simplify_descs and the retargeted geometry descriptors of covt_plan_simplified_geometry_descs, built
+ * on the device next to the select records (covt_device_plan_geometry; the host plan's exactly); 0 / NULL
+ * before that call. */
+int64_t covt_device_plan_simplify_bytes(const covt_device_plan* plan);
+const covt_simplify_desc* covt_device_plan_simplify_descs_device(const covt_device_plan* plan);
+int covt_device_plan_simplify_copy(const covt_device_plan* plan, covt_simplify_info* infos, covt_simplify_desc* descs);
+const covt_geom_desc* covt_device_plan_simplified_geometry_descs_device(const covt_device_plan* plan);
+/* covt_geometry_simplify_device over the plan's descriptors, after covt_device_plan_assemble on the same
+ * stream: d_simplify covt_device_plan_simplify_bytes bytes, d_gres_out one result per column in launch order. */
+int covt_device_plan_simplify(covt_device_plan* plan, const uint8_t* d_decoded, const uint8_t* d_asm,
+                              const covt_geom_result* d_gres, int32_t shift, const int32_t* d_shift,
+                              uint8_t* d_simplify, covt_geom_result* d_gres_out, void* hip_stream);
 /* Property columns from a device plan made with COVT_PLAN_PROPERTIES in opts->flags: the records,
  * output layout and largest-first descriptors of covt_plan_property_columns / covt_plan_property_descs,
  * built on the device with the plan (the host plan's exactly); a plan without the flag has none. */
