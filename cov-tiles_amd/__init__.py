@@ -245,6 +245,119 @@ class SelectPred(C.Structure):
             self.flags, tuple(self.window), self.min_area, self.min_length)
 
 
+# property predicates (include/covt.h "Property predicates")
+WHERE_MAX_CLAUSES, WHERE_MAX_VALUES, WHERE_MAX_TEXT, WHERE_MAX_IN = 8, 32, 1024, 16
+(WHERE_EQ, WHERE_NE, WHERE_LT, WHERE_LE, WHERE_GT, WHERE_GE, WHERE_IN, WHERE_NOT_IN, WHERE_IS_NULL,
+ WHERE_NOT_NULL) = range(10)
+WHERE_BOOL, WHERE_INT, WHERE_REAL, WHERE_STRING = 1, 2, 4, 8
+WHERE_NULL_MATCHES = 1
+WHERE_WRITE, WHERE_AND = 0, 1
+_WHERE_OPS = {"==": WHERE_EQ, "!=": WHERE_NE, "<": WHERE_LT, "<=": WHERE_LE, ">": WHERE_GT, ">=": WHERE_GE,
+              "in": WHERE_IN, "not in": WHERE_NOT_IN, "is null": WHERE_IS_NULL, "not null": WHERE_NOT_NULL}
+
+
+class WhereValue(C.Structure):
+    """covt_where_value: one literal of a Where, a value per kind it may be read as."""
+    _fields_ = [("i", C.c_int64), ("d", C.c_double), ("str_off", C.c_int32), ("str_len", C.c_int32),
+                ("kinds", C.c_uint32), ("b", C.c_int32)]
+
+
+class WhereClause(C.Structure):
+    """covt_where_clause: op, flags, the range of its literals and of its column name."""
+    _fields_ = [("op", C.c_int32), ("flags", C.c_uint32), ("first_value", C.c_int32), ("n_values", C.c_int32),
+                ("name_off", C.c_int32), ("name_len", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class WhereLiteral(C.Structure):
+    """covt_where_literal: a literal as covt_where_add_clause takes it."""
+    _fields_ = [("kinds", C.c_uint32), ("b", C.c_int32), ("i", C.c_int64), ("d", C.c_double), ("str", C.c_char_p),
+                ("str_len", C.c_int32), ("reserved", C.c_int32)]
+
+
+def _where_literal(x) -> WhereLiteral:
+    """The literal of a Python value: bool -> BOOL; int -> INT, plus REAL when |x| <= 2^53; float -> REAL (NaN
+    raises), plus INT when integral and inside int64; str / bytes -> STRING."""
+    L = WhereLiteral()
+    if isinstance(x, (bool, np.bool_)):
+        L.kinds, L.b = WHERE_BOOL, int(bool(x))
+    elif isinstance(x, (int, np.integer)):
+        x = int(x)
+        if not -(1 << 63) <= x < (1 << 63):
+            raise IllegalArgumentException("integer literal %d does not fit int64" % x)
+        L.kinds, L.i = WHERE_INT, x
+        if abs(x) <= (1 << 53):
+            L.kinds |= WHERE_REAL
+            L.d = float(x)
+    elif isinstance(x, (float, np.floating)):
+        x = float(x)
+        if x != x:
+            raise IllegalArgumentException("a NaN literal compares with nothing")
+        L.kinds, L.d = WHERE_REAL, x
+        if x.is_integer() and -2.0 ** 63 <= x < 2.0 ** 63:
+            L.kinds |= WHERE_INT
+            L.i = int(x)
+    elif isinstance(x, (str, bytes, bytearray)):
+        raw = x.encode("utf-8") if isinstance(x, str) else bytes(x)
+        L.kinds, L.str, L.str_len = WHERE_STRING, raw, len(raw)
+    else:
+        raise IllegalArgumentException("a literal must be a bool, int, float, str or bytes, not %r" % type(x).__name__)
+    return L
+
+
+class Where(C.Structure):
+    """covt_where (include/covt.h "Property predicates"): a conjunction of clauses over named property columns,
+    ``Where(("class", "in", ["motorway", "trunk"]), ("rank", "<=", 3), ("name:de", "is null"))``.  A clause is
+    (name, op, value[, null_matches]) with op one of "==" "!=" "<" "<=" ">" ">=" "in" "not in" "is null"
+    "not null" (the last two take no value); a name is the column's, plus ':<lang>' for a localized sub-column
+    (Plan.property_name).  null_matches: a feature without a value satisfies the clause."""
+    _fields_ = [("size", C.c_uint32), ("n_clauses", C.c_uint32), ("n_values", C.c_uint32), ("text_len", C.c_uint32),
+                ("clauses", WhereClause * WHERE_MAX_CLAUSES), ("values", WhereValue * WHERE_MAX_VALUES),
+                ("text", C.c_uint8 * WHERE_MAX_TEXT)]
+
+    def __init__(self, *clauses):
+        super().__init__()
+        lib().covt_where_init(C.byref(self))
+        for c in clauses:
+            self.add(*c)
+
+    def add(self, name, op, value=None, null_matches: bool = False) -> "Where":
+        """One more clause (covt_where_add_clause); raises IllegalArgumentException where it refuses."""
+        if isinstance(op, str):
+            if op not in _WHERE_OPS:
+                raise IllegalArgumentException("unknown op %r" % op)
+            op = _WHERE_OPS[op]
+        if op in (WHERE_IS_NULL, WHERE_NOT_NULL):
+            vals = [] if value is None else [value]
+        elif op in (WHERE_IN, WHERE_NOT_IN) and not isinstance(value, (str, bytes, bytearray)) and np.ndim(value) == 1:
+            vals = list(value)
+        elif op in (WHERE_IN, WHERE_NOT_IN) and isinstance(value, (set, frozenset)):
+            vals = sorted(value)
+        else:
+            vals = [value]
+        lits = (WhereLiteral * max(len(vals), 1))(*[_where_literal(v) for v in vals])
+        raw = name.encode("utf-8") if isinstance(name, str) else bytes(name)
+        _raise(lib().covt_where_add_clause(C.byref(self), raw, len(raw), int(op),
+                                           WHERE_NULL_MATCHES if null_matches else 0, lits, len(vals)),
+               "covt_where_add_clause")
+        return self
+
+    def valid(self) -> bool:
+        return bool(lib().covt_where_valid(C.byref(self)))
+
+    def tobytes(self) -> bytes:
+        return bytes(memoryview(self))
+
+    def __repr__(self):
+        return "Where(n_clauses=%d, n_values=%d, text=%r)" % (self.n_clauses, self.n_values,
+                                                             bytes(self.text[:self.text_len]))
+
+
+def where_dict_bounds():
+    """(workgroup per column, wave per column): the dictionary sizes up to which the where kernel answers a
+    STRING clause from a match bitmap in LDS (covt_where_dict_bound)."""
+    return int(lib().covt_where_dict_bound(0)), int(lib().covt_where_dict_bound(1))
+
+
 STREAM_INFO_DTYPE = np.dtype([(n, np.int32 if t is C.c_int32 else np.int64) for n, t in StreamInfo._fields_])
 assert STREAM_INFO_DTYPE.itemsize == C.sizeof(StreamInfo)
 assert C.sizeof(StreamDesc) == 32
@@ -313,6 +426,15 @@ _SIGNATURES = {
     "covt_select_predicate_device": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "covt_geometry_select_device": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "covt_plan_select_host": (_int, [_vp, _u8p, _u64, _i32, _vp, _vp, _vp, _vp]),
+    # property predicates
+    "covt_where_init": (None, [_vp]),
+    "covt_where_add_clause": (_int, [_vp, C.c_char_p, _i32, _i32, C.c_uint32, _vp, _i32]),
+    "covt_where_valid": (_int, [_vp]),
+    "covt_where_bind": (_int, [_vp, _vp, _i64, _vp, _i64, _u8p, _u64, _vp]),
+    "covt_plan_where_bind": (_int, [_vp, _u8p, _u64, _vp, _vp]),
+    "covt_where_dict_bound": (_i32, [_i32]),
+    "covt_select_where_device": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "covt_plan_select_where_host": (_int, [_vp, _u8p, _u64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     # geometry simplification
     "covt_plan_simplify_shifts": (_int, [_vp, _vp, _vp]),
     "covt_geometry_simplify_device": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
@@ -889,18 +1011,39 @@ class Plan:
         return MeasuresColumn(buf[o:o + 8 * n].view(np.float64), buf[o + 8 * n:o + 16 * n].view(np.float64),
                               buf[o + 16 * n:o + 20 * n].view(np.int32))
 
-    def select_host(self, pred: "SelectPred", crs=None, tile_zxy=None):
+    def select_host(self, pred: Optional["SelectPred"], crs=None, tile_zxy=None, where: Optional["Where"] = None):
         """H2D + decode + geometry assembly + WKB and bounding boxes (in `crs`, given the tiles' z, x, y) +
-        measures if `pred` has a size cut + predicate + select + D2H (covt_plan_select_host).
+        measures if `pred` has a size cut + predicate + select + D2H (covt_plan_select_host).  With `where`
+        (a plan made with PLAN_PROPERTIES) covt_plan_select_where_host: the property predicate ANDed into
+        `pred`'s masks, or alone with pred=None; its per-column statuses in tile order are kept as
+        ``self.where_status``.
         Returns (uint8 select buffer, results[num_geometry_columns] in tile order); see select_column."""
         buf = np.zeros(max(self.select_bytes, 1), dtype=np.uint8)
         res = np.zeros(max(self.num_geometry_columns, 1), dtype=SELECT_RESULT_DTYPE)
         zxy = _zxy(tile_zxy, self.n_tiles) if tile_zxy is not None else None
-        _raise(lib().covt_plan_select_host(self._h, _ptr(self.blob, C.c_uint8), self.blob.size,
-                                           CRS_TILE if crs is None else crs,
-                                           zxy.ctypes.data if zxy is not None else None, C.byref(pred),
-                                           buf.ctypes.data, res.ctypes.data), "covt_plan_select_host")
+        if where is None:
+            _raise(lib().covt_plan_select_host(self._h, _ptr(self.blob, C.c_uint8), self.blob.size,
+                                               CRS_TILE if crs is None else crs,
+                                               zxy.ctypes.data if zxy is not None else None, C.byref(pred),
+                                               buf.ctypes.data, res.ctypes.data), "covt_plan_select_host")
+            return buf[:self.select_bytes], res[:self.num_geometry_columns]
+        wst = np.zeros(max(self.num_geometry_columns, 1), dtype=np.int32)
+        _raise(lib().covt_plan_select_where_host(self._h, _ptr(self.blob, C.c_uint8), self.blob.size,
+                                                 CRS_TILE if crs is None else crs,
+                                                 zxy.ctypes.data if zxy is not None else None,
+                                                 C.byref(pred) if pred is not None else None, C.byref(where),
+                                                 buf.ctypes.data, res.ctypes.data, wst.ctypes.data),
+               "covt_plan_select_where_host")
+        self.where_status = wst[:self.num_geometry_columns]
         return buf[:self.select_bytes], res[:self.num_geometry_columns]
+
+    def where_bind(self, where: "Where") -> np.ndarray:
+        """covt_plan_where_bind: int32 [num_geometry_columns, WHERE_MAX_CLAUSES] in launch order, entry [c, k]
+        the property descriptor clause k reads in geometry column c (-1: none in that layer)."""
+        out = np.full((max(self.num_geometry_columns, 1), WHERE_MAX_CLAUSES), -1, dtype=np.int32)
+        _raise(lib().covt_plan_where_bind(self._h, _ptr(self.blob, C.c_uint8), self.blob.size, C.byref(where),
+                                          out.ctypes.data), "covt_plan_where_bind")
+        return out[:self.num_geometry_columns]
 
     def select_column(self, buf: np.ndarray, sres: np.ndarray, c: int) -> "SelectedColumn":
         """Column c (tile order) of a select buffer -> SelectedColumn (raises on its status)."""
@@ -1245,6 +1388,45 @@ class DeviceBatch:
                                                   C.byref(pred), self.d_select.data_ptr(),
                                                   _stream(stream, self.device)), "covt_select_predicate_device")
 
+    def _where(self, where: "Where"):
+        """The device copies of a Where and its bind table, uploaded once and kept on the batch (another
+        predicate replaces them) -> (blob pointer, bind pointer)."""
+        import torch
+
+        raw = where.tobytes()
+        if getattr(self, "_where_host", None) != raw:
+            bind = self.plan.where_bind(where).reshape(-1)
+            self.d_where = torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).to(self.device)
+            self.d_bind = torch.from_numpy(bind.copy()).to(self.device) if bind.size else \
+                torch.zeros(WHERE_MAX_CLAUSES, dtype=torch.int32, device=self.device)
+            self._where_host = raw
+        return self.d_where.data_ptr(), self.d_bind.data_ptr()
+
+    def select_where(self, where: "Where", mode: int = WHERE_WRITE, stream=None):
+        """Enqueue the where pass: every column's keep mask from the property predicate (WHERE_WRITE), or ANDed
+        into the masks already there (WHERE_AND), after materialize_properties() and whatever wrote the masks
+        on the same stream.  The blob and its bind table are uploaded on the first call with a predicate (call
+        once before capturing a graph)."""
+        import torch
+
+        self._buffers("property")
+        self._buffers("select")
+        d_where, d_bind = self._where(where)
+        if getattr(self, "d_where_status", None) is None:
+            self.d_where_status = torch.zeros(max(self.plan.num_geometry_columns, 1), dtype=torch.int32,
+                                              device=self.device)
+        _raise(lib().covt_select_where_device(self.d_pdesc.data_ptr(), self.d_props.data_ptr(), self.d_pres.data_ptr(),
+                                              self.plan.num_property_columns, self.d_sdesc.data_ptr(),
+                                              self.plan.num_geometry_columns, d_where, d_bind, int(mode),
+                                              self.d_select.data_ptr(), self.d_where_status.data_ptr(),
+                                              _stream(stream, self.device)), "covt_select_where_device")
+
+    def where_status(self) -> np.ndarray:
+        """The where pass's per-column statuses in tile order, copied to the host (after select_where())."""
+        st = self.d_where_status.cpu().numpy()[:self.plan.num_geometry_columns]
+        idx = self.plan.select["desc_index"]
+        return st[idx] if idx.size else st
+
     def select(self, stream=None):
         """Enqueue the selection: every column's selection vector and compacted WKB from its keep mask (after
         wkb() and select_predicate(), or the caller's own masks, on the same stream)."""
@@ -1506,6 +1688,31 @@ class DevicePlan:
                                              d_sres.data_ptr(), _stream(stream, self.device)),
                "covt_device_plan_select")
 
+    def where_bind(self, where: "Where", blob) -> np.ndarray:
+        """covt_where_bind over this plan's record copies: int32 [num_geometry_columns, WHERE_MAX_CLAUSES] in
+        launch order.  `blob`: the tiles' bytes on the host (the column names are read from them)."""
+        ginfo, _ = self.geometry_copy()
+        pinfo, _ = self.property_copy()
+        raw = _u8(blob)
+        out = np.full((max(ginfo.size, 1), WHERE_MAX_CLAUSES), -1, dtype=np.int32)
+        _raise(lib().covt_where_bind(C.byref(where), ginfo.ctypes.data, ginfo.size, pinfo.ctypes.data, pinfo.size,
+                                     _ptr(raw, C.c_uint8), raw.size, out.ctypes.data), "covt_where_bind")
+        return out[:ginfo.size]
+
+    def select_where(self, d_props, d_pres, d_where, d_bind, d_select, mode: int = WHERE_WRITE, d_status=None,
+                     stream=None):
+        """Enqueue the where pass over this plan's property and select descriptors (after materialize() and
+        whatever wrote the masks on the same stream): d_where the Where's bytes and d_bind the table of
+        where_bind() as device tensors, d_status an int32 tensor of num_geometry_columns entries or None."""
+        self.geometry(stream)
+        L = lib()
+        _raise(L.covt_select_where_device(L.covt_device_plan_property_descs_device(self._h), d_props.data_ptr(),
+                                          d_pres.data_ptr(), self.num_property_columns,
+                                          L.covt_device_plan_select_descs_device(self._h), self.num_geometry_columns,
+                                          d_where.data_ptr(), d_bind.data_ptr(), int(mode), d_select.data_ptr(),
+                                          d_status.data_ptr() if d_status is not None else None,
+                                          _stream(stream, self.device)), "covt_select_where_device")
+
     def simplify_copy(self):
         """(simplify records in tile order, descriptors in launch order) as host arrays (Plan.simplify /
         Plan.spdescs)."""
@@ -1749,18 +1956,22 @@ class CovtParser:
     @staticmethod
     def decode_covt(covt_buffer: bytes, fmt: int = FORMAT_GENC, id_mode: int = ID_FORMAT,
                     properties: bool = False, tile_id=None, crs: int = CRS_TILE,
-                    select: Optional[SelectPred] = None, simplify: Optional[int] = None) -> List[LayerColumns]:
+                    select: Optional[SelectPred] = None, simplify: Optional[int] = None,
+                    where: Optional["Where"] = None) -> List[LayerColumns]:
         """CovtParser.decodeCovt (CovtParser.java:53-133) decoded on the GPU: Id + Geometry columns, and with
         ``properties`` every property column as a PropertyColumn (LayerColumns.properties, by name).
         ``tile_id`` = (z, x, y) and ``crs`` give every layer's wkb / bbox in that CRS (LayerColumns.crs).
         ``select``, a SelectPred whose window is in that CRS, gives every layer the features it keeps
         (LayerColumns.selected: their numbers and their WKB values; the other columns are array[selected.index]).
         ``simplify``, a shift, gives every layer's wkb, bbox, measures and selected from the column simplified to
-        the grid of 2^shift tile pixels, and that column as LayerColumns.simplified; None: no simplification."""
+        the grid of 2^shift tile pixels, and that column as LayerColumns.simplified; None: no simplification.
+        ``where``, a Where, keeps in LayerColumns.selected only the features whose properties satisfy it (with
+        ``select`` both must hold); it implies the property plan, and a layer without a named column sees that
+        clause's values as absent."""
         if crs != CRS_TILE and tile_id is None:
             raise IllegalArgumentException("a CRS other than CRS_TILE needs the tile's (z, x, y)")
         geo = (crs, [tile_id]) if crs != CRS_TILE else (None, None)
-        plan = Plan.from_tiles([covt_buffer], fmt, id_mode, PLAN_PROPERTIES if properties else 0)
+        plan = Plan.from_tiles([covt_buffer], fmt, id_mode, PLAN_PROPERTIES if properties or where is not None else 0)
         _raise(int(plan.tile_status[0]), "decodeLayerMetadata")
         out, res = plan.decode_host()
         layers = split_layers(plan, out, res, 0)
@@ -1790,8 +2001,8 @@ class CovtParser:
                 lc = by_layer.get(int(plan.measures["layer"][c]))
                 if lc is not None and int(mres["status"][c]) == OK:  # (a failed column keeps measures = None)
                     lc.measures = plan.measures_column(mbuf, mres, c)
-            if select is not None:
-                sbuf, sres = plan.select_host(select, *geo)
+            if select is not None or where is not None:
+                sbuf, sres = plan.select_host(select, *geo, where=where)
                 for c in range(plan.num_geometry_columns):
                     lc = by_layer.get(int(plan.select["layer"][c]))
                     if lc is not None and int(sres["status"][c]) == OK:  # (a failed column keeps selected = None)
@@ -1818,12 +2029,12 @@ def version() -> str:
 _BUILD_SOURCES = (  # the Makefile's SRC, then its HDR, one to one
     ("csrc/covt_decode.hip", "csrc/covt_assemble.hip", "csrc/covt_props.hip", "csrc/covt_plan_device.hip",
      "csrc/covt_wkb.hip", "csrc/covt_bbox.hip", "csrc/covt_measures.hip", "csrc/covt_select.hip",
-     "csrc/covt_simplify.hip", "csrc/covt_host.cpp")
+     "csrc/covt_simplify.hip", "csrc/covt_where.hip", "csrc/covt_host.cpp")
     + ("../include/covt.h", "csrc/covt_internal.h", "csrc/covt_wave.h", "csrc/covt_segscan.h", "csrc/covt_walk.h",
        "csrc/covt_props_plan.h",
        "csrc/covt_scratch.h", "csrc/covt_coop.h", "csrc/covt_wkb_plan.h", "csrc/covt_bbox_plan.h",
        "csrc/covt_measures_plan.h", "csrc/covt_select_plan.h", "csrc/covt_simplify_plan.h", "csrc/covt_geo_plan.h", "csrc/covt_arena.h", "csrc/covt_split_plan.h",
-       "csrc/covt_container.h"))
+       "csrc/covt_container.h", "csrc/covt_where_plan.h"))
 
 
 def source_build_id() -> str:

@@ -29,6 +29,7 @@
 #include "covt_bbox_plan.h"
 #include "covt_measures_plan.h"
 #include "covt_select_plan.h"
+#include "covt_where_plan.h"
 #include "covt_simplify_plan.h"
 #include "covt_geo_plan.h"
 
@@ -2062,6 +2063,84 @@ int covt_plan_select_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_b
                                                  w.res.as<covt_wkb_result>(), sdesc, n, buf, sres, s);
             return st;
         });
+}
+
+// the bind table of `w` over the plan's geometry and property records (covt_where_plan.h)
+int covt_plan_where_bind(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, const covt_where* w, int32_t* out) {
+    if (!p || !(p->opts.flags & COVT_PLAN_PROPERTIES)) return COVT_ERR_INVALID_ARG;
+    return where_bind(w, p->ginfo.data(), (int64_t)p->ginfo.size(), p->pinfo.data(), (int64_t)p->pinfo.size(), bytes,
+                      n_bytes, out);
+}
+
+// covt_plan_select_host with a property predicate: the properties materialized into a device-only buffer, the
+// where pass after the geometric predicate (AND) or in its place (WRITE)
+int covt_plan_select_where_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, int32_t crs,
+                                const int32_t* tile_zxy, const covt_select_pred* pred, const covt_where* where,
+                                uint8_t* host_select, covt_select_result* host_sres, int32_t* host_where_status) {
+    if (!p || (pred && !select_pred_valid(pred)) || (!bytes && n_bytes)) return COVT_ERR_INVALID_ARG;
+    const size_t ng = p->ginfo.size();
+    std::vector<int32_t> bind(std::max<size_t>(ng, 1) * COVT_WHERE_MAX_CLAUSES, -1), wst(std::max<size_t>(ng, 1), 0);
+    if (const int st = covt_plan_where_bind(p, bytes, n_bytes, where, bind.data())) return st;
+    GeoTable g;  // (this and the intermediate products outlive the pipeline's synchronize)
+    if (const int st = g.make(p, crs, tile_zxy)) return st;
+    DevProduct<covt_wkb_desc, covt_wkb_result> w;
+    DevProduct<covt_bbox_desc, covt_bbox_result> b;
+    DevProduct<covt_measures_desc, covt_measures_result> m;
+    DevProduct<covt_prop_desc, covt_prop_result> pr;
+    DevMem d_where, d_bind, d_wst;
+    const int rc = plan_product_host(
+        p, bytes, n_bytes, p->sinfo, p->sdescs, p->select_bytes, host_select, host_sres, true,
+        [&](const PlanDev& d, const covt_select_desc* sdesc, int64_t n, uint8_t* buf, covt_select_result* sres,
+            hipStream_t s) {
+            const bool size = pred && (pred->flags & COVT_SELECT_MIN_SIZE) != 0;
+            const int64_t np = (int64_t)p->pdescs.size();
+            int st = g.upload(s);
+            if (st == COVT_OK) st = w.make(p->wdescs, p->wkb_bytes, s);
+            if (st == COVT_OK && pred) st = b.make(p->bdescs, p->bbox_bytes, s);
+            if (st == COVT_OK && size) st = m.make(p->mdescs, p->measures_bytes, s);
+            if (st == COVT_OK) st = pr.make(p->pdescs, p->prop_bytes, s);
+            if (st == COVT_OK &&
+                (hipMalloc(&d_where.p, sizeof(covt_where)) != hipSuccess ||
+                 hipMalloc(&d_bind.p, bind.size() * sizeof(int32_t)) != hipSuccess ||
+                 hipMalloc(&d_wst.p, wst.size() * sizeof(int32_t)) != hipSuccess ||
+                 hipMemcpyAsync(d_where.p, where, sizeof(covt_where), hipMemcpyHostToDevice, s) != hipSuccess ||
+                 hipMemcpyAsync(d_bind.p, bind.data(), bind.size() * sizeof(int32_t), hipMemcpyHostToDevice, s) != hipSuccess ||
+                 hipMemsetAsync(d_wst.p, 0, wst.size() * sizeof(int32_t), s) != hipSuccess))
+                st = COVT_ERR_DEVICE;
+            const covt_geo_xform* xf = g.dev.as<covt_geo_xform>();
+            if (st == COVT_OK)
+                st = covt_materialize_properties_device(d.in, d.out, d.res, pr.desc.as<covt_prop_desc>(), np,
+                                                        pr.buf.as<uint8_t>(), pr.res.as<covt_prop_result>(), s);
+            if (st == COVT_OK)
+                st = covt_geometry_wkb_projected_device(d.out, d.gdesc, d.asm_buf, d.gres, w.desc.as<covt_wkb_desc>(), n,
+                                                        w.buf.as<uint8_t>(), w.res.as<covt_wkb_result>(), xf, g.kinds, s);
+            if (st == COVT_OK && pred)
+                st = covt_geometry_bbox_projected_device(d.gdesc, d.asm_buf, d.gres, b.desc.as<covt_bbox_desc>(), n,
+                                                         b.buf.as<uint8_t>(), b.res.as<covt_bbox_result>(), xf, g.kinds, s);
+            if (st == COVT_OK && size)
+                st = covt_geometry_measures_device(d.out, d.gdesc, d.asm_buf, d.gres, m.desc.as<covt_measures_desc>(), n,
+                                                   m.buf.as<uint8_t>(), m.res.as<covt_measures_result>(), s);
+            if (st == COVT_OK && pred)
+                st = covt_select_predicate_device(b.desc.as<covt_bbox_desc>(), b.buf.as<uint8_t>(),
+                                                  b.res.as<covt_bbox_result>(), m.desc.as<covt_measures_desc>(),
+                                                  m.buf.as<uint8_t>(), m.res.as<covt_measures_result>(), sdesc, n, pred,
+                                                  buf, s);
+            if (st == COVT_OK)
+                st = covt_select_where_device(pr.desc.as<covt_prop_desc>(), pr.buf.as<uint8_t>(),
+                                              pr.res.as<covt_prop_result>(), np, sdesc, n, d_where.as<covt_where>(),
+                                              d_bind.as<int32_t>(), pred ? COVT_WHERE_AND : COVT_WHERE_WRITE, buf,
+                                              d_wst.as<int32_t>(), s);
+            if (st == COVT_OK)
+                st = covt_geometry_select_device(w.desc.as<covt_wkb_desc>(), w.buf.as<uint8_t>(),
+                                                 w.res.as<covt_wkb_result>(), sdesc, n, buf, sres, s);
+            if (st == COVT_OK && n &&
+                hipMemcpyAsync(wst.data(), d_wst.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess)
+                st = COVT_ERR_DEVICE;
+            return st;
+        });
+    if (rc == COVT_OK && host_where_status)
+        for (size_t k = 0; k < ng; ++k) host_where_status[k] = wst[(size_t)p->sinfo[k].desc_index];
+    return rc;
 }
 
 int64_t covt_plan_simplify_bytes(const covt_plan* p) { return p ? p->simplify_bytes : 0; }

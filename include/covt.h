@@ -725,8 +725,9 @@ int covt_plan_bbox_projected_host(const covt_plan* plan, const uint8_t* bytes, u
  * the bounding-box and measures results.
  * A NaN in window, min_area or min_length, an unknown flag bit or a wrong `size` makes a call return
  * COVT_ERR_INVALID_ARG.
- * Out of scope: compacted copies of the fixed-width columns (sel indexes them), clipping to the window,
- * predicates over property values beyond a caller-written mask, any spatial index.
+ * Out of scope: compacted copies of the fixed-width columns (sel indexes them), clipping to the window, any
+ * spatial index.  Predicates over property values are the where pass ("Property predicates" below), which
+ * writes these masks or ANDs into them.
  * ------------------------------------------------------------------------- */
 #define COVT_SELECT_TOO_LARGE 0x1 /* covt_select_desc.flags: set exactly where COVT_WKB_TOO_LARGE is */
 
@@ -1010,6 +1011,159 @@ int64_t covt_scratch_blocks(void);
  * host_props: covt_plan_property_bytes bytes; host_pres: one result per (sub)column in tile order. */
 int covt_plan_properties_host(const covt_plan* plan, const uint8_t* bytes, uint64_t n_bytes, uint8_t* host_props,
                               covt_prop_result* host_pres);
+
+/* ---------------------------------------------------------------------------
+ * Property predicates: the *where* pass.  A conjunction of clauses over named property (sub)columns, evaluated
+ * per feature on the device over the materialized property columns (covt_materialize_properties_device), which
+ * writes the keep masks covt_geometry_select_device consumes, or ANDs into them: `class in (motorway, trunk)`,
+ * `rank <= 3`, `name:de is null`.
+ *
+ * The predicate (covt_where) is one flat POD, filled on the host (covt_where_init, covt_where_add_clause) and
+ * copied to the device by the caller as it lies: clause headers, the literals of all clauses, and one text area
+ * holding the clause names and the string literals.  Values per op: IS_NULL / NOT_NULL 0, EQ .. GE exactly 1,
+ * IN / NOT_IN 1 .. COVT_WHERE_MAX_IN.  A literal carries a set of kinds and one value per kind; it compares only
+ * with a column of one of its kinds.  covt_where_add_clause returns COVT_ERR_INVALID_ARG, and leaves *w byte for
+ * byte as it was, for: a value with no kind bit (or an unknown one), a NaN d, an unknown op or flag, a wrong
+ * number of values, a ninth clause, a 33rd value, text past COVT_WHERE_MAX_TEXT bytes, a *w that is not valid.
+ *
+ * Binding.  A clause names a (sub)column as Plan.property_name spells it: the column name, plus ':' + language
+ * for a localized sub-column.  covt_where_bind is pure host code over the record arrays (a host plan's, or the
+ * copies a device plan hands out): out[g.desc_index * COVT_WHERE_MAX_CLAUSES + k] = the desc_index of the first
+ * property record, in tile order, with tile == g.tile, layer == g.layer and a full name bytewise equal to
+ * clause k's name; -1 when none matches, and for the unused clause slots.  Names are read from `bytes` at
+ * name_off / lang_off; a name that leaves [0, n_bytes) matches nothing.
+ *
+ * Truth of clause k for feature f of geometry column c, bound to property column p = bind[c * 8 + k]:
+ *   Absent (p == -1, or validity bit f of p clear): IS_NULL true, NOT_NULL false, every other op true iff the
+ *     clause has COVT_WHERE_NULL_MATCHES.
+ *   Present: IS_NULL false, NOT_NULL true.  The other ops start from eq(v, L) and lt(v, L) between the value
+ *     and a literal:
+ *       BOOLEAN column: defined iff L has COVT_WHERE_BOOL; eq is v == (L.b != 0); no order.
+ *       INT64 column: defined iff L has COVT_WHERE_INT; int64 comparisons with L.i.
+ *       FLOAT column: defined iff L has COVT_WHERE_REAL; the float32 value widened exactly to double and
+ *         compared with L.d by plain IEEE comparisons (a NaN value equals nothing and is ordered with nothing;
+ *         (double)0.1f == 0.1 is false).
+ *       STRING column: defined iff L has COVT_WHERE_STRING; eq iff the lengths and the bytes are equal, the
+ *         entry being dict_bytes[dict_offsets[v] .. dict_offsets[v + 1]) with the offsets read clamped to
+ *         [0, dict_bytes] (an inverted range is empty); an index outside [0, n_dict) equals nothing; no order.
+ *     An undefined eq or lt is false.  EQ = eq(v, L0), NE = !EQ; LT = lt, LE = lt || eq, GT = lt(L0, v),
+ *     GE = GT || eq (false where undefined, and for a NaN value); IN = any literal equal, NOT_IN = !IN.
+ *   P[f] = the AND over the n_clauses clauses (no clause: true).  COVT_WHERE_WRITE: mask[f] = P;
+ *   COVT_WHERE_AND: mask[f] = (mask[f] != 0 && P) ? 1 : 0.
+ * Column rule.  The whole mask of column c becomes 0, in both modes, and status[c] gets the cause, when for some
+ * clause k (the lowest such k wins): the bind entry lies outside [-1, n_prop_columns) -> COVT_ERR_INVALID_ARG;
+ * the bound column's covt_prop_result.status is not COVT_OK -> that status; the bound column's descriptor
+ * n_features differs from the select descriptor's -> COVT_ERR_INVALID_ARG.  A select descriptor flagged
+ * COVT_SELECT_TOO_LARGE, or with n_features <= 0, writes no mask byte and gets status COVT_OK.
+ *
+ * The kernel reads the blob clamped to its own bounds (n_clauses <= 8, value ranges inside `values`, text ranges
+ * inside `text`), dictionary indices and offsets clamped as above, and the property members as the layout rule
+ * sizes them (every member padded to 16 bytes): whatever the buffers hold, no access leaves the property
+ * slices, the blob, the bind table, the mask members and the status array.  Every mask byte of a live column is
+ * written exactly once; no atomics, no scratch buffer, so the same input gives the same bytes and the pass can
+ * be captured in a HIP graph as it is.
+ * Out of scope: OR / NOT trees; string ordering or prefix match; mixed-kind numeric comparison (an INT-only
+ * literal on a FLOAT column matches nothing, by the rule above); compacted copies of property columns; the Java
+ * binding; building the bind table on the device.
+ * ------------------------------------------------------------------------- */
+#define COVT_WHERE_MAX_CLAUSES 8
+#define COVT_WHERE_MAX_VALUES 32  /* over all clauses */
+#define COVT_WHERE_MAX_TEXT 1024  /* bytes of clause names + string literals */
+#define COVT_WHERE_MAX_IN 16      /* values of one IN / NOT_IN */
+
+#define COVT_WHERE_EQ 0
+#define COVT_WHERE_NE 1
+#define COVT_WHERE_LT 2
+#define COVT_WHERE_LE 3
+#define COVT_WHERE_GT 4
+#define COVT_WHERE_GE 5
+#define COVT_WHERE_IN 6
+#define COVT_WHERE_NOT_IN 7
+#define COVT_WHERE_IS_NULL 8
+#define COVT_WHERE_NOT_NULL 9
+
+#define COVT_WHERE_BOOL 1u /* covt_where_value.kinds: a bit set */
+#define COVT_WHERE_INT 2u
+#define COVT_WHERE_REAL 4u
+#define COVT_WHERE_STRING 8u
+
+#define COVT_WHERE_NULL_MATCHES 1u /* covt_where_clause.flags: an absent value satisfies the clause */
+
+#define COVT_WHERE_WRITE 0 /* mode: mask = P */
+#define COVT_WHERE_AND 1   /* mode: mask = mask && P */
+
+/* One literal of the blob (32 bytes): a value per kind it may be read as. */
+typedef struct covt_where_value {
+    int64_t i;                /* COVT_WHERE_INT */
+    double d;                 /* COVT_WHERE_REAL (never NaN) */
+    int32_t str_off, str_len; /* COVT_WHERE_STRING: bytes of covt_where.text */
+    uint32_t kinds;
+    int32_t b;                /* COVT_WHERE_BOOL: false iff 0 */
+} covt_where_value;
+
+/* One clause of the blob (32 bytes). */
+typedef struct covt_where_clause {
+    int32_t op;
+    uint32_t flags;
+    int32_t first_value, n_values; /* its literals: covt_where.values[first_value .. first_value + n_values) */
+    int32_t name_off, name_len;    /* the (sub)column's name in covt_where.text */
+    int32_t reserved[2];
+} covt_where_clause;
+
+/* The predicate (2320 bytes). */
+typedef struct covt_where {
+    uint32_t size, n_clauses, n_values, text_len; /* size: sizeof(covt_where), set by covt_where_init */
+    covt_where_clause clauses[COVT_WHERE_MAX_CLAUSES];
+    covt_where_value values[COVT_WHERE_MAX_VALUES];
+    uint8_t text[COVT_WHERE_MAX_TEXT];
+} covt_where;
+
+/* A literal as covt_where_add_clause takes it (40 bytes): str points at str_len bytes in host memory. */
+typedef struct covt_where_literal {
+    uint32_t kinds;
+    int32_t b;
+    int64_t i;
+    double d;
+    const uint8_t* str;
+    int32_t str_len, reserved;
+} covt_where_literal;
+
+void covt_where_init(covt_where* w); /* size set, no clause, everything else 0 */
+int covt_where_add_clause(covt_where* w, const uint8_t* name, int32_t name_len, int32_t op, uint32_t flags,
+                          const covt_where_literal* literals, int32_t n);
+int covt_where_valid(const covt_where* w); /* 1: what covt_where_add_clause builds; 0 otherwise */
+
+/* The bind table of `w` over geometry records ginfo[n_geom] and property records pinfo[n_props] (both in tile
+ * order), names read from bytes[0, n_bytes): out holds n_geom * COVT_WHERE_MAX_CLAUSES entries.
+ * COVT_ERR_INVALID_ARG for an invalid w, a null array or a desc_index outside [0, n_geom). */
+int covt_where_bind(const covt_where* w, const covt_geom_info* ginfo, int64_t n_geom, const covt_prop_info* pinfo,
+                    int64_t n_props, const uint8_t* bytes, uint64_t n_bytes, int32_t* out);
+/* The same over a host plan's records; COVT_ERR_INVALID_ARG for a plan made without COVT_PLAN_PROPERTIES. */
+int covt_plan_where_bind(const covt_plan* plan, const uint8_t* bytes, uint64_t n_bytes, const covt_where* w,
+                         int32_t* out);
+
+/* The where pass on `hip_stream`, after covt_materialize_properties_device and, with COVT_WHERE_AND, after
+ * whatever wrote the masks, on the same stream: d_pdesc / d_props / d_pres the property descriptors, buffer
+ * and results (n_prop_columns of them), d_sdesc the select descriptors of n_columns geometry columns (launch
+ * order), d_where the blob and d_bind the bind table (n_columns * COVT_WHERE_MAX_CLAUSES) in device memory,
+ * d_select the select buffer (16-byte aligned), d_status n_columns statuses in launch order (may be null).
+ * Asynchronous, no scratch buffer, capturable. */
+int covt_select_where_device(const covt_prop_desc* d_pdesc, const uint8_t* d_props, const covt_prop_result* d_pres,
+                             int64_t n_prop_columns, const covt_select_desc* d_sdesc, int64_t n_columns,
+                             const covt_where* d_where, const int32_t* d_bind, int32_t mode, uint8_t* d_select,
+                             int32_t* d_status, void* hip_stream);
+/* Dictionary entries up to which a STRING clause is evaluated through a match bitmap in LDS: which = 0 a
+ * workgroup per column (batches of at most 4,096 columns), 1 a wave per column. */
+int32_t covt_where_dict_bound(int32_t which);
+
+/* Convenience: covt_plan_select_host with a property predicate: H2D + decode + assembly + property
+ * materialization + WKB and bounding boxes in `crs` + the geometric predicate (pred not null) and the where
+ * pass in AND mode, or (pred null) the where pass in WRITE mode + select + D2H.  host_where_status: one status
+ * per column in tile order (may be null).  The plan must have been made with COVT_PLAN_PROPERTIES; honours
+ * covt_plan_set_simplify. */
+int covt_plan_select_where_host(const covt_plan* plan, const uint8_t* bytes, uint64_t n_bytes, int32_t crs,
+                                const int32_t* tile_zxy, const covt_select_pred* pred, const covt_where* where,
+                                uint8_t* host_select, covt_select_result* host_sres, int32_t* host_where_status);
 
 /* ---- Device-side plan ------------------------------------------------------------------------
  * covt_plan_create's Id / Geometry walk run on the GPU, for tiles already resident in HBM (the host
