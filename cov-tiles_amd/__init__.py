@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import struct
 import subprocess
 from dataclasses import dataclass
 from typing import List, NamedTuple, Optional
@@ -188,6 +189,17 @@ SIMPLIFY_INFO_DTYPE = np.dtype([("tile", np.int32), ("layer", np.int32), ("n_fea
 SIMPLIFY_TOO_LARGE = 0x1
 SIMPLIFY_MAX_SHIFT = 30
 assert SIMPLIFY_DESC_DTYPE.itemsize == 32 and SIMPLIFY_INFO_DTYPE.itemsize == 40
+# geometry as MVT command streams (include/covt.h "Geometry as MVT")
+MVT_DESC_DTYPE = np.dtype([("off", np.int64), ("byte_cap", np.int64), ("n_features", np.int32), ("flags", np.int32),
+                           ("ring_cap", np.int32), ("coord_cap", np.int32)])
+MVT_RESULT_DTYPE = np.dtype([("status", np.int32), ("n_empty", np.int32), ("n_bytes", np.int64)])
+MVT_INFO_DTYPE = np.dtype([("tile", np.int32), ("layer", np.int32), ("n_features", np.int32),
+                           ("desc_index", np.int32), ("off", np.int64), ("byte_cap", np.int64), ("flags", np.int32),
+                           ("ring_cap", np.int32), ("coord_cap", np.int32), ("reserved", np.int32)])
+MVT_TOO_LARGE = 0x1
+MVT_ORIENT = 0x1
+MVT_MAX_SHIFT = 30
+assert MVT_DESC_DTYPE.itemsize == 32 and MVT_INFO_DTYPE.itemsize == 48 and MVT_RESULT_DTYPE.itemsize == 16
 # georeferenced geometry (include/covt.h "Georeferenced geometry")
 CRS_TILE, CRS_WEB_MERCATOR, CRS_CRS84 = 0, 1, 2
 GEO_IDENTITY, GEO_AFFINE, GEO_AFFINE_LAT = 0, 1, 2
@@ -304,6 +316,15 @@ def _where_literal(x) -> WhereLiteral:
     return L
 
 
+class MvtOptions(C.Structure):
+    """covt_mvt_options (include/covt.h "Geometry as MVT"): orient winds polygon rings as MVT 2.1 asks, shift
+    divides the coordinates by 2^shift (a tile of extent E >> shift, after simplify(shift))."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("shift", C.c_int32), ("reserved", C.c_int32)]
+
+    def __init__(self, orient: bool = False, shift: int = 0):
+        super().__init__(C.sizeof(MvtOptions), MVT_ORIENT if orient else 0, int(shift), 0)
+
+
 class Where(C.Structure):
     """covt_where (include/covt.h "Property predicates"): a conjunction of clauses over named property columns,
     ``Where(("class", "in", ["motorway", "trunk"]), ("rank", "<=", 3), ("name:de", "is null"))``.  A clause is
@@ -397,14 +418,15 @@ _SIGNATURES = {
     **_sig(None, [_vp], "covt_plan_options_init", "covt_plan_destroy", "covt_device_plan_destroy"),
     **_sig(_i64, [_vp], "covt_plan_num_streams", "covt_plan_output_bytes", "covt_plan_num_descs",
            "covt_plan_num_geometry_columns", "covt_plan_assembly_bytes", "covt_plan_wkb_bytes", "covt_plan_bbox_bytes",
-           "covt_plan_measures_bytes", "covt_plan_select_bytes", "covt_plan_simplify_bytes",
+           "covt_plan_measures_bytes", "covt_plan_select_bytes", "covt_plan_simplify_bytes", "covt_plan_mvt_bytes",
            "covt_plan_num_property_columns", "covt_plan_property_bytes"),
     **_sig(_int, [_vp, _i64p, _i64p, _i64p], "covt_plan_totals", "covt_device_plan_totals"),
     **_sig(_int, [_vp, _vp], "covt_plan_streams", "covt_plan_descs", "covt_plan_geometry_columns",
            "covt_plan_geometry_descs", "covt_plan_wkb_columns", "covt_plan_wkb_descs", "covt_plan_bbox_columns",
            "covt_plan_bbox_descs", "covt_plan_measures_columns", "covt_plan_measures_descs", "covt_plan_select_columns",
            "covt_plan_select_descs", "covt_plan_simplify_columns", "covt_plan_simplify_descs",
-           "covt_plan_simplified_geometry_descs", "covt_plan_property_columns", "covt_plan_property_descs"),
+           "covt_plan_simplified_geometry_descs", "covt_plan_mvt_columns", "covt_plan_mvt_descs",
+           "covt_plan_property_columns", "covt_plan_property_descs"),
     **_sig(_int, [_vp, _i64p], "covt_plan_desc_streams", "covt_plan_family_counts", "covt_device_plan_family_counts"),
     "covt_plan_tile_status": (_int, [_vp, _i32p]),
     "covt_plan_release_device": (_int, [_vp]),
@@ -441,6 +463,11 @@ _SIGNATURES = {
     "covt_plan_simplify_host": (_int, [_vp, _u8p, _u64, _i32, _vp, _vp, _vp]),
     "covt_plan_set_simplify": (_int, [_vp, _i32, _i32, _vp]),
     "covt_device_plan_simplify": (_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    # geometry as MVT
+    "covt_mvt_options_init": (None, [_vp]),
+    "covt_geometry_mvt_device": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "covt_plan_mvt_host": (_int, [_vp, _u8p, _u64, _vp, _vp, _vp]),
+    "covt_device_plan_mvt": (_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     # georeferenced geometry
     "covt_geo_transform": (_int, [_i32, _i32, _i32, _i32, _i32, _vp]),
     "covt_plan_geometry_extents": (_int, [_vp, _vp]),
@@ -456,17 +483,18 @@ _SIGNATURES = {
     **_sig(_i64, [_vp], "covt_device_plan_num_streams", "covt_device_plan_num_descs", "covt_device_plan_output_bytes",
            "covt_device_plan_num_geometry_columns", "covt_device_plan_assembly_bytes", "covt_device_plan_wkb_bytes",
            "covt_device_plan_bbox_bytes", "covt_device_plan_measures_bytes", "covt_device_plan_select_bytes",
-           "covt_device_plan_simplify_bytes", "covt_device_plan_num_property_columns", "covt_device_plan_property_bytes"),
+           "covt_device_plan_simplify_bytes", "covt_device_plan_mvt_bytes", "covt_device_plan_num_property_columns", "covt_device_plan_property_bytes"),
     **_sig(_vp, [_vp], "covt_device_plan_descs_device", "covt_device_plan_streams_device",
            "covt_device_plan_tile_status_device", "covt_device_plan_order_device",
            "covt_device_plan_geometry_descs_device", "covt_device_plan_wkb_descs_device",
            "covt_device_plan_bbox_descs_device", "covt_device_plan_measures_descs_device", "covt_device_plan_select_descs_device",
            "covt_device_plan_simplify_descs_device", "covt_device_plan_simplified_geometry_descs_device",
+           "covt_device_plan_mvt_descs_device",
            "covt_device_plan_property_descs_device"),
     "covt_device_plan_copy": (_int, [_vp, _vp, _vp, _i32p]),
     **_sig(_int, [_vp, _vp, _vp], "covt_device_plan_geometry_copy", "covt_device_plan_wkb_copy",
            "covt_device_plan_bbox_copy", "covt_device_plan_measures_copy", "covt_device_plan_select_copy",
-           "covt_device_plan_simplify_copy", "covt_device_plan_property_copy"),
+           "covt_device_plan_simplify_copy", "covt_device_plan_mvt_copy", "covt_device_plan_property_copy"),
     "covt_device_plan_geometry": (_int, [_vp, _vp]),
     "covt_device_plan_decode": (_int, [_vp, _vp, _vp, _vp, _vp]),
     **_sig(_int, [_vp] * 6, "covt_device_plan_assemble", "covt_device_plan_bbox", "covt_device_plan_select"),
@@ -775,6 +803,8 @@ _PRODUCTS = {
     "simplify": _Product("num_geometry_columns", "simplify_bytes", "spdescs", "simplify", SIMPLIFY_INFO_DTYPE,
                          SIMPLIFY_DESC_DTYPE, SIMPLIFY_DESC_DTYPE.itemsize, GEOM_RESULT_DTYPE, ("int32", 4), False, True,
                          ("d_spdesc", "d_simplify", "d_sgres")),
+    "mvt": _Product("num_geometry_columns", "mvt_bytes", "mvdescs", "mvt", MVT_INFO_DTYPE, MVT_DESC_DTYPE,
+                    MVT_DESC_DTYPE.itemsize, MVT_RESULT_DTYPE, ("int64", 2), False, True, ("d_mvdesc", "d_mvt", "d_mvres")),
     "property": _Product("num_property_columns", "property_bytes", "pdescs", "props", PROP_INFO_DTYPE, PROP_DESC_DTYPE,
                          PROP_DESC_DTYPE.itemsize, PROP_RESULT_DTYPE, ("int32", 2), True, False,
                          ("d_pdesc", "d_props", "d_pres")),
@@ -881,6 +911,13 @@ class Plan:
             L.covt_plan_simplify_columns(h, self.simplify.ctypes.data)
             L.covt_plan_simplify_descs(h, self.spdescs.ctypes.data)
             L.covt_plan_simplified_geometry_descs(h, self.sgdescs.ctypes.data)
+        # geometry as MVT (include/covt.h "Geometry as MVT"): one column per geometry column
+        self.mvt_bytes = int(L.covt_plan_mvt_bytes(h))
+        self.mvt = np.zeros(self.num_geometry_columns, dtype=MVT_INFO_DTYPE)
+        self.mvdescs = np.zeros(self.num_geometry_columns, dtype=MVT_DESC_DTYPE)
+        if self.num_geometry_columns:
+            L.covt_plan_mvt_columns(h, self.mvt.ctypes.data)
+            L.covt_plan_mvt_descs(h, self.mvdescs.ctypes.data)
         # property columns (include/covt.h "Property columns"; plans made with PLAN_PROPERTIES)
         self.num_property_columns = int(L.covt_plan_num_property_columns(h))
         self.property_bytes = int(L.covt_plan_property_bytes(h))
@@ -997,6 +1034,28 @@ class Plan:
         a = buf[o:o + 32 * n].view(np.float64)
         return BboxColumn(a[:n], a[n:2 * n], a[2 * n:3 * n], a[3 * n:], np.array(r["extent"], dtype=np.float64),
                           int(r["n_empty"]))
+
+    def mvt_host(self, opts: Optional["MvtOptions"] = None):
+        """H2D + decode + geometry assembly (+ simplification while set_simplify is set) + MVT encoding + D2H
+        (covt_plan_mvt_host).  Returns (uint8 mvt buffer, results[num_geometry_columns] in tile order); see
+        mvt_column."""
+        opts = opts if opts is not None else MvtOptions()
+        buf = np.zeros(max(self.mvt_bytes, 1), dtype=np.uint8)
+        res = np.zeros(max(self.num_geometry_columns, 1), dtype=MVT_RESULT_DTYPE)
+        _raise(lib().covt_plan_mvt_host(self._h, _ptr(self.blob, C.c_uint8), self.blob.size, C.addressof(opts),
+                                        buf.ctypes.data, res.ctypes.data), "covt_plan_mvt_host")
+        return buf[:self.mvt_bytes], res[:self.num_geometry_columns]
+
+    def mvt_column(self, buf: np.ndarray, res: np.ndarray, c: int) -> "MvtColumn":
+        """Column c (tile order) of an mvt buffer -> MvtColumn (raises on its status)."""
+        q, r = self.mvt[c], res[c]
+        _raise(int(r["status"]), "mvt column %d (tile %d, layer %d)" % (c, q["tile"], q["layer"]))
+        a16 = lambda x: (x + 15) & ~15  # noqa: E731  (covt_mvt_plan.h: every member padded to 16 bytes)
+        o, n = int(q["off"]), int(q["n_features"])
+        oo = o + a16(n)
+        ob = oo + a16(4 * (n + 1))
+        return MvtColumn(buf[o:o + n], buf[oo:oo + 4 * (n + 1)].view(np.int32), buf[ob:ob + int(r["n_bytes"])],
+                         int(r["n_empty"]))
 
     def measures_host(self):
         """H2D + decode + geometry assembly + measures + D2H (covt_plan_measures_host).
@@ -1354,6 +1413,21 @@ class DeviceBatch:
         """(bounding-box bytes, results in tile order) copied to the host (after bbox())."""
         return self._results("bbox")
 
+    def mvt(self, opts: Optional["MvtOptions"] = None, stream=None, simplified: bool = False):
+        """Enqueue the MVT encoding of every assembled geometry column (after assemble() on the same stream).
+        simplified: of the simplified column (after simplify() on the same stream)."""
+        gdesc, col, gres = self._column_source(simplified)
+        self._buffers("mvt")
+        opts = opts if opts is not None else MvtOptions()
+        _raise(lib().covt_geometry_mvt_device(self.d_out.data_ptr(), gdesc, col, gres, self.d_mvdesc.data_ptr(),
+                                              self.plan.num_geometry_columns, C.addressof(opts), self.d_mvt.data_ptr(),
+                                              self.d_mvres.data_ptr(), _stream(stream, self.device)),
+               "covt_geometry_mvt_device")
+
+    def mvt_results(self):
+        """(mvt bytes, mvt results in tile order) copied to the host (after mvt()); see Plan.mvt_column."""
+        return self._results("mvt")
+
     def measures(self, stream=None, simplified: bool = False):
         """Enqueue the measures (area, length, num_coords) of every assembled geometry column (after
         assemble() on the same stream).  simplified: of the simplified column (after simplify())."""
@@ -1587,6 +1661,7 @@ class DevicePlan:
         self.measures_bytes = lib().covt_device_plan_measures_bytes(self._h)
         self.select_bytes = lib().covt_device_plan_select_bytes(self._h)
         self.simplify_bytes = lib().covt_device_plan_simplify_bytes(self._h)
+        self.mvt_bytes = lib().covt_device_plan_mvt_bytes(self._h)
         return self.num_geometry_columns
 
     def geometry_copy(self):
@@ -1733,6 +1808,22 @@ class DevicePlan:
                                                d_simplify.data_ptr(), d_sgres.data_ptr(), _stream(stream, self.device)),
                "covt_device_plan_simplify")
 
+    def mvt_copy(self):
+        """(mvt records in tile order, descriptors in launch order) as host arrays (Plan.mvt / Plan.mvdescs)."""
+        return self._copy("mvt", "covt_device_plan_mvt_copy")
+
+    def alloc_mvt(self):
+        """(mvt buffer, mvt results) on the device, sized for this plan's geometry columns."""
+        return self._alloc("mvt")
+
+    def mvt(self, d_out, d_asm, d_gres, opts, d_mvt, d_mvres, stream=None, simplified: bool = False):
+        """Enqueue the MVT encoding over this plan's descriptors (after assemble() on the same stream; simplified:
+        after simplify(), d_asm / d_gres its buffer and results); results in launch order."""
+        opts = opts if opts is not None else MvtOptions()
+        _raise(lib().covt_device_plan_mvt(self._h, d_out.data_ptr(), d_asm.data_ptr(), d_gres.data_ptr(),
+                                          1 if simplified else 0, C.addressof(opts), d_mvt.data_ptr(), d_mvres.data_ptr(),
+                                          _stream(stream, self.device)), "covt_device_plan_mvt")
+
     def simplified_geometry_descs_device(self) -> int:
         """Device address of the geometry descriptors that name the simplified columns (launch order)."""
         self.geometry()
@@ -1824,6 +1915,25 @@ class WkbColumn:
     "Geometry as WKB"): int32 offsets [n + 1] into data; feature i is data[offsets[i]:offsets[i + 1]]."""
     offsets: np.ndarray
     data: np.ndarray
+
+    def __len__(self) -> int:
+        return int(self.offsets.size) - 1
+
+    def feature(self, i: int) -> bytes:
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        return bytes(self.data[int(self.offsets[i]):int(self.offsets[i + 1])])
+
+
+@dataclass
+class MvtColumn:
+    """One geometry column as MVT geometry (include/covt.h "Geometry as MVT"): per feature its GeomType (types,
+    uint8: 1 point, 2 line, 3 polygon) and the payload of Feature.geometry, an Arrow binary column: int32 offsets
+    [n + 1] into data; feature i is data[offsets[i]:offsets[i + 1]], empty for a feature without a coordinate."""
+    types: np.ndarray
+    offsets: np.ndarray
+    data: np.ndarray
+    n_empty: int = 0
 
     def __len__(self) -> int:
         return int(self.offsets.size) - 1
@@ -1928,6 +2038,7 @@ class LayerColumns:
     measures: Optional["MeasuresColumn"] = None  # their area, length and num_coords, in tile pixels whatever the crs
     selected: Optional["SelectedColumn"] = None  # decode_covt(select=...): the features the predicate keeps
     simplified: Optional["GeoArrowGeometry"] = None  # decode_covt(simplify=shift): the simplified column
+    mvt: Optional["MvtColumn"] = None  # decode_covt(mvt=MvtOptions): the geometries as MVT command streams
 
 
 _GEOM_FIELD = {GEOMETRY_TYPES: "geometryTypes", GEOMETRY_OFFSETS: "geometryOffsets", PART_OFFSETS: "partOffsets",
@@ -1957,7 +2068,7 @@ class CovtParser:
     def decode_covt(covt_buffer: bytes, fmt: int = FORMAT_GENC, id_mode: int = ID_FORMAT,
                     properties: bool = False, tile_id=None, crs: int = CRS_TILE,
                     select: Optional[SelectPred] = None, simplify: Optional[int] = None,
-                    where: Optional["Where"] = None) -> List[LayerColumns]:
+                    where: Optional["Where"] = None, mvt: Optional["MvtOptions"] = None) -> List[LayerColumns]:
         """CovtParser.decodeCovt (CovtParser.java:53-133) decoded on the GPU: Id + Geometry columns, and with
         ``properties`` every property column as a PropertyColumn (LayerColumns.properties, by name).
         ``tile_id`` = (z, x, y) and ``crs`` give every layer's wkb / bbox in that CRS (LayerColumns.crs).
@@ -1967,7 +2078,9 @@ class CovtParser:
         the grid of 2^shift tile pixels, and that column as LayerColumns.simplified; None: no simplification.
         ``where``, a Where, keeps in LayerColumns.selected only the features whose properties satisfy it (with
         ``select`` both must hold); it implies the property plan, and a layer without a named column sees that
-        clause's values as absent."""
+        clause's values as absent.
+        ``mvt``, an MvtOptions, gives every layer's geometries as MVT command streams (LayerColumns.mvt), from the
+        simplified column when ``simplify`` is given; mvt_layer_bytes and mvt_tile_bytes wrap them into a tile."""
         if crs != CRS_TILE and tile_id is None:
             raise IllegalArgumentException("a CRS other than CRS_TILE needs the tile's (z, x, y)")
         geo = (crs, [tile_id]) if crs != CRS_TILE else (None, None)
@@ -2001,6 +2114,12 @@ class CovtParser:
                 lc = by_layer.get(int(plan.measures["layer"][c]))
                 if lc is not None and int(mres["status"][c]) == OK:  # (a failed column keeps measures = None)
                     lc.measures = plan.measures_column(mbuf, mres, c)
+            if mvt is not None:
+                vbuf, vres = plan.mvt_host(mvt)
+                for c in range(plan.num_geometry_columns):
+                    lc = by_layer.get(int(plan.mvt["layer"][c]))
+                    if lc is not None and int(vres["status"][c]) == OK:  # (a failed column keeps mvt = None)
+                        lc.mvt = plan.mvt_column(vbuf, vres, c)
             if select is not None or where is not None:
                 sbuf, sres = plan.select_host(select, *geo, where=where)
                 for c in range(plan.num_geometry_columns):
@@ -2021,6 +2140,77 @@ class CovtParser:
         return layers
 
 
+# ---- MVT tile writer (host side, the framing of vector_tile.proto 2.1 around the device's command streams) ----
+def _pb_varint(v: int) -> bytes:
+    out = bytearray()
+    while v >= 0x80:
+        out.append((v & 0x7F) | 0x80)
+        v >>= 7
+    out.append(v)
+    return bytes(out)
+
+
+def _pb_bytes(field: int, payload: bytes) -> bytes:
+    return _pb_varint(field << 3 | 2) + _pb_varint(len(payload)) + payload
+
+
+def _mvt_value(ptype: int, v) -> bytes:
+    """A Tile.Value message: STRING string_value, FLOAT float_value, INT64 uint_value (>= 0) or sint_value,
+    BOOLEAN bool_value."""
+    if ptype == PROP_STRING:
+        return _pb_bytes(1, v.encode("utf-8"))
+    if ptype == PROP_FLOAT:
+        return b"\x15" + struct.pack("<f", v)
+    if ptype == PROP_INT64:
+        return b"\x28" + _pb_varint(v) if v >= 0 else b"\x30" + _pb_varint(((v << 1) ^ (v >> 63)) & 0xFFFFFFFFFFFFFFFF)
+    return b"\x38" + (b"\x01" if v else b"\x00")
+
+
+def mvt_layer_bytes(name: str, extent: int, column: "MvtColumn", ids=None, properties=None, index=None) -> bytes:
+    """One complete Tile.layers entry (the field-3 record) of an MVT 2.1 tile around an MvtColumn: version 2,
+    name, features, keys, values, extent.  A feature carries its id (when ``ids`` is given), its packed tags
+    (when it has any), its type and its geometry; features with an empty value are left out.  ``index`` (for
+    example LayerColumns.selected.index) restricts and orders the features written.  ``properties``: a dict
+    of PropertyColumns (LayerColumns.properties) or a sequence of them, one key per (sub)column in that order;
+    a feature gets a tag where the validity bit is set.  Values are deduplicated by kind and exact value
+    (floats by bit pattern) in first-use order."""
+    props = list(properties.values()) if isinstance(properties, dict) else list(properties or ())
+    values: List[bytes] = []
+    value_index: dict = {}
+    feats = bytearray()
+    for i in (range(len(column)) if index is None else (int(k) for k in index)):
+        geom = column.feature(i)
+        if not geom:
+            continue
+        f = bytearray()
+        if ids is not None:
+            f += b"\x08" + _pb_varint(int(ids[i]) & 0xFFFFFFFFFFFFFFFF)
+        tags = bytearray()
+        for k, pc in enumerate(props):
+            v = pc.value(i)
+            if v is None:
+                continue
+            enc = _mvt_value(pc.type, v)
+            j = value_index.get(enc)
+            if j is None:
+                j = value_index[enc] = len(values)
+                values.append(enc)
+            tags += _pb_varint(k) + _pb_varint(j)
+        if tags:
+            f += _pb_bytes(2, bytes(tags))
+        f += b"\x18" + _pb_varint(int(column.types[i])) + _pb_bytes(4, geom)
+        feats += _pb_bytes(2, bytes(f))
+    layer = (b"\x78\x02" + _pb_bytes(1, name.encode("utf-8")) + bytes(feats)
+             + b"".join(_pb_bytes(3, pc.name.encode("utf-8")) for pc in props)
+             + b"".join(_pb_bytes(4, v) for v in values) + b"\x28" + _pb_varint(int(extent)))
+    return _pb_bytes(3, layer)
+
+
+def mvt_tile_bytes(layers) -> bytes:
+    """A complete MVT tile: the concatenation of mvt_layer_bytes records."""
+    return b"".join(layers)
+
+
 def version() -> str:
     return lib().covt_version().decode()
 
@@ -2029,12 +2219,12 @@ def version() -> str:
 _BUILD_SOURCES = (  # the Makefile's SRC, then its HDR, one to one
     ("csrc/covt_decode.hip", "csrc/covt_assemble.hip", "csrc/covt_props.hip", "csrc/covt_plan_device.hip",
      "csrc/covt_wkb.hip", "csrc/covt_bbox.hip", "csrc/covt_measures.hip", "csrc/covt_select.hip",
-     "csrc/covt_simplify.hip", "csrc/covt_where.hip", "csrc/covt_host.cpp")
+     "csrc/covt_simplify.hip", "csrc/covt_where.hip", "csrc/covt_mvt.hip", "csrc/covt_host.cpp")
     + ("../include/covt.h", "csrc/covt_internal.h", "csrc/covt_wave.h", "csrc/covt_segscan.h", "csrc/covt_walk.h",
        "csrc/covt_props_plan.h",
        "csrc/covt_scratch.h", "csrc/covt_coop.h", "csrc/covt_wkb_plan.h", "csrc/covt_bbox_plan.h",
        "csrc/covt_measures_plan.h", "csrc/covt_select_plan.h", "csrc/covt_simplify_plan.h", "csrc/covt_geo_plan.h", "csrc/covt_arena.h", "csrc/covt_split_plan.h",
-       "csrc/covt_container.h", "csrc/covt_where_plan.h"))
+       "csrc/covt_container.h", "csrc/covt_where_plan.h", "csrc/covt_mvt_plan.h"))
 
 
 def source_build_id() -> str:

@@ -30,6 +30,7 @@
 #include "covt_measures_plan.h"
 #include "covt_select_plan.h"
 #include "covt_where_plan.h"
+#include "covt_mvt_plan.h"
 #include "covt_simplify_plan.h"
 #include "covt_geo_plan.h"
 
@@ -602,6 +603,9 @@ struct covt_plan {
     std::vector<covt_simplify_info> spinfo;   // simplify columns, tile order (one per geometry column)
     std::vector<covt_simplify_desc> spdescs;  // launch order (that of gdescs)
     int64_t simplify_bytes = 0;
+    std::vector<covt_mvt_info> mvinfo;        // mvt columns, tile order (one per geometry column)
+    std::vector<covt_mvt_desc> mvdescs;       // launch order (that of gdescs)
+    int64_t mvt_bytes = 0;
     bool simplify_on = false;                 // covt_plan_set_simplify: the host conveniences read the simplified column
     int32_t simplify_shift = 0;               //   its uniform shift, or
     std::vector<int32_t> simplify_col_shift;  //   one per column in launch order (empty: uniform)
@@ -826,6 +830,21 @@ void plan_simplify(covt_plan* p) {
         [](covt_simplify_info& r, const covt_simplify_desc& d) {
             r.off = d.off;
             r.part_cap = d.part_cap;
+            r.ring_cap = d.ring_cap;
+            r.coord_cap = d.coord_cap;
+        });
+}
+
+// MVT columns (include/covt.h "Geometry as MVT"): slices in a buffer of their own (covt_mvt_plan.h).
+void plan_mvt(covt_plan* p) {
+    p->mvt_bytes = plan_geometry_product(
+        p, p->mvinfo, p->mvdescs,
+        [](const covt_geom_info& g, int64_t off, covt_mvt_desc& d) {
+            return mvt_column_layout(g.n_features, g.ring_cap, g.coord_cap, (uint32_t)g.flags, off, d);
+        },
+        [](covt_mvt_info& r, const covt_mvt_desc& d) {
+            r.off = d.off;
+            r.byte_cap = d.byte_cap;
             r.ring_cap = d.ring_cap;
             r.coord_cap = d.coord_cap;
         });
@@ -1482,6 +1501,7 @@ int covt_plan_create_opts(const uint8_t* bytes, const uint64_t* tile_offsets, co
     plan_measures(p);
     plan_select(p);
     plan_simplify(p);
+    plan_mvt(p);
     plan_property_layout(p);
     *out = p;
     return COVT_OK;
@@ -2204,6 +2224,22 @@ int covt_plan_simplify_host(const covt_plan* p, const uint8_t* bytes, uint64_t n
             return covt_geometry_simplify_device(d.out, d.gdesc, d.asm_buf, d.gres, sdesc, n, shift,
                                                  tile_shift ? d_cs.as<int32_t>() : nullptr, buf, gres, s);
         });
+}
+
+int64_t covt_plan_mvt_bytes(const covt_plan* p) { return p ? p->mvt_bytes : 0; }
+int covt_plan_mvt_columns(const covt_plan* p, covt_mvt_info* out) { return copy_records(p ? &p->mvinfo : nullptr, out); }
+int covt_plan_mvt_descs(const covt_plan* p, covt_mvt_desc* out) { return copy_records(p ? &p->mvdescs : nullptr, out); }
+
+// decode, assembly (simplify while covt_plan_set_simplify is set), mvt
+int covt_plan_mvt_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, const covt_mvt_options* opts,
+                       uint8_t* host_mvt, covt_mvt_result* host_mvres) {
+    if (!p || !mvt_options_valid(opts)) return COVT_ERR_INVALID_ARG;
+    return plan_product_host(p, bytes, n_bytes, p->mvinfo, p->mvdescs, p->mvt_bytes, host_mvt, host_mvres, true,
+                             [opts](const PlanDev& d, const covt_mvt_desc* mdesc, int64_t n, uint8_t* buf,
+                                    covt_mvt_result* mres, hipStream_t s) {
+                                 return covt_geometry_mvt_device(d.out, d.gdesc, d.asm_buf, d.gres, mdesc, n, opts, buf,
+                                                                 mres, s);
+                             });
 }
 
 int64_t covt_plan_num_property_columns(const covt_plan* p) { return p ? (int64_t)p->pinfo.size() : 0; }

@@ -72,7 +72,7 @@ struct SumV {
 
 // the edge term from (x0, y0) to (x1, y1)
 __device__ __forceinline__ MsSum ms_edge(int32_t x0, int32_t y0, int32_t x1, int32_t y1) {
-    const uint64_t s = (uint64_t)((int64_t)x0 * (int64_t)y1) - (uint64_t)((int64_t)x1 * (int64_t)y0);
+    const uint64_t s = shoelace_term(x0, y0, x1, y1);
     const double dx = (double)x1 - (double)x0, dy = (double)y1 - (double)y0;  // (exact)
     return MsSum{s, sqrt(dx * dx + dy * dy)};
 }

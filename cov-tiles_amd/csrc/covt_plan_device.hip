@@ -43,6 +43,7 @@
 #include "covt_bbox_plan.h"
 #include "covt_measures_plan.h"
 #include "covt_select_plan.h"
+#include "covt_mvt_plan.h"
 #include "covt_simplify_plan.h"
 
 struct covt_device_plan {
@@ -75,6 +76,9 @@ struct covt_device_plan {
     covt_simplify_info* d_spinfo = nullptr;
     covt_simplify_desc* d_spdesc = nullptr;
     covt_geom_desc* d_sgdesc = nullptr;
+    int64_t mvt_bytes = 0;         // mvt columns (likewise)
+    covt_mvt_info* d_mvinfo = nullptr;
+    covt_mvt_desc* d_mvdesc = nullptr;
     void* prop_arena = nullptr;    // property columns (COVT_PLAN_PROPERTIES): records, infos, descriptors
     void* scratch = nullptr;       // creation-time scratch (the property walk's record slots), freed on the way
     int64_t n_props = 0, prop_bytes = 0;
@@ -2198,6 +2202,19 @@ struct SimplifyProduct {  // covt_simplify_plan.h
         r.coord_cap = d.coord_cap;
     }
 };
+struct MvtProduct {  // covt_mvt_plan.h
+    using Info = covt_mvt_info;
+    using Desc = covt_mvt_desc;
+    static __device__ int64_t layout(const covt_geom_info& g, int64_t off, Desc& d) {
+        return mvt_column_layout(g.n_features, g.ring_cap, g.coord_cap, (uint32_t)g.flags, off, d);
+    }
+    static __device__ void fill(Info& r, const Desc& d) {
+        r.off = d.off;
+        r.byte_cap = d.byte_cap;
+        r.ring_cap = d.ring_cap;
+        r.coord_cap = d.coord_cap;
+    }
+};
 // the geometry descriptors of the simplified columns (covt_plan_simplified_geometry_descs), launch order
 __global__ void simplified_descs(const covt_geom_desc* __restrict__ gdesc, const covt_simplify_desc* __restrict__ sdesc,
                                  int64_t nc, covt_geom_desc* __restrict__ out) {
@@ -2824,6 +2841,7 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     const ProductSlice<MeasuresProduct> a_measures(L, m);
     const ProductSlice<SelectProduct> a_select(L, m);
     const ProductSlice<SimplifyProduct> a_simplify(L, m);
+    const ProductSlice<MvtProduct> a_mvt(L, m);
     const auto a_sgd = L.take<covt_geom_desc>(m);
     // the arena is the plan's only on success: a failed build frees it (a retry allocates afresh)
     StreamFree arena{nullptr, s};
@@ -2836,6 +2854,7 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     uint8_t* cscan = a_cs.at(g);
     HIP_TRY(hipMemsetAsync(colbytes, 0, (m + 1) * 8, s));
     int64_t asm_bytes = 0, wkb_bytes = 0, bbox_bytes = 0, measures_bytes = 0, select_bytes = 0, simplify_bytes = 0;
+    int64_t mvt_bytes = 0;
     if (nc > 0) {
         geom_columns<<<(int)((ns + 255) / 256), 256, 0, s>>>(p->d_info, ns, p->format, gst, gpos, p->d_ginfo, colbytes);
         HIP_TRY(hipGetLastError());
@@ -2858,6 +2877,8 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
         st = plan_product(a_select, g, m, nc, p->d_ginfo, cscan, cscan_tmp, s, p->d_sinfo, p->d_sdesc, &select_bytes);
     if (st == COVT_OK)
         st = plan_product(a_simplify, g, m, nc, p->d_ginfo, cscan, cscan_tmp, s, p->d_spinfo, p->d_spdesc, &simplify_bytes);
+    if (st == COVT_OK)
+        st = plan_product(a_mvt, g, m, nc, p->d_ginfo, cscan, cscan_tmp, s, p->d_mvinfo, p->d_mvdesc, &mvt_bytes);
     if (st) return st;
     p->d_sgdesc = a_sgd.at(g);
     if (nc > 0) {
@@ -2876,6 +2897,7 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     p->measures_bytes = measures_bytes;
     p->select_bytes = select_bytes;
     p->simplify_bytes = simplify_bytes;
+    p->mvt_bytes = mvt_bytes;
     p->geo_built = true;
     return COVT_OK;
 }
@@ -2993,6 +3015,24 @@ int covt_device_plan_simplify(covt_device_plan* p, const uint8_t* d_decoded, con
     if (st) return st;
     return covt_geometry_simplify_device(d_decoded, p->d_gdesc, d_asm, d_gres, p->d_spdesc, p->n_geo, shift, d_shift,
                                          d_simplify, d_gres_out, hip_stream);
+}
+
+int64_t covt_device_plan_mvt_bytes(const covt_device_plan* p) { return p && p->geo_built ? p->mvt_bytes : 0; }
+const covt_mvt_desc* covt_device_plan_mvt_descs_device(const covt_device_plan* p) {
+    return p && p->geo_built ? p->d_mvdesc : nullptr;
+}
+int covt_device_plan_mvt_copy(const covt_device_plan* p, covt_mvt_info* infos, covt_mvt_desc* descs) {
+    if (!p || !p->geo_built) return COVT_ERR_INVALID_ARG;
+    return copy_to_host(p->n_geo, infos, p->d_mvinfo, descs, p->d_mvdesc);
+}
+int covt_device_plan_mvt(covt_device_plan* p, const uint8_t* d_decoded, const uint8_t* d_asm,
+                         const covt_geom_result* d_gres, int32_t simplified, const covt_mvt_options* opts,
+                         uint8_t* d_mvt, covt_mvt_result* d_mvres, void* hip_stream) {
+    if (!p) return COVT_ERR_INVALID_ARG;
+    const int st = covt_device_plan_geometry(p, hip_stream);
+    if (st) return st;
+    return covt_geometry_mvt_device(d_decoded, simplified ? p->d_sgdesc : p->d_gdesc, d_asm, d_gres, p->d_mvdesc, p->n_geo,
+                                    opts, d_mvt, d_mvres, hip_stream);
 }
 
 int covt_device_plan_assemble(covt_device_plan* p, const uint8_t* d_decoded, const covt_stream_result* d_res,

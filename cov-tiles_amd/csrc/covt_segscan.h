@@ -114,6 +114,13 @@ __device__ __forceinline__ GeomCol geom_col(const covt_geom_desc& gd, const covt
     return c;
 }
 
+// The int64 policy of a ring's doubled signed area S_r (include/covt.h "Geometry measures"; the winding of
+// "Geometry as MVT"): the edge from (x0, y0) to (x1, y1) adds x0 * y1 - x1 * y0, every product exact in int64,
+// the sum taken mod 2^64.
+__host__ __device__ __forceinline__ uint64_t shoelace_term(int32_t x0, int32_t y0, int32_t x1, int32_t y1) {
+    return (uint64_t)((int64_t)x0 * (int64_t)y1) - (uint64_t)((int64_t)x1 * (int64_t)y0);
+}
+
 // a product column's status before any work: that of the pass it reads (`upstream`), then the layout's
 // (too_large, off_ok: the descriptors' flags and offsets; n_ok: planned for the rows its input has)
 __device__ __forceinline__ int32_t product_precheck(int32_t upstream, bool too_large, bool off_ok, bool n_ok) {

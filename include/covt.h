@@ -900,6 +900,114 @@ int covt_plan_simplify_host(const covt_plan* plan, const uint8_t* bytes, uint64_
 int covt_plan_set_simplify(covt_plan* plan, int32_t enabled, int32_t shift, const int32_t* tile_shift);
 
 /* ---------------------------------------------------------------------------
+ * Geometry as MVT: per feature the payload of a Mapbox Vector Tile Feature.geometry (field 4: packed uint32
+ * varints, the command stream of the MVT 2.1 specification, section 4.3) and its GeomType, what a tile server
+ * sends to MapLibre, OpenLayers, QGIS or ogr2ogr.  A host-side writer (the Python package's mvt_layer_bytes)
+ * wraps the values, ids and property columns into layers; nothing of the protobuf framing is made on the device.
+ *
+ * Input: an assembled column (n features, P parts, R rings, V coordinates, offsets read clamped as every product
+ * reads them), the types t_f of its GeometryTypes stream and covt_mvt_options {flags, shift}.  All arithmetic is
+ * integer, so every byte is exact.
+ *
+ *   Coordinates.  q_i = (x_i >> s, y_i >> s), an arithmetic shift, s = shift in [0, COVT_MVT_MAX_SHIFT]: s = 0 for
+ *     a tile at the layer's extent; after simplify(s), s emits a tile of extent E >> s.  All below is over q.
+ *   Varint.  A uint32 is written as a 1 to 5 byte LEB128 varint.  A parameter is zz(d) = (d << 1) ^ (d >> 31) of
+ *     the int32 difference d between the vertex and the cursor, taken with two's-complement wrap-around, so a
+ *     reader that sums mod 2^32 recovers q exactly.  The cursor is (0, 0) at the start of every feature and the
+ *     last emitted vertex afterwards; ClosePath does not move it.  A command integer is (count << 3) | id with
+ *     MoveTo 1, LineTo 2, ClosePath 7.
+ *   POINT, MULTIPOINT (t 0, 3).  c the feature's coordinate count: nothing if c = 0, else MoveTo(c) and the c
+ *     parameter pairs in column order.
+ *   LINESTRING, MULTILINESTRING (t 1, 4).  Per ring of m coordinates [a, a + m), in order: nothing if m = 0; else
+ *     MoveTo(1) e_0 and, if m > 1, LineTo(m - 1) e_1 .. e_{m-1}, e_j = q_{a+j}.
+ *   POLYGON, MULTIPOLYGON (t 2, 5).  Per ring [a, b), m = b - a: closed = m >= 2 and q_{b-1} == q_a; k = m - closed;
+ *     nothing if k = 0, else MoveTo(1) e_0, LineTo(k - 1) e_1 .. e_{k-1} if k > 1, ClosePath(1).  Without
+ *     COVT_MVT_ORIENT e_j = q_{a+j}, the ring as stored.  With it, S_r is the int64 shoelace of "Geometry
+ *     measures" over q (the sum over i in a .. b - 2 of x_i * y_{i+1} - x_{i+1} * y_i mod 2^64, read as int64); a
+ *     ring is reversed iff it is closed and it is the first ring of its part with S_r < 0 or another ring of its
+ *     part with S_r > 0; a reversed ring emits e_j = q_{b-1-j} (it still starts at q_a = q_{b-1}).  Rings with
+ *     S_r = 0 and rings that are not closed are emitted as stored.  This is the winding rule of MVT 2.1:
+ *     exterior rings positive, interior rings negative in tile coordinates; snapping can flip small rings.
+ *   GeomType.  type[f] = 1 for t 0 or 3, 2 for t 1 or 4, 3 for t 2 or 5, whatever the value's length.
+ *   A feature whose value is empty (no coordinate, or only empty rings) has offsets[f + 1] == offsets[f].
+ *
+ * Per column one slice of the mvt buffer (16-byte aligned start, every member padded to 16 bytes):
+ *
+ *   type[n] uint8 | offsets[n + 1] int32 | bytes[byte_cap] | scratch (contents unspecified)
+ *
+ * byte_cap = 10 * coord_cap + 7 * ring_cap + 5 * n_features always suffices (a coordinate at most two 5-byte
+ * varints, a ring at most MoveTo 1 + LineTo 5 + ClosePath 1, a point feature's MoveTo at most 5), so there is no
+ * capacity status.  A column assembly refuses, or a capacity above INT32_MAX, gets COVT_MVT_TOO_LARGE.
+ *
+ * Result per column: covt_mvt_result {status, n_empty (features with an empty value), n_bytes = offsets[n]; both
+ * 0 unless the status is COVT_OK}.  Every element of the output is written exactly once; there are no atomics
+ * and no allocation, so the pass can be captured in a HIP graph as it is and its bytes do not depend on
+ * scheduling.  Not written: offsets past n + 1, bytes past n_bytes, the padding, and the whole slice of a failed
+ * column.  Every destination is checked against the slice: whatever the input holds, no access leaves the slices.
+ * The values are defined, and free of scheduling, for a well-formed column, which is what assembly and simplify
+ * write: offsets nondecreasing, every ring inside a part of a feature.  A column that is not (rings no part
+ * covers, say) is still read and written inside its slices, but its bytes, offsets and n_bytes are unspecified.
+ * Statuses: a column whose geometry result is not COVT_OK gets that status; COVT_GEOM_TOO_LARGE,
+ * COVT_MVT_TOO_LARGE or a descriptor whose capacities are not the geometry descriptor's -> COVT_ERR_INVALID_ARG
+ * for that column; a shift outside the range, an unknown flag bit or a wrong `size` makes the call return
+ * COVT_ERR_INVALID_ARG.
+ * Out of scope: clipping, compaction of selected features on the device, the protobuf layer, gzip, the Java
+ * binding.
+ * ------------------------------------------------------------------------- */
+#define COVT_MVT_TOO_LARGE 0x1 /* covt_mvt_desc.flags: assembly refuses the column, or its capacity passes INT32_MAX */
+#define COVT_MVT_ORIENT 0x1    /* covt_mvt_options.flags: wind polygon rings as MVT 2.1 asks */
+#define COVT_MVT_MAX_SHIFT 30
+
+/* Options of a call (16 bytes): host memory, read before the call returns. */
+typedef struct covt_mvt_options {
+    uint32_t size;  /* sizeof(covt_mvt_options) */
+    uint32_t flags; /* COVT_MVT_ORIENT */
+    int32_t shift, reserved;
+} covt_mvt_options;
+void covt_mvt_options_init(covt_mvt_options* opts); /* size set, no flags, shift 0 */
+
+/* One device-resident mvt column entry (32 bytes), parallel to covt_geom_desc (launch order). */
+typedef struct covt_mvt_desc {
+    int64_t off;      /* byte offset of the column's slice in the mvt buffer (16-byte aligned) */
+    int64_t byte_cap; /* capacity of bytes[] */
+    int32_t n_features, flags;
+    int32_t ring_cap, coord_cap; /* = covt_geom_desc's: what the slice was sized for */
+} covt_mvt_desc;
+
+/* Host-visible mvt column record of a plan, in tile order (48 bytes); column c belongs to geometry column c.
+ * type[] is at off, offsets[] at off + align16(n_features), bytes[] after the offsets' align16(4 (n_features + 1)). */
+typedef struct covt_mvt_info {
+    int32_t tile, layer, n_features, desc_index; /* desc_index: row in the launch-ordered descriptors */
+    int64_t off, byte_cap;
+    int32_t flags, ring_cap, coord_cap, reserved;
+} covt_mvt_info;
+
+typedef struct covt_mvt_result {
+    int32_t status, n_empty;
+    int64_t n_bytes;
+} covt_mvt_result;
+
+int64_t covt_plan_mvt_bytes(const covt_plan* plan); /* size of the mvt buffer */
+int covt_plan_mvt_columns(const covt_plan* plan, covt_mvt_info* out); /* tile order, num_geometry_columns */
+int covt_plan_mvt_descs(const covt_plan* plan, covt_mvt_desc* out);   /* launch order (= covt_plan_geometry_descs) */
+
+/* Encode every assembled geometry column on `hip_stream`, after covt_assemble_geometry_device on the same stream:
+ * d_decoded the decode output (GeometryTypes are read from it), d_gdesc / d_asm / d_gres the assembly's
+ * descriptors, output and results (or covt_plan_simplified_geometry_descs, the simplify buffer and the simplify
+ * results: the simplified column), d_mvdesc the mvt descriptors (same order), d_mvt the mvt buffer of
+ * covt_plan_mvt_bytes bytes (16-byte aligned), d_mvres n_columns results (same order).  Asynchronous; allocates
+ * nothing, capturable. */
+int covt_geometry_mvt_device(const uint8_t* d_decoded, const covt_geom_desc* d_gdesc, const uint8_t* d_asm,
+                             const covt_geom_result* d_gres, const covt_mvt_desc* d_mvdesc, int64_t n_columns,
+                             const covt_mvt_options* opts, uint8_t* d_mvt, covt_mvt_result* d_mvres, void* hip_stream);
+
+/* Convenience: H2D + decode + assembly (+ simplify while covt_plan_set_simplify is set) + mvt + D2H of the whole
+ * plan on the current device.  host_mvt: covt_plan_mvt_bytes bytes; host_mvres: one result per column in tile
+ * order. */
+int covt_plan_mvt_host(const covt_plan* plan, const uint8_t* bytes, uint64_t n_bytes, const covt_mvt_options* opts,
+                       uint8_t* host_mvt, covt_mvt_result* host_mvres);
+
+/* ---------------------------------------------------------------------------
  * Property columns: the GPU replacement for
  * CovtParser.decodePropertyColumn (CovtParser.java:276-354) and getStringDictionary (:367-377).
  * A plan created with COVT_PLAN_PROPERTIES also plans every property column: its present / data /
@@ -1286,6 +1394,18 @@ const covt_geom_desc* covt_device_plan_simplified_geometry_descs_device(const co
 int covt_device_plan_simplify(covt_device_plan* plan, const uint8_t* d_decoded, const uint8_t* d_asm,
                               const covt_geom_result* d_gres, int32_t shift, const int32_t* d_shift,
                               uint8_t* d_simplify, covt_geom_result* d_gres_out, void* hip_stream);
+/* MVT columns from a device plan: the records and descriptors of covt_plan_mvt_columns / covt_plan_mvt_descs,
+ * built on the device next to the simplify records (the host plan's exactly); 0 / NULL before
+ * covt_device_plan_geometry. */
+int64_t covt_device_plan_mvt_bytes(const covt_device_plan* plan);
+const covt_mvt_desc* covt_device_plan_mvt_descs_device(const covt_device_plan* plan);
+int covt_device_plan_mvt_copy(const covt_device_plan* plan, covt_mvt_info* infos, covt_mvt_desc* descs);
+/* covt_geometry_mvt_device over the plan's descriptors, after covt_device_plan_assemble (simplified != 0: after
+ * covt_device_plan_simplify, d_asm / d_gres its buffer and results) on the same stream: d_mvt
+ * covt_device_plan_mvt_bytes bytes, d_mvres one result per column in launch order. */
+int covt_device_plan_mvt(covt_device_plan* plan, const uint8_t* d_decoded, const uint8_t* d_asm,
+                         const covt_geom_result* d_gres, int32_t simplified, const covt_mvt_options* opts,
+                         uint8_t* d_mvt, covt_mvt_result* d_mvres, void* hip_stream);
 /* Property columns from a device plan made with COVT_PLAN_PROPERTIES in opts->flags: the records,
  * output layout and largest-first descriptors of covt_plan_property_columns / covt_plan_property_descs,
  * built on the device with the plan (the host plan's exactly); a plan without the flag has none. */
