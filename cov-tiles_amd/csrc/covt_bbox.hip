@@ -36,8 +36,6 @@ namespace covt {
 constexpr int kBboxWin = 512;    // start() values of consecutive features staged in LDS per wave
 constexpr int kBboxAhead = 320;  // window entries wanted past the first open feature at a chunk's start
 
-typedef __attribute__((address_space(1))) double gw_f64;
-
 // a box: (xmin, ymin, xmax, ymax) in the int32 domain, joined by min / max
 struct BoxV {
     typedef i32x4 T;

@@ -7,14 +7,11 @@
 // replays the pass as it is and the bytes do not depend on scheduling):
 //
 //   1. init: the column's status (the assembly's, then the layout's).
-//   2. rings: the segmented reduction of covt_segscan.h (the chunks, the runs and their owners, the hand-over
-//      to the workgroup: described there) under RingPolicy: the segments are the rings, read from ring[]
-//      directly, the value is (S, length) under addition, a chunk is one row of 128 coordinates (16 bytes a
-//      lane), and a coordinate's term is its edge to the next one -- the lane takes it from its neighbour (DPP)
-//      -- x_i * y_{i+1} - x_{i+1} * y_i in int64 (mod 2^64) and sqrt(dx * dx + dy * dy) in float64, both zero
-//      where the next coordinate starts another ring or the column ends (so heads are marked up to and
-//      including the chunk's end).  A ring's (S_r, length) goes to the column's scratch; the workgroup's
-//      partial sums are added in a fixed order.
+//   2. rings: the segmented reduction of covt_segscan.h over the rings' edges (seg_run under RingEdgePolicy:
+//      the chunks, the runs and their owners, the hand-over to the workgroup and the edge's neighbour fetch
+//      are described there).  The value is (S, length) under addition and an edge's term (MsEdge)
+//      x_i * y_{i+1} - x_{i+1} * y_i in int64 (mod 2^64) and sqrt(dx * dx + dy * dy) in float64.  A ring's
+//      (S_r, length) goes to the column's scratch; the partial sums are added in a fixed order.
 //   3. features: a thread per feature.  Its rings are the one range [part[geo[f]], part[geo[f + 1]]), so with
 //      A = sum of |S_r| over them and H = sum of |S of the first ring| over its non-empty parts, the shell-
 //      minus-holes total is T_f = 2 H - A (mod 2^64, exact).  A feature of fewer than kMsNarrow rings and
@@ -34,12 +31,6 @@ namespace covt {
 
 constexpr int kMsWaves = 4;    // waves per workgroup
 constexpr int kMsNarrow = 64;  // rings or parts from which a feature is finished by the whole wave
-
-typedef __attribute__((address_space(1))) double gw_f64;
-typedef __attribute__((address_space(1))) int64_t gw_i64;
-typedef __attribute__((address_space(1))) int32_t gw_i32;
-typedef __attribute__((address_space(1))) const int64_t g_i64;
-typedef __attribute__((address_space(1))) const double g_f64;
 
 // a partial sum of edge terms: s the doubled signed area mod 2^64, len the length
 struct MsSum {
@@ -93,59 +84,20 @@ __device__ __forceinline__ MsCol ms_column(const covt_geom_desc& gd, const covt_
     return c;
 }
 
-// The rings of a column as the segments of covt_segscan.h.
-struct RingPolicy {
+// what the rings pass supplies to RingEdgePolicy: the coordinates as they are, ms_edge, a ring's two sums
+struct MsEdge {
     typedef SumV V;
-    static constexpr int kWaves = kMsWaves;
-    static constexpr int kRows = 1;     // one row of 64 lanes x 2 coordinates per chunk: 128 coordinates
-    static constexpr int kWide = 2048;  // coordinates left past a run from which the workgroup finishes a ring
-    static constexpr int kIncl = 1;     // an edge's term depends on whether the next coordinate is a head
-    static constexpr int kAhead = 1;
-    struct Raw {
-        i32x4 q;
-        int32_t tx, ty;  // the coordinate after the chunk (uniform)
-    };
-
     const MsCol& c;
-
-    __device__ __forceinline__ int32_t count() const { return c.R; }
-    __device__ __forceinline__ int32_t items() const { return c.V; }
-    __device__ __forceinline__ int32_t first_at(int32_t x) const {
-        return seg_first_at(c.R, x, [&](int32_t r) { return c.ring_at(r); });
-    }
-    __device__ __forceinline__ void open(int32_t) {}
-    __device__ __forceinline__ void ensure(int32_t, int32_t) {}
-    __device__ __forceinline__ int32_t start(int32_t r) const { return r <= c.R ? c.ring_at(r) : 0x7fffffff; }
-    __device__ __forceinline__ void load(Raw& r, int32_t a, int32_t b) const {
-        r.q = c.load2(a + 2 * lane_id(), b);
-        r.tx = r.ty = 0;
-        if (b < c.V) c.load1(b, r.tx, r.ty);
-    }
-    __device__ __forceinline__ void terms(const Raw& r, int, int32_t a, int32_t p0, int32_t L, int32_t h1, int32_t h2,
-                                          MsSum& t0, MsSum& t1) const {
-        // the coordinate after this lane's two: the next lane's first (lane 63: the one after the chunk)
-        const int32_t nx = (int32_t)lane_next((uint32_t)r.q.x, (uint32_t)r.tx);
-        const int32_t ny = (int32_t)lane_next((uint32_t)r.q.y, (uint32_t)r.ty);
-        const MsSum e0 = ms_edge(r.q.x, r.q.y, r.q.z, r.q.w), e1 = ms_edge(r.q.z, r.q.w, nx, ny);
-        t0 = V::sel(a + p0 + 1 < c.V && h1 == 0 && p0 + 1 < L, e0, V::id());
-        t1 = V::sel(a + p0 + 2 < c.V && h2 == 0 && p0 + 1 < L, e1, V::id());
-    }
-    // the edges from the coordinates [from, to - 1)
-    __device__ __forceinline__ MsSum tail(int32_t from, int32_t to, int32_t tid, int32_t threads) const {
-        MsSum part = V::id();
-        for (int32_t i = from + tid; i + 1 < to; i += threads) {
-            int32_t x0, y0, x1, y1;
-            c.load1(i, x0, y0);
-            c.load1(i + 1, x1, y1);
-            part = V::join(part, ms_edge(x0, y0, x1, y1));
-        }
-        return part;
+    __device__ __forceinline__ int32_t map(int32_t v) const { return v; }
+    __device__ __forceinline__ MsSum edge(int32_t x0, int32_t y0, int32_t x1, int32_t y1) const {
+        return ms_edge(x0, y0, x1, y1);
     }
     __device__ __forceinline__ void put(int32_t r, MsSum v, bool) const {
         ((gw_i64*)(c.out + measures_ring_s_off(c.n, c.ring_cap)))[r] = (int64_t)v.s;
         ((gw_f64*)(c.out + measures_ring_len_off(c.n, c.ring_cap)))[r] = v.len;
     }
 };
+typedef RingEdgePolicy<MsEdge, kMsWaves> MsRings;
 
 // ---- 1. init ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void measures_init_kernel(const covt_geom_desc* __restrict__ gdescs,
@@ -168,11 +120,12 @@ __global__ __launch_bounds__(64 * kMsWaves) void measures_rings_kernel(
     const covt_geom_desc* __restrict__ gdescs, const uint8_t* __restrict__ asmb, const covt_geom_result* __restrict__ gres,
     const covt_measures_desc* __restrict__ mdescs, uint8_t* __restrict__ out,
     const covt_measures_result* __restrict__ mres) {
-    __shared__ SegSmem<RingPolicy> sm;
+    __shared__ SegSmem<MsRings> sm;
     const int64_t col = blockIdx.x;
     if (mres[col].status != COVT_OK) return;  // (launch 1's, earlier on this stream; uniform over the workgroup)
     const MsCol c = ms_column(gdescs[col], gres[col], mdescs[col], nullptr, asmb, out);
-    RingPolicy p{c};
+    const MsEdge e{c};
+    MsRings p{c, e};
     seg_run(p, sm);
 }
 
@@ -226,8 +179,7 @@ __global__ __launch_bounds__(64 * kMsWaves) void measures_features_kernel(const 
             o_len[f] = len;
         }
         // the wide features of this step, one after the other by the whole wave
-        for (uint64_t m = __ballot(wide); m; m &= m - 1) {
-            const int src = __ffsll((unsigned long long)m) - 1;
+        wave_each(wide, [&](int src) {
             const int32_t wf = f0 + src;
             const int32_t wg0 = (int32_t)lane_bcast((uint32_t)g0, src), wg1 = (int32_t)lane_bcast((uint32_t)g1, src);
             const int32_t wr0 = (int32_t)lane_bcast((uint32_t)r0, src), wr1 = (int32_t)lane_bcast((uint32_t)r1, src);
@@ -246,7 +198,7 @@ __global__ __launch_bounds__(64 * kMsWaves) void measures_features_kernel(const 
                 o_area[wf] = wpoly ? (double)(int64_t)(2 * shells - all.s) * 0.5 : 0.0;
                 o_len[wf] = all.len;
             }
-        }
+        });
     }
 }
 

@@ -6,24 +6,23 @@
 // once by one thread (so a captured graph replays the pass as it is and the bytes do not depend on scheduling):
 //
 //   1. init: the column's status (the geometry's, then the layout's).
-//   2. rings (COVT_MVT_ORIENT only): the segmented reduction of covt_segscan.h under AreaPolicy: the segments are
-//      the rings, the value the int64 shoelace S_r over the shifted coordinates (shoelace_term, the measures
-//      pass's policy); S_r goes to the upper half of the ring's record.
+//   2. rings (COVT_MVT_ORIENT only): the segmented reduction of covt_segscan.h over the rings' edges (seg_run
+//      under RingEdgePolicy), the value the int64 shoelace S_r over the shifted coordinates (MvEdge:
+//      shoelace_term, the measures pass's policy); S_r goes to the upper half of the ring's record.
 //   3. features: a thread per feature, the whole wave (a lane per ring, 64 rings a step) for those of kMvNarrow
 //      rings or more.  It writes type[f] and walks the feature's rings in order; per ring it fixes k, whether the
 //      ring is reversed, and the cursor predecessor: the source index of the last vertex the previous non-empty
 //      ring of the feature emits, or -1 for the origin (the wave: a running maximum over the rings).  The record
 //      {k, predecessor, flags, the feature's coordinate count} is all the coordinate passes need: an item is
 //      local to its coordinate and its ring's record.
-//   4. count: the coordinates in chunks of COVT_MVT_CHUNK, a wave per chunk, a row of 128 at a time, in output
-//      order: position a + j of the ring [a, b) is item j of the ring, which reads source b - 1 - j if the ring is
-//      reversed; the position of a closed polygon ring's last coordinate is no item.  A coordinate's ring as in
-//      covt_simplify.hip: the chunk's first by the 64-ary search, then ring starts marked in LDS and a running
-//      maximum (DPP).  An item's bytes are the commands in front of it (MoveTo before a ring's first item or a
-//      point feature's first, LineTo before a ring's second), its two parameters and ClosePath after a polygon
-//      ring's last.  The chunk's byte total goes to chunk_k[chunk].
+//   4. count: the coordinates in chunks of COVT_MVT_CHUNK, each with its ring and its predecessor (ring_stream
+//      of covt_segscan.h), in output order: position a + j of the ring [a, b) is item j of the ring, which reads
+//      source b - 1 - j if the ring is reversed; the position of a closed polygon ring's last coordinate is no
+//      item.  An item's bytes are the commands in front of it (MoveTo before a ring's first item or a point
+//      feature's first, LineTo before a ring's second), its two parameters and ClosePath after a polygon ring's
+//      last.  The chunk's byte total goes to chunk_k[chunk].
 //   5. scan: per column (a workgroup in small batches, a wave in large ones) the exclusive scan of chunk_k in
-//      place -> n_bytes, and n_empty: the features without a coordinate.
+//      place -> n_bytes, and n_empty: the features without a coordinate (StepScan of covt_coop.h).
 //   6. write: pass 4 again; an item's destination is its chunk's base plus its exclusive prefix in the chunk.  The
 //      item is put together in registers (at most 16 bytes) and stored with align-1 vector stores of 8, 4, 2 and
 //      1 bytes.  The first item of a ring also stores its destination to ring_base[ring].
@@ -43,8 +42,6 @@ constexpr int kMvWaves = 4;                // waves per workgroup
 constexpr int kMvNarrow = 64;              // rings from which a feature is finished by the whole wave
 constexpr int kMvIpl = 4;                  // scan: items per thread and step
 constexpr int kMvCoopMaxColumns = 4096;    // scan: batches of at most this many columns get a workgroup per column
-constexpr int kMvRows = COVT_MVT_CHUNK / 128;  // count / write: rows of 128 coordinates per chunk
-static_assert(COVT_MVT_CHUNK % 128 == 0, "a chunk is whole rows");
 static_assert(COVT_MVT_RING_REC == 16, "a ring's record is four words");
 
 // a ring's record: x = k, y = the cursor predecessor (a source index, -1: the origin), z = flags, w = the
@@ -53,40 +50,6 @@ constexpr uint32_t kMvPoints = 1u;   // a ring of a POINT / MULTIPOINT feature: 
 constexpr uint32_t kMvFirst = 2u;    // the first non-empty ring of a point feature: MoveTo(w) in front
 constexpr uint32_t kMvPolygon = 4u;  // ClosePath after the last item
 constexpr uint32_t kMvRev = 8u;      // item j reads source b - 1 - j
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) const u32x4 g_u32x4;
-typedef __attribute__((address_space(1))) u32x4 gw_u32x4;
-typedef __attribute__((address_space(1))) uint8_t gw_u8;
-typedef __attribute__((address_space(1))) uint32_t gw_u32;
-typedef __attribute__((address_space(1))) int32_t gw_i32;
-typedef __attribute__((address_space(1))) int64_t gw_i64;
-typedef __attribute__((address_space(1))) const int64_t g_i64;
-typedef uint64_t u64u __attribute__((aligned(1)));
-typedef uint32_t u32u __attribute__((aligned(1)));
-typedef uint16_t u16u __attribute__((aligned(1)));
-typedef __attribute__((address_space(1))) u64u gw_u64u;
-typedef __attribute__((address_space(1))) u32u gw_u32u;
-typedef __attribute__((address_space(1))) u16u gw_u16u;
-
-// a doubled signed area mod 2^64 under addition
-struct AreaV {
-    typedef uint64_t T;
-    static __device__ __forceinline__ T id() { return 0ull; }
-    static __device__ __forceinline__ T join(T a, T b) { return a + b; }
-    static __device__ __forceinline__ T sel(bool p, T a, T b) { return p ? a : b; }
-    template <int CTRL, int RMASK>
-    static __device__ __forceinline__ T dpp(T old, T v) {
-        return dpp_move<CTRL, RMASK>(old, v);
-    }
-    static __device__ __forceinline__ T bcast(T v, int src) { return lane_bcast64(v, src); }
-    template <int N>
-    struct Lds {
-        uint64_t v[N];
-        __device__ __forceinline__ T get(int i) const { return v[i]; }
-        __device__ __forceinline__ void put(int i, T x) { v[i] = x; }
-    };
-};
 
 struct MvCol : GeomCol {
     const uint8_t* types;
@@ -104,10 +67,6 @@ struct MvCol : GeomCol {
     __device__ __forceinline__ void loadq(int32_t i, int32_t& x, int32_t& y) const {
         load1(clamp0(i, V - 1), x, y);
         x = q(x), y = q(y);
-    }
-    // chunks of the count and write passes (a column without rings emits nothing)
-    __device__ __forceinline__ int32_t chunks() const {
-        return R > 0 ? (int32_t)(((int64_t)V + COVT_MVT_CHUNK - 1) / COVT_MVT_CHUNK) : 0;
     }
 };
 __device__ __forceinline__ MvCol mv_column(const covt_geom_desc& gd, const covt_geom_result& gr, const covt_mvt_desc& md,
@@ -129,62 +88,18 @@ __device__ __forceinline__ MvCol mv_column(const covt_geom_desc& gd, const covt_
     return c;
 }
 
-// The rings of a column as the segments of covt_segscan.h, the value S_r over the shifted coordinates.
-struct AreaPolicy {
-    typedef AreaV V;
-    static constexpr int kWaves = kMvWaves;
-    static constexpr int kRows = 1;     // one row of 64 lanes x 2 coordinates per chunk: 128 coordinates
-    static constexpr int kWide = 2048;  // coordinates left past a run from which the workgroup finishes a ring
-    static constexpr int kIncl = 1;     // an edge's term depends on whether the next coordinate is a head
-    static constexpr int kAhead = 1;
-    struct Raw {
-        i32x4 q;         // shifted
-        int32_t tx, ty;  // the coordinate after the chunk, shifted (uniform)
-    };
-
+// what the rings pass supplies to RingEdgePolicy: the shifted coordinates, shoelace_term, S_r into the upper half
+// of the ring's record
+struct MvEdge {
+    typedef AddV<uint64_t> V;
     const MvCol& c;
-
-    __device__ __forceinline__ int32_t count() const { return c.R; }
-    __device__ __forceinline__ int32_t items() const { return c.V; }
-    __device__ __forceinline__ int32_t first_at(int32_t x) const {
-        return seg_first_at(c.R, x, [&](int32_t r) { return c.ring_at(r); });
+    __device__ __forceinline__ int32_t map(int32_t v) const { return c.q(v); }
+    __device__ __forceinline__ uint64_t edge(int32_t x0, int32_t y0, int32_t x1, int32_t y1) const {
+        return shoelace_term(x0, y0, x1, y1);
     }
-    __device__ __forceinline__ void open(int32_t) {}
-    __device__ __forceinline__ void ensure(int32_t, int32_t) {}
-    __device__ __forceinline__ int32_t start(int32_t r) const { return r <= c.R ? c.ring_at(r) : 0x7fffffff; }
-    __device__ __forceinline__ void load(Raw& r, int32_t a, int32_t b) const {
-        const i32x4 q = c.load2(a + 2 * lane_id(), b);
-        r.q = i32x4{c.q(q.x), c.q(q.y), c.q(q.z), c.q(q.w)};
-        r.tx = r.ty = 0;
-        if (b < c.V) {
-            c.load1(b, r.tx, r.ty);
-            r.tx = c.q(r.tx), r.ty = c.q(r.ty);
-        }
-    }
-    __device__ __forceinline__ void terms(const Raw& r, int, int32_t a, int32_t p0, int32_t L, int32_t h1, int32_t h2,
-                                          uint64_t& t0, uint64_t& t1) const {
-        // the coordinate after this lane's two: the next lane's first (lane 63: the one after the chunk)
-        const int32_t nx = (int32_t)lane_next((uint32_t)r.q.x, (uint32_t)r.tx);
-        const int32_t ny = (int32_t)lane_next((uint32_t)r.q.y, (uint32_t)r.ty);
-        const uint64_t e0 = shoelace_term(r.q.x, r.q.y, r.q.z, r.q.w), e1 = shoelace_term(r.q.z, r.q.w, nx, ny);
-        t0 = a + p0 + 1 < c.V && h1 == 0 && p0 + 1 < L ? e0 : 0ull;
-        t1 = a + p0 + 2 < c.V && h2 == 0 && p0 + 1 < L ? e1 : 0ull;
-    }
-    // the edges from the coordinates [from, to - 1)
-    __device__ __forceinline__ uint64_t tail(int32_t from, int32_t to, int32_t tid, int32_t threads) const {
-        uint64_t part = 0;
-        for (int32_t i = from + tid; i + 1 < to; i += threads) {
-            int32_t x0, y0, x1, y1;
-            c.load1(i, x0, y0);
-            c.load1(i + 1, x1, y1);
-            part += shoelace_term(c.q(x0), c.q(y0), c.q(x1), c.q(y1));
-        }
-        return part;
-    }
-    __device__ __forceinline__ void put(int32_t r, uint64_t v, bool) const {
-        ((gw_i64*)(c.rec + r))[1] = (int64_t)v;
-    }
+    __device__ __forceinline__ void put(int32_t r, uint64_t v, bool) const { ((gw_i64*)(c.rec + r))[1] = (int64_t)v; }
 };
+typedef RingEdgePolicy<MvEdge, kMvWaves> MvRings;
 
 // ---- 1. init ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void mvt_init_kernel(const covt_geom_desc* __restrict__ gdescs,
@@ -213,11 +128,12 @@ __global__ __launch_bounds__(64 * kMvWaves) void mvt_rings_kernel(
     const covt_geom_desc* __restrict__ gdescs, const uint8_t* __restrict__ asmb, const covt_geom_result* __restrict__ gres,
     const covt_mvt_desc* __restrict__ mdescs, uint32_t flags, int32_t shift, uint8_t* __restrict__ out,
     const covt_mvt_result* __restrict__ mres) {
-    __shared__ SegSmem<AreaPolicy> sm;
+    __shared__ SegSmem<MvRings> sm;
     const int64_t col = blockIdx.x;
     if (mres[col].status != COVT_OK) return;  // (launch 1's, earlier on this stream; uniform over the workgroup)
     const MvCol c = mv_column(gdescs[col], gres[col], mdescs[col], nullptr, asmb, out, flags, shift);
-    AreaPolicy p{c};
+    const MvEdge e{c};
+    MvRings p{c, e};
     seg_run(p, sm);
 }
 
@@ -291,8 +207,7 @@ __global__ __launch_bounds__(64 * kMvWaves) void mvt_features_kernel(
             }
         }
         // the wide features of this step, one after the other by the whole wave, a lane per ring, 64 rings a step
-        for (uint64_t m = __ballot(wide); m; m &= m - 1) {
-            const int src = __ffsll((unsigned long long)m) - 1;
+        wave_each(wide, [&](int src) {
             const int32_t wg0 = (int32_t)lane_bcast((uint32_t)g0, src), wg1 = (int32_t)lane_bcast((uint32_t)g1, src);
             const int32_t wr0 = (int32_t)lane_bcast((uint32_t)r0, src), wr1 = (int32_t)lane_bcast((uint32_t)r1, src);
             const int32_t wcnt = (int32_t)lane_bcast((uint32_t)cnt, src);
@@ -320,7 +235,7 @@ __global__ __launch_bounds__(64 * kMvWaves) void mvt_features_kernel(
                 carry = max(carry, lane_bcast(inc, 63));
                 if (in) mv_put_rec(c, r, ring, (int32_t)before - 1, wcnt);
             }
-        }
+        });
     }
 }
 
@@ -416,10 +331,8 @@ __device__ __forceinline__ void mv_store(const MvCol& c, uint32_t d, MvItem it) 
     if (it.len & 1u) *(gw_u8*)p = (uint8_t)v;
 }
 
-// blockIdx.x: the column; a wave per chunk, the column's gridDim.y * kMvWaves waves striding over them.  Per row
-// of 128 coordinates the rings that start in it are marked in LDS, a lane per ring (ring + 1 at the start of a
-// non-empty ring: one ring per position), and a coordinate's ring is the running maximum of the marks up to it
-// (DPP), carried from row to row; the chunk's first by the 64-ary search.
+// blockIdx.x: the column; the walk is ring_stream's, the row here: the items' lengths, their inclusive scan
+// over the row (its total the row's bytes) and, WRITE, the items' stores.
 template <bool WRITE>
 __global__ __launch_bounds__(64 * kMvWaves) void mvt_stream_kernel(
     const covt_geom_desc* __restrict__ gdescs, const uint8_t* __restrict__ asmb, const covt_geom_result* __restrict__ gres,
@@ -429,105 +342,32 @@ __global__ __launch_bounds__(64 * kMvWaves) void mvt_stream_kernel(
     const int64_t col = blockIdx.x;
     if (mres[col].status != COVT_OK) return;
     const MvCol c = mv_column(gdescs[col], gres[col], mdescs[col], nullptr, asmb, out, flags, shift);
-    const int l = lane_id();
-    uint32_t* const mark = marks[threadIdx.x >> 6];
-    const int32_t chunks = c.chunks();
-    const auto ring_at = [&](int32_t r) { return c.ring_at(r); };
-    *(uint64_t*)(mark + 2 * l) = 0ull;
-    wave_sync();
-    for (int32_t ch = uni((int32_t)(blockIdx.y * kMvWaves + (threadIdx.x >> 6))); ch < chunks;
-         ch += (int32_t)(gridDim.y * kMvWaves)) {
-        const int32_t A = ch * COVT_MVT_CHUNK, B = min(A + COVT_MVT_CHUNK, c.V);
-        // the ring of the chunk's first coordinate: the last one that starts at or before it
-        const int32_t rlo = clamp0(seg_first_at(c.R, A + 1, ring_at) - 1, c.R - 1);
-        uint32_t open = (uint32_t)rlo + 1u;  // ring + 1 of the coordinate before the row (uniform)
-        int32_t sc = rlo;                    // the first ring not yet marked (uniform; rlo may start at A itself)
-        uint32_t run = WRITE ? (uint32_t)uni((int32_t)((g_u32*)c.chunk_k)[ch]) : 0u;
-        int32_t px = 0, py = 0;  // the coordinate before the row, shifted (uniform)
-        if (A > 0) c.loadq(A - 1, px, py);
-        for (int k = 0; k < kMvRows; ++k) {
-            const int32_t a = A + 128 * k, b = min(a + 128, B), i0 = a + 2 * l;
-            if (a >= B) break;  // (uniform)
-            const i32x4 q = c.load2(i0, B);
-            // the rings from sc on that start below b, 64 a step
-            for (;;) {
-                const int32_t s = sc + l;
-                const int32_t st = s < c.R ? c.ring_at(s) : 0x7fffffff;
-                const bool in = st < b;  // (a prefix of the lanes)
-                if (in && st >= a && c.ring_at(s + 1) > st) mark[st - a] = (uint32_t)s + 1u;
-                const int cnt = __popcll(__ballot(in));
-                sc += cnt;
-                if (cnt < 64) break;
-            }
-            wave_sync();
-            const uint64_t mm = *(const uint64_t*)(mark + 2 * l);
-            *(uint64_t*)(mark + 2 * l) = 0ull;  // (the next row's marks follow the wave_sync below)
-            const uint32_t m0 = (uint32_t)mm, m1 = (uint32_t)(mm >> 32);
-            const uint32_t inc = incl_max_scan(max(m0, m1));
-            // the maximum over the lanes before (wave_shr:1), the rows before (open) and the lane's own marks
-            const uint32_t r0 = max(max(dpp_move<0x138, 0xf>(0u, inc), open), m0), r1 = max(r0, m1);
-            open = max(open, lane_bcast(inc, 63));
-            const int32_t x0 = c.q(q.x), y0 = c.q(q.y), x1 = c.q(q.z), y1 = c.q(q.w);
-            // the coordinate before this lane's two: the lane before's second (lane 0: the one before the row)
-            const int32_t bx = (int32_t)dpp_move<0x138, 0xf>((uint32_t)px, (uint32_t)x1);
-            const int32_t by = (int32_t)dpp_move<0x138, 0xf>((uint32_t)py, (uint32_t)y1);
-            px = (int32_t)lane_bcast((uint32_t)x1, 63), py = (int32_t)lane_bcast((uint32_t)y1, 63);
-            // (r0, r1 are in 1 .. R: open is, and so is every mark)
-            const MvItem it0 = mv_item<WRITE>(c, i0 < B, i0, (int32_t)r0 - 1, x0, y0, bx, by);
-            const MvItem it1 = mv_item<WRITE>(c, i0 + 1 < B, i0 + 1, (int32_t)r1 - 1, x1, y1, x0, y0);
+    ring_stream<COVT_MVT_CHUNK, kMvWaves, WRITE>(
+        c, c.chunk_k, marks[threadIdx.x >> 6], [&](int32_t v) { return c.q(v); }, [&](const RingRow& w) {
+            const MvItem it0 = mv_item<WRITE>(c, w.i0 < w.B, w.i0, w.r0, w.x0, w.y0, w.bx, w.by);
+            const MvItem it1 = mv_item<WRITE>(c, w.i0 + 1 < w.B, w.i0 + 1, w.r1, w.x1, w.y1, w.x0, w.y0);
             const uint32_t own = it0.len + it1.len;
             const uint32_t incl = incl_scan(own);
             if (WRITE) {
-                const uint32_t d0 = run + incl - own, d1 = d0 + it0.len;
+                const uint32_t d0 = w.run + incl - own, d1 = d0 + it0.len;
                 mv_store(c, d0, it0);
                 mv_store(c, d1, it1);
                 // a ring's first position: the byte offset of the ring (offsets kernel)
-                if (m0 != 0u && i0 < B) ((gw_u32*)c.ring_base)[m0 - 1u] = d0;
-                if (m1 != 0u && i0 + 1 < B) ((gw_u32*)c.ring_base)[m1 - 1u] = d1;
+                if (w.m0 != 0u && w.i0 < w.B) ((gw_u32*)c.ring_base)[w.m0 - 1u] = d0;
+                if (w.m1 != 0u && w.i0 + 1 < w.B) ((gw_u32*)c.ring_base)[w.m1 - 1u] = d1;
             }
-            run += lane_bcast(incl, 63);
-            wave_sync();
-        }
-        if (!WRITE && l == 0) ((gw_u32*)c.chunk_k)[ch] = run;
-    }
+            return lane_bcast(incl, 63);
+        });
 }
 
 // ---- 5. scan ------------------------------------------------------------------------------------------
 // chunk_k -> its exclusive scan in place and n_bytes; n_empty
 template <int NW>
 __device__ void mvt_scan_column(const MvCol& c, covt_mvt_result* res, AsmSmemT<NW, kMvIpl>& sm) {
-    constexpr int K = Coop<NW, kMvIpl>::K;
     const int l = Coop<NW, kMvIpl>::tid();
-    auto ioff = [&](int k) { return NW == 1 ? 64 * k + l : kMvIpl * l + k; };
-    int buf = 0;
-    const int32_t chunks = c.chunks();
-    uint32_t base = 0;
-    for (int32_t h0 = 0; h0 < chunks; h0 += K) {
-        uint32_t x[kMvIpl], ex[kMvIpl], tot;
-#pragma unroll
-        for (int k = 0; k < kMvIpl; ++k) {
-            const int32_t h = h0 + ioff(k);
-            x[k] = h < chunks ? ((g_u32*)c.chunk_k)[h] : 0u;
-        }
-        excl_scan4(sm, buf, x, ex, tot);
-#pragma unroll
-        for (int k = 0; k < kMvIpl; ++k) {
-            const int32_t h = h0 + ioff(k);
-            if (h < chunks) ((gw_u32*)c.chunk_k)[h] = add_sat(base, ex[k]);
-        }
-        base = add_sat(base, tot);
-    }
-    uint32_t empty = 0;
-    for (int32_t f0 = 0; f0 < c.n; f0 += K) {
-        uint32_t x[kMvIpl], ex[kMvIpl], tot;
-#pragma unroll
-        for (int k = 0; k < kMvIpl; ++k) {
-            const int32_t f = f0 + ioff(k);
-            x[k] = f < c.n && c.start(f + 1) <= c.start(f) ? 1u : 0u;
-        }
-        excl_scan4(sm, buf, x, ex, tot);
-        empty += tot;
-    }
+    StepScan<NW, kMvIpl> scan{sm};
+    const uint32_t base = scan.in_place(c.chunk_k, ring_chunks<COVT_MVT_CHUNK>(c));
+    const uint32_t empty = scan.sum(c.n, [&](int32_t f) { return c.start(f + 1) <= c.start(f) ? 1u : 0u; });
     if (l == 0) {  // (the byte total of a well-formed column is within the capacity)
         res->n_empty = (int32_t)empty;
         res->n_bytes = (int64_t)min((int64_t)base, c.byte_cap);

@@ -1,6 +1,9 @@
-// covt_segscan.h -- what the per-column geometry products share on the device (covt_bbox.hip, covt_measures.hip;
-// covt_wkb.hip uses the precheck and the launch sizing, covt_select.hip those and the 64-ary search): the clamped view of an assembled column, the status
-// before any work, the workgroups per column, and the segmented inclusive reduction over a column's items.
+// covt_segscan.h -- what the per-column geometry products share on the device (covt_bbox.hip, covt_measures.hip,
+// covt_simplify.hip, covt_mvt.hip; covt_wkb.hip uses the precheck and the launch sizing, covt_select.hip those
+// and the 64-ary search): the clamped view of an assembled column, the status before any work, the workgroups per
+// column, the segmented inclusive reduction over a column's items (below), its policy for per-ring sums over
+// edges (RingEdgePolicy: measures, simplify, mvt), and the walk that hands every coordinate its ring
+// (ring_stream: the count and write passes of simplify and mvt).
 //
 // The reduction.  A column's items (coordinates) fall into consecutive segments (features, rings), segment s
 // being the range [start(s), start(s + 1)) with start nondecreasing; a value type with an associative join
@@ -200,6 +203,29 @@ __device__ __forceinline__ void seg_row_scan(typename V::T c0, typename V::T c1,
     carry = V::bcast(v, 63);
 }
 
+// a sum mod 2^32 or 2^64 (U: uint32_t, uint64_t) under addition
+template <class U>
+struct AddV {
+    typedef U T;
+    static __device__ __forceinline__ T id() { return 0; }
+    static __device__ __forceinline__ T join(T a, T b) { return a + b; }
+    static __device__ __forceinline__ T sel(bool p, T a, T b) { return p ? a : b; }
+    template <int CTRL, int RMASK>
+    static __device__ __forceinline__ T dpp(T old, T v) {
+        return dpp_move<CTRL, RMASK>(old, v);
+    }
+    static __device__ __forceinline__ T bcast(T v, int src) {
+        if constexpr (sizeof(U) == 8) return lane_bcast64(v, src);
+        else return lane_bcast(v, src);
+    }
+    template <int N>
+    struct Lds {
+        U v[N];
+        __device__ __forceinline__ T get(int i) const { return v[i]; }
+        __device__ __forceinline__ void put(int i, T x) { v[i] = x; }
+    };
+};
+
 // zero the wave's N head bytes (N a multiple of 4), four a lane and step
 template <int N>
 __device__ __forceinline__ void seg_clear_heads(uint8_t* head) {
@@ -335,6 +361,164 @@ __device__ __forceinline__ void seg_run(P& p, SegSmem<P>& sm) {
             p.put(s, v, true);
         }
         __syncthreads();
+    }
+}
+
+// ---- the rings of a column as segments ------------------------------------------------------------------
+// The policy of a per-ring sum over edges: the segments are the rings of a GeomCol, read from ring[] directly;
+// a chunk is one row of 128 coordinates (16 bytes a lane); a coordinate's term is that of its edge to the next
+// coordinate -- the lane takes it from its neighbour (DPP) -- and id() where the next coordinate starts another
+// ring or the column ends (so heads are marked up to and including the chunk's end).  The product is
+//
+//   struct Edge {
+//       typedef ValueTrait V;
+//       int32_t map(int32_t v) const;                                      // applied to every coordinate read
+//       V::T edge(int32_t x0, int32_t y0, int32_t x1, int32_t y1) const;   // of mapped coordinates
+//       void put(int32_t r, V::T v, bool any) const;                       // ring r's sum (any: it has a coordinate)
+//   };
+template <class Edge, int WAVES>
+struct RingEdgePolicy {
+    typedef typename Edge::V V;
+    typedef typename V::T T;
+    static constexpr int kWaves = WAVES;
+    static constexpr int kRows = 1;
+    static constexpr int kWide = 2048;  // coordinates left past a run from which the workgroup finishes a ring
+    static constexpr int kIncl = 1;     // an edge's term depends on whether the next coordinate is a head
+    static constexpr int kAhead = 1;
+    struct Raw {
+        i32x4 q;         // mapped
+        int32_t tx, ty;  // the coordinate after the chunk, mapped (uniform)
+    };
+
+    const GeomCol& c;
+    const Edge& e;
+
+    __device__ __forceinline__ int32_t count() const { return c.R; }
+    __device__ __forceinline__ int32_t items() const { return c.V; }
+    __device__ __forceinline__ int32_t first_at(int32_t x) const {
+        return seg_first_at(c.R, x, [&](int32_t r) { return c.ring_at(r); });
+    }
+    __device__ __forceinline__ void open(int32_t) {}
+    __device__ __forceinline__ void ensure(int32_t, int32_t) {}
+    __device__ __forceinline__ int32_t start(int32_t r) const { return r <= c.R ? c.ring_at(r) : 0x7fffffff; }
+    __device__ __forceinline__ void load(Raw& r, int32_t a, int32_t b) const {
+        const i32x4 q = c.load2(a + 2 * lane_id(), b);
+        r.q = i32x4{e.map(q.x), e.map(q.y), e.map(q.z), e.map(q.w)};
+        r.tx = r.ty = 0;
+        if (b < c.V) {
+            c.load1(b, r.tx, r.ty);
+            r.tx = e.map(r.tx), r.ty = e.map(r.ty);
+        }
+    }
+    __device__ __forceinline__ void terms(const Raw& r, int, int32_t a, int32_t p0, int32_t L, int32_t h1, int32_t h2,
+                                          T& t0, T& t1) const {
+        // the coordinate after this lane's two: the next lane's first (lane 63: the one after the chunk)
+        const int32_t nx = (int32_t)lane_next((uint32_t)r.q.x, (uint32_t)r.tx);
+        const int32_t ny = (int32_t)lane_next((uint32_t)r.q.y, (uint32_t)r.ty);
+        const T e0 = e.edge(r.q.x, r.q.y, r.q.z, r.q.w), e1 = e.edge(r.q.z, r.q.w, nx, ny);
+        t0 = V::sel(a + p0 + 1 < c.V && h1 == 0 && p0 + 1 < L, e0, V::id());
+        t1 = V::sel(a + p0 + 2 < c.V && h2 == 0 && p0 + 1 < L, e1, V::id());
+    }
+    // the edges from the coordinates [from, to - 1)
+    __device__ __forceinline__ T tail(int32_t from, int32_t to, int32_t tid, int32_t threads) const {
+        T part = V::id();
+        for (int32_t i = from + tid; i + 1 < to; i += threads) {
+            int32_t x0, y0, x1, y1;
+            c.load1(i, x0, y0);
+            c.load1(i + 1, x1, y1);
+            part = V::join(part, e.edge(e.map(x0), e.map(y0), e.map(x1), e.map(y1)));
+        }
+        return part;
+    }
+    __device__ __forceinline__ void put(int32_t r, T v, bool any) const { e.put(r, v, any); }
+};
+
+// ---- the ring of every coordinate -----------------------------------------------------------------------
+// chunks of CHUNK coordinates of a column's count and write passes (a column without rings has no item)
+template <int CHUNK>
+__device__ __forceinline__ int32_t ring_chunks(const GeomCol& c) {
+    return c.R > 0 ? (int32_t)(((int64_t)c.V + CHUNK - 1) / CHUNK) : 0;
+}
+
+// what a row's callback gets: the lane's two positions and what the walk knows of them
+struct RingRow {
+    int32_t i0, B;           // the positions i0, i0 + 1 (those at or past the chunk's end B are none)
+    int32_t r0, r1;          // their rings (in 0 .. R - 1)
+    uint32_t m0, m1;         // their marks: ring + 1 at the first position of a non-empty ring, else 0
+    int32_t x0, y0, x1, y1;  // their coordinates, mapped
+    int32_t bx, by;          // the coordinate before i0, mapped (i0 + 1's is (x0, y0))
+    uint32_t run;            // the chunk's base plus what the rows before advanced it by (uniform)
+};
+
+// A column's coordinates in chunks of CHUNK, a wave per chunk, the column's gridDim.y * WAVES waves striding over
+// them, a row of 128 at a time, two consecutive positions a lane: row(RingRow) is called by the whole wave once
+// per row and returns what the row adds to `run` (uniform).  `run` starts at 0 and the chunk's total goes to
+// chunk_k[chunk] (the count pass), or WRITE: it starts at chunk_k[chunk], by then its exclusive scan.  map is
+// applied to every coordinate.  `mark` is the wave's 128 words of LDS.
+//
+// The ring of the chunk's first coordinate comes from the 64-ary search; per row the rings that start in it are
+// marked in LDS, a lane per ring, and a coordinate's ring is the running maximum of the marks up to it (DPP),
+// carried from row to row in `open`; its predecessor comes by DPP too.  What this rests on:
+//   - a mark is ring + 1 at the start of a *non-empty* ring, so there is one ring per position and the maximum
+//     is the position's own ring; rlo, the last ring that starts at or before the chunk, may be empty or start
+//     at the chunk's first position itself, so the marking starts from it;
+//   - the lane clears its two marks as it reads them; the next row's marks (and the next chunk's) follow the
+//     wave_sync at the row's end, the reads follow the wave_sync after the marking;
+//   - sc, open, run, px and py are wave-uniform, so every branch on them is, and the DPP moves and the ballots
+//     of the walk and of the callback run with the whole wave active.
+template <int CHUNK, int WAVES, bool WRITE, class Map, class Row>
+__device__ __forceinline__ void ring_stream(const GeomCol& c, uint32_t* chunk_k, uint32_t* mark, Map map, Row row) {
+    static_assert(CHUNK % 128 == 0, "a chunk is whole rows");
+    const int l = lane_id();
+    const int32_t chunks = ring_chunks<CHUNK>(c);
+    const auto ring_at = [&](int32_t r) { return c.ring_at(r); };
+    *(uint64_t*)(mark + 2 * l) = 0ull;
+    wave_sync();
+    for (int32_t ch = uni((int32_t)(blockIdx.y * WAVES + (threadIdx.x >> 6))); ch < chunks;
+         ch += (int32_t)(gridDim.y * WAVES)) {
+        const int32_t A = ch * CHUNK, B = min(A + CHUNK, c.V);
+        // the ring of the chunk's first coordinate: the last one that starts at or before it
+        const int32_t rlo = clamp0(seg_first_at(c.R, A + 1, ring_at) - 1, c.R - 1);
+        uint32_t open = (uint32_t)rlo + 1u;  // ring + 1 of the coordinate before the row
+        int32_t sc = rlo;                    // the first ring not yet marked
+        uint32_t run = WRITE ? (uint32_t)uni((int32_t)((g_u32*)chunk_k)[ch]) : 0u;
+        int32_t px = 0, py = 0;  // the coordinate before the row, mapped
+        if (A > 0) {
+            c.load1(A - 1, px, py);
+            px = map(px), py = map(py);
+        }
+        for (int k = 0; k < CHUNK / 128; ++k) {
+            const int32_t a = A + 128 * k, b = min(a + 128, B), i0 = a + 2 * l;
+            if (a >= B) break;
+            const i32x4 q = c.load2(i0, B);
+            // the rings from sc on that start below b, 64 a step
+            for (;;) {
+                const int32_t s = sc + l;
+                const int32_t st = s < c.R ? c.ring_at(s) : 0x7fffffff;
+                const bool in = st < b;  // (a prefix of the lanes)
+                if (in && st >= a && c.ring_at(s + 1) > st) mark[st - a] = (uint32_t)s + 1u;
+                const int cnt = __popcll(__ballot(in));
+                sc += cnt;
+                if (cnt < 64) break;
+            }
+            wave_sync();
+            const uint64_t mm = *(const uint64_t*)(mark + 2 * l);
+            *(uint64_t*)(mark + 2 * l) = 0ull;
+            const uint32_t m0 = (uint32_t)mm, m1 = (uint32_t)(mm >> 32);
+            const uint32_t inc = incl_max_scan(max(m0, m1));
+            // the maximum over the lanes before (wave_shr:1), the rows before (open) and the lane's own marks
+            const uint32_t r0 = max(max(dpp_move<0x138, 0xf>(0u, inc), open), m0), r1 = max(r0, m1);
+            open = max(open, lane_bcast(inc, 63));
+            const int32_t x0 = map(q.x), y0 = map(q.y), x1 = map(q.z), y1 = map(q.w);
+            // the coordinate before this lane's two: the lane before's second (lane 0: the one before the row)
+            const int32_t bx = (int32_t)dpp_move<0x138, 0xf>((uint32_t)px, (uint32_t)x1);
+            const int32_t by = (int32_t)dpp_move<0x138, 0xf>((uint32_t)py, (uint32_t)y1);
+            px = (int32_t)lane_bcast((uint32_t)x1, 63), py = (int32_t)lane_bcast((uint32_t)y1, 63);
+            // (r0, r1 are in 1 .. R: open is, and so is every mark)
+            run += row(RingRow{i0, B, (int32_t)r0 - 1, (int32_t)r1 - 1, m0, m1, x0, y0, x1, y1, bx, by, run});
+            wave_sync();
+        }
+        if (!WRITE && l == 0) ((gw_u32*)chunk_k)[ch] = run;
     }
 }
 

@@ -51,17 +51,6 @@ constexpr int kSelWaves = 4;              // waves per workgroup (predicate, wav
 constexpr int kSelChunk = 64 * 16;        // copy: output bytes per wave chunk, 16 per lane
 constexpr int kSelWin = 256;              // copy: owners staged in LDS per window (a multiple of 64)
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(1)));
-typedef uint32_t sel_u32u __attribute__((aligned(1)));
-typedef __attribute__((address_space(1))) const u32x4u gs_u32x4u;
-typedef __attribute__((address_space(1))) const sel_u32u gs_u32u;
-typedef __attribute__((address_space(1))) u32x4 gd_u32x4;
-typedef __attribute__((address_space(1))) uint32_t gd_u32;
-typedef __attribute__((address_space(1))) uint8_t gd_u8;
-typedef __attribute__((address_space(1))) int32_t gd_i32;
-typedef __attribute__((address_space(1))) const double g_f64;
-
 // ---- the predicate -------------------------------------------------------------------------------------
 // small batches: blockIdx.x the column, its features over gridDim.y workgroups; large ones: a wave per column
 __global__ __launch_bounds__(64 * kSelWaves) void sel_predicate_kernel(
@@ -115,7 +104,7 @@ __global__ __launch_bounds__(64 * kSelWaves) void sel_predicate_kernel(
             }
             m = select_keep(pred, xmin, ymin, xmax, ymax, a, len);
         }
-        ((gd_u8*)mask)[f] = m;
+        ((gw_u8*)mask)[f] = m;
     }
 }
 
@@ -160,6 +149,8 @@ __device__ __forceinline__ int32_t sel_precheck(const covt_wkb_desc& wd, const c
 }
 
 // ---- 1. scan -------------------------------------------------------------------------------------------
+// (the stepped loop written out, not StepScan of covt_coop.h: a step scans two values, count and bytes, from one
+// set of loads, and a kept feature's store needs both prefixes)
 template <int NW, int IPL>
 __device__ void sel_scan_column(const covt_wkb_desc& wd, const covt_wkb_result& wr, const uint8_t* __restrict__ wkb,
                                 const covt_select_desc& sd, uint8_t* __restrict__ select, covt_select_result& res,
@@ -188,8 +179,8 @@ __device__ void sel_scan_column(const covt_wkb_desc& wd, const covt_wkb_result& 
         for (int k = 0; k < IPL; ++k) {
             if (!keep[k]) continue;
             const uint32_t j = J + ej[k];  // (below n_features: a rank)
-            ((gd_i32*)c.sel)[j] = f0 + ioff(k);
-            ((gd_i32*)c.offs)[j] = (int32_t)add_sat(B, eb[k]);  // (saturated only in a column that fails below)
+            ((gw_i32*)c.sel)[j] = f0 + ioff(k);
+            ((gw_i32*)c.offs)[j] = (int32_t)add_sat(B, eb[k]);  // (saturated only in a column that fails below)
         }
         J += tj;
         B = add_sat(B, tb);
@@ -198,7 +189,7 @@ __device__ void sel_scan_column(const covt_wkb_desc& wd, const covt_wkb_result& 
         res.status = COVT_ERR_COUNT_MISMATCH;
         return;
     }
-    if (l == 0) ((gd_i32*)c.offs)[J] = (int32_t)B;
+    if (l == 0) ((gw_i32*)c.offs)[J] = (int32_t)B;
     res.n_selected = (int32_t)J;
     res.n_bytes = (int64_t)B;
 }
@@ -324,7 +315,7 @@ __device__ __forceinline__ int32_t sel_copy_chunk(const SelWindow& w, uint32_t b
     uint8_t* dst = w.c.bytes + b;
     uint32_t v[4] = {0u, 0u, 0u, 0u};
     if ((uint32_t)cur.o1 >= b + 16u) {  // the vector lies inside one value
-        const u32x4 q = *(gs_u32x4u*)cur.at(w, b);
+        const u32x4 q = *(g_u32x4u*)cur.at(w, b);
         v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
     } else {
         // The vector's pieces, one per value it touches: a piece at bytes [a, e) of the vector comes out of one
@@ -338,7 +329,7 @@ __device__ __forceinline__ int32_t sel_copy_chunk(const SelWindow& w, uint32_t b
             const uint32_t a = pos - b, e = pe - b;
             const int32_t so = w.src_of(cur.j) + (int32_t)(pos - (uint32_t)cur.o0) - (int32_t)a;  // of vector byte 0
             if (so >= 0 && so <= w.c.src_nb - 16) {
-                const u32x4 q = *(gs_u32x4u*)(w.c.wbytes + so);
+                const u32x4 q = *(g_u32x4u*)(w.c.wbytes + so);
                 const uint32_t qq[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {  // bytes [lo, hi) of dword k belong to the piece
@@ -357,7 +348,7 @@ __device__ __forceinline__ int32_t sel_copy_chunk(const SelWindow& w, uint32_t b
         }
     }
     if (b + 16u <= nb) {
-        *(gd_u32x4*)dst = u32x4{v[0], v[1], v[2], v[3]};
+        *(gw_u32x4*)dst = u32x4{v[0], v[1], v[2], v[3]};
         return hint;
     }
     // the column's tail vector: whole dwords, then bytes
@@ -365,11 +356,11 @@ __device__ __forceinline__ int32_t sel_copy_chunk(const SelWindow& w, uint32_t b
     for (int k = 0; k < 4; ++k) {
         const uint32_t p = b + 4u * k;
         if (p + 4u <= nb) {
-            *(gd_u32*)(dst + 4 * k) = v[k];
+            *(gw_u32*)(dst + 4 * k) = v[k];
         } else {
 #pragma unroll
             for (int t = 0; t < 4; ++t)
-                if (p + t < nb) *(gd_u8*)(dst + 4 * k + t) = (uint8_t)(v[k] >> (8 * t));
+                if (p + t < nb) *(gw_u8*)(dst + 4 * k + t) = (uint8_t)(v[k] >> (8 * t));
         }
     }
     return hint;

@@ -118,6 +118,13 @@ __device__ __forceinline__ int32_t bits_below(uint64_t m) {
 __device__ __forceinline__ int32_t lane_get(int32_t x, int32_t src) {
     return __builtin_amdgcn_ds_bpermute(src << 2, x);
 }
+// f(src) once per lane whose pred is set, in lane order, the whole wave active in each call (src uniform): how
+// a wave finishes, one after the other, the items that one lane each found too wide to take alone.  Every lane
+// of the wave calls it.
+template <class F>
+__device__ __forceinline__ void wave_each(bool pred, F f) {
+    for (uint64_t m = __ballot(pred); m; m &= m - 1) f(__ffsll((unsigned long long)m) - 1);
+}
 
 }  // namespace covt
 

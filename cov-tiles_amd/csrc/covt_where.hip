@@ -48,11 +48,6 @@ constexpr int kWhereDictPerFeature = 4;       // wave per column: bitmap while n
 constexpr int kWhereBitmapWords = COVT_WHERE_MAX_CLAUSES * kWhereDictBitsGroup / 32;
 static_assert(kWhereDictBitsWave % 64 == 0, "a wave stores its ballot as two whole words");
 
-typedef uint32_t wu32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) const wu32x4 gw_u32x4;
-typedef __attribute__((address_space(1))) uint32_t gwd_u32;
-typedef __attribute__((address_space(1))) uint8_t gwd_u8;
-
 constexpr int32_t kWhereUnbound = -1;  // WhereCol::type of a clause without a column
 constexpr int32_t kWhereNoType = 4;    // ... of a column whose type is none of COVT_PROP_*: nothing is defined
 
@@ -112,9 +107,9 @@ __device__ __forceinline__ uint32_t where_clause_bits(const covt_where& w, const
             break;
         }
         case COVT_PROP_INT64: {
-            const gw_u32x4* p = (const gw_u32x4*)(q.values + 8 * f);
-            const wu32x4 a = p[0];
-            wu32x4 b = {0u, 0u, 0u, 0u};
+            const g_u32x4* p = (const g_u32x4*)(q.values + 8 * f);
+            const u32x4 a = p[0];
+            u32x4 b = {0u, 0u, 0u, 0u};
             if (f + 2 < n) b = p[1];  // (a column of 4k + 1 or 4k + 2 features ends inside the first vector)
             const int64_t v[4] = {(int64_t)(((uint64_t)a.y << 32) | a.x), (int64_t)(((uint64_t)a.w << 32) | a.z),
                                   (int64_t)(((uint64_t)b.y << 32) | b.x), (int64_t)(((uint64_t)b.w << 32) | b.z)};
@@ -132,7 +127,7 @@ __device__ __forceinline__ uint32_t where_clause_bits(const covt_where& w, const
             break;
         }
         case COVT_PROP_FLOAT: {
-            const wu32x4 a = *(const gw_u32x4*)(q.values + 4 * f);
+            const u32x4 a = *(const g_u32x4*)(q.values + 4 * f);
             const float v[4] = {__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z), __uint_as_float(a.w)};
             for (int32_t j = 0; j < q.count; ++j) {
                 const covt_where_value& L = w.values[q.first + j];
@@ -148,7 +143,7 @@ __device__ __forceinline__ uint32_t where_clause_bits(const covt_where& w, const
             break;
         }
         case COVT_PROP_STRING: {
-            const wu32x4 a = *(const gw_u32x4*)(q.values + 4 * f);
+            const u32x4 a = *(const g_u32x4*)(q.values + 4 * f);
             const uint32_t v[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -276,11 +271,11 @@ __global__ __launch_bounds__(64 * kWhereWaves) void where_kernel(
 #pragma unroll
             for (int i = 0; i < 4; ++i)
                 out |= (((keep >> i) & 1u) && ((old >> (8 * i)) & 0xffu)) ? 1u << (8 * i) : 0u;
-            *(gwd_u32*)(mask + f) = out;
+            *(gw_u32*)(mask + f) = out;
         } else {
             for (int i = 0; f + i < n; ++i) {
                 const bool old = mode == COVT_WHERE_AND ? ((const g_u8*)mask)[f + i] != 0 : true;
-                ((gwd_u8*)mask)[f + i] = (((keep >> i) & 1u) && old) ? 1 : 0;
+                ((gw_u8*)mask)[f + i] = (((keep >> i) & 1u) && old) ? 1 : 0;
             }
         }
     }

@@ -6,7 +6,7 @@
 //   1. size scan: a feature's byte count is a closed form of its type and six offset gathers
 //      (geo[f], geo[f + 1], part[..], ring[..]); the exclusive scan over the column's features is
 //      wkb_offsets, the total the column's byte count.  One wave per column in a large batch, a workgroup
-//      of kWkbCoopWaves waves per column in a small one (Coop / excl_scan4 of covt_coop.h, the assembly's
+//      of kWkbCoopWaves waves per column in a small one (Coop / StepScan of covt_coop.h, the assembly's
 //      scans; sums saturate and the total is checked against the slice capacity).
 //   2. write: with wkb_offsets known every output byte has a closed-form address, so the column's
 //      coordinates, rings, parts and features are four flat item ranges cut into chunks of kWkbChunk
@@ -47,12 +47,6 @@ constexpr int kWkbIpl = 4;                 // items per thread and step
 constexpr int kWkbWriteWaves = 4;          // write: waves per workgroup
 constexpr int kWkbChunk = 64 * kWkbIpl;    // write: items per wave chunk (lane-major, kWkbIpl per lane)
 constexpr int kWkbWin = 384;               // write: offsets of a level staged in LDS per chunk (a multiple of 64)
-
-typedef uint32_t u32u __attribute__((aligned(1)));
-typedef double f64x2u __attribute__((ext_vector_type(2), aligned(1)));
-typedef __attribute__((address_space(1))) uint8_t gw_u8;
-typedef __attribute__((address_space(1))) u32u gw_u32u;
-typedef __attribute__((address_space(1))) f64x2u gw_f64x2u;
 
 // G parts, R rings, C coordinates of feature f (assembled offsets; types <= 5 checked by the assembly)
 __device__ __forceinline__ uint32_t wkb_feature_size(uint32_t t, const int32_t* geo, const int32_t* part,
@@ -103,32 +97,17 @@ __device__ void wkb_scan_column(const uint8_t* __restrict__ dec, const covt_geom
                                 const uint8_t* __restrict__ asmb, const covt_geom_result& gr, const covt_wkb_desc& wd,
                                 uint8_t* __restrict__ wkb, covt_wkb_result& res, AsmSmemT<NW, IPL>& sm,
                                 int32_t geo_status = COVT_OK) {
-    constexpr int K = Coop<NW, IPL>::K;
     const int l = Coop<NW, IPL>::tid();
-    auto ioff = [&](int k) { return NW == 1 ? 64 * k + l : IPL * l + k; };
     res.reserved = 0;
     res.n_bytes = 0;
     res.status = wkb_precheck(gd, gr, wd);
     if (res.status == COVT_OK) res.status = geo_status;  // (a projected launch: the column's transform kind)
     if (res.status != COVT_OK) return;
     const WkbCol c = wkb_col(dec, gd, asmb, wd, wkb);
-    int buf = 0;
-    uint32_t B = 0;
-    for (int32_t f0 = 0; f0 < c.n; f0 += K) {
-        uint32_t x[IPL], ex[IPL], tot;
-#pragma unroll
-        for (int k = 0; k < IPL; ++k) {
-            const int32_t f = f0 + ioff(k);
-            x[k] = f < c.n ? wkb_feature_size((uint32_t)((const g_u8*)c.types)[f], c.geo, c.part, c.ring, f) : 0u;
-        }
-        excl_scan4(sm, buf, x, ex, tot);
-#pragma unroll
-        for (int k = 0; k < IPL; ++k) {
-            const int32_t f = f0 + ioff(k);
-            if (f < c.n) c.woff[f] = (int32_t)add_sat(B, ex[k]);  // (saturated only in a column that fails below)
-        }
-        B = add_sat(B, tot);
-    }
+    StepScan<NW, IPL> scan{sm};
+    const uint32_t B = scan.run(
+        c.n, [&](int32_t f) { return wkb_feature_size((uint32_t)((const g_u8*)c.types)[f], c.geo, c.part, c.ring, f); },
+        [&](int32_t f, uint32_t before) { c.woff[f] = (int32_t)before; });  // (saturated only in a column that fails below)
     if ((int64_t)B > wd.byte_cap) {
         res.status = COVT_ERR_COUNT_MISMATCH;
         return;
