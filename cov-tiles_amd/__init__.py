@@ -2224,7 +2224,7 @@ _BUILD_SOURCES = (  # the Makefile's SRC, then its HDR, one to one
        "csrc/covt_props_plan.h",
        "csrc/covt_scratch.h", "csrc/covt_coop.h", "csrc/covt_wkb_plan.h", "csrc/covt_bbox_plan.h",
        "csrc/covt_measures_plan.h", "csrc/covt_select_plan.h", "csrc/covt_simplify_plan.h", "csrc/covt_geo_plan.h", "csrc/covt_arena.h", "csrc/covt_split_plan.h",
-       "csrc/covt_container.h", "csrc/covt_where_plan.h", "csrc/covt_mvt_plan.h"))
+       "csrc/covt_container.h", "csrc/covt_where_plan.h", "csrc/covt_mvt_plan.h", "csrc/covt_products.h"))
 
 
 def source_build_id() -> str:

@@ -31,4 +31,17 @@ COVT_BBOX_HD inline int64_t bbox_column_layout(int32_t n_features, uint32_t geom
     return bbox_align16(off + bbox_slice_bytes(b.n_features));
 }
 
+// The bounding-box product of a plan (covt_products.h).
+struct BboxProduct {
+    using Info = covt_bbox_info;
+    using Desc = covt_bbox_desc;
+    using Res = covt_bbox_result;
+    static constexpr uint32_t kTooLarge = COVT_BBOX_TOO_LARGE;
+    static constexpr bool kReadsSimplified = true;
+    COVT_BBOX_HD static int64_t layout(const covt_geom_info& g, int64_t off, Desc& d) {
+        return bbox_column_layout(g.n_features, (uint32_t)g.flags, off, d);
+    }
+    COVT_BBOX_HD static void fill(Info& b, const Desc& d) { b.off = d.off; }
+};
+
 #endif

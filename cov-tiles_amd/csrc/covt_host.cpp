@@ -25,13 +25,8 @@
 #include "covt_walk.h"
 #include "covt_props_plan.h"
 #include "covt_container.h"
-#include "covt_wkb_plan.h"
-#include "covt_bbox_plan.h"
-#include "covt_measures_plan.h"
-#include "covt_select_plan.h"
+#include "covt_products.h"
 #include "covt_where_plan.h"
-#include "covt_mvt_plan.h"
-#include "covt_simplify_plan.h"
 #include "covt_geo_plan.h"
 
 namespace {
@@ -573,6 +568,14 @@ struct HostShard {
     }
 };
 
+// one per-column product of a plan (covt_products.h): a column per geometry column and the size of its buffer
+template <class P>
+struct PlanProduct {
+    std::vector<typename P::Info> info;   // the records, tile order
+    std::vector<typename P::Desc> descs;  // the descriptors, launch order (that of gdescs)
+    int64_t bytes = 0;
+};
+
 struct covt_plan {
     covt_plan_options opts{};  // resolved options the plan was made with
     int32_t n_tiles = 0;
@@ -588,24 +591,11 @@ struct covt_plan {
     std::vector<covt_geom_desc> gdescs;  // launch order: largest first
     std::vector<int32_t> gextent;        // the extent of each geometry column's layer, tile order
     int64_t asm_bytes = 0;
-    std::vector<covt_wkb_info> winfo;    // WKB columns, tile order (one per geometry column)
-    std::vector<covt_wkb_desc> wdescs;   // launch order (that of gdescs)
-    int64_t wkb_bytes = 0;
-    std::vector<covt_bbox_info> binfo;   // bounding-box columns, tile order (one per geometry column)
-    std::vector<covt_bbox_desc> bdescs;  // launch order (that of gdescs)
-    int64_t bbox_bytes = 0;
-    std::vector<covt_measures_info> minfo;   // measures columns, tile order (one per geometry column)
-    std::vector<covt_measures_desc> mdescs;  // launch order (that of gdescs)
-    int64_t measures_bytes = 0;
-    std::vector<covt_select_info> sinfo;   // select columns, tile order (one per geometry column)
-    std::vector<covt_select_desc> sdescs;  // launch order (that of gdescs)
-    int64_t select_bytes = 0;
-    std::vector<covt_simplify_info> spinfo;   // simplify columns, tile order (one per geometry column)
-    std::vector<covt_simplify_desc> spdescs;  // launch order (that of gdescs)
-    int64_t simplify_bytes = 0;
-    std::vector<covt_mvt_info> mvinfo;        // mvt columns, tile order (one per geometry column)
-    std::vector<covt_mvt_desc> mvdescs;       // launch order (that of gdescs)
-    int64_t mvt_bytes = 0;
+    Products::Each<PlanProduct> products;  // the per-column products (covt_products.h), one column per geometry column
+    template <class P>
+    PlanProduct<P>& product() { return std::get<PlanProduct<P>>(products); }
+    template <class P>
+    const PlanProduct<P>& product() const { return std::get<PlanProduct<P>>(products); }
     bool simplify_on = false;                 // covt_plan_set_simplify: the host conveniences read the simplified column
     int32_t simplify_shift = 0;               //   its uniform shift, or
     std::vector<int32_t> simplify_col_shift;  //   one per column in launch order (empty: uniform)
@@ -739,115 +729,19 @@ void plan_geometry(covt_plan* p, int32_t nthr) {
     });
 }
 
-// Products computed per geometry column (WKB, bounding boxes): one column each, slices laid out in tile
-// order by the product's layout rule, descriptors in the geometry descriptors' order.  `layout` is the rule
-// (column, offset, descriptor) -> next offset, `fill` copies the product's own offsets into the record.
-template <class Info, class Desc, class Layout, class Fill>
-int64_t plan_geometry_product(const covt_plan* p, std::vector<Info>& info, std::vector<Desc>& descs, Layout layout,
-                              Fill fill) {
+// The per-column products (covt_products.h): for each, one column per geometry column in a buffer of the
+// product's own, slices laid out in tile order by its layout rule, descriptors in the geometry descriptors' order.
+void plan_products(covt_plan* p) {
     const size_t nc = p->ginfo.size();
-    info.resize(nc);
-    descs.resize(nc);
-    int64_t off = 0;
-    for (size_t c = 0; c < nc; ++c) {
-        const covt_geom_info& g = p->ginfo[c];
-        Desc d{};
-        off = layout(g, off, d);
-        Info r{};
-        r.tile = g.tile;
-        r.layer = g.layer;
-        r.n_features = d.n_features;
-        r.desc_index = g.desc_index;
-        r.flags = d.flags;
-        fill(r, d);
-        info[c] = r;
-        descs[(size_t)g.desc_index] = d;
-    }
-    return off;
-}
-
-// WKB columns (include/covt.h "Geometry as WKB"): slices next to the assembly layout (covt_wkb_plan.h).
-void plan_wkb(covt_plan* p) {
-    p->wkb_bytes = plan_geometry_product(
-        p, p->winfo, p->wdescs,
-        [](const covt_geom_info& g, int64_t off, covt_wkb_desc& d) {
-            return wkb_column_layout(g.n_features, g.part_cap, g.ring_cap, g.coord_cap, (uint32_t)g.flags, off, d);
-        },
-        [](covt_wkb_info& w, const covt_wkb_desc& d) {
-            w.offsets_off = d.offsets_off;
-            w.bytes_off = d.bytes_off;
-            w.byte_cap = d.byte_cap;
-        });
-}
-
-// Bounding-box columns (include/covt.h "Geometry bounding boxes"): slices in a buffer of their own
-// (covt_bbox_plan.h).
-void plan_bbox(covt_plan* p) {
-    p->bbox_bytes = plan_geometry_product(
-        p, p->binfo, p->bdescs,
-        [](const covt_geom_info& g, int64_t off, covt_bbox_desc& d) {
-            return bbox_column_layout(g.n_features, (uint32_t)g.flags, off, d);
-        },
-        [](covt_bbox_info& b, const covt_bbox_desc& d) { b.off = d.off; });
-}
-
-// Measures columns (include/covt.h "Geometry measures"): slices in a buffer of their own, each with its
-// per-ring scratch (covt_measures_plan.h).
-void plan_measures(covt_plan* p) {
-    p->measures_bytes = plan_geometry_product(
-        p, p->minfo, p->mdescs,
-        [](const covt_geom_info& g, int64_t off, covt_measures_desc& d) {
-            return measures_column_layout(g.n_features, g.ring_cap, (uint32_t)g.flags, off, d);
-        },
-        [](covt_measures_info& m, const covt_measures_desc& d) {
-            m.off = d.off;
-            m.ring_cap = d.ring_cap;
-        });
-}
-
-// Select columns (include/covt.h "Feature selection"): slices in a buffer of their own, the compacted bytes
-// sized by the column's WKB capacity (covt_select_plan.h).
-void plan_select(covt_plan* p) {
-    p->select_bytes = plan_geometry_product(
-        p, p->sinfo, p->sdescs,
-        [](const covt_geom_info& g, int64_t off, covt_select_desc& d) {
-            return select_column_layout(g.n_features, g.part_cap, g.ring_cap, g.coord_cap, (uint32_t)g.flags, off, d);
-        },
-        [](covt_select_info& r, const covt_select_desc& d) {
-            r.off = d.off;
-            r.byte_cap = d.byte_cap;
-        });
-}
-
-// Simplify columns (include/covt.h "Geometry simplification"): slices in a buffer of their own, sized by the
-// geometry column's capacities (covt_simplify_plan.h).
-void plan_simplify(covt_plan* p) {
-    p->simplify_bytes = plan_geometry_product(
-        p, p->spinfo, p->spdescs,
-        [](const covt_geom_info& g, int64_t off, covt_simplify_desc& d) {
-            return simplify_column_layout(g.n_features, g.part_cap, g.ring_cap, g.coord_cap, (uint32_t)g.flags, off, d);
-        },
-        [](covt_simplify_info& r, const covt_simplify_desc& d) {
-            r.off = d.off;
-            r.part_cap = d.part_cap;
-            r.ring_cap = d.ring_cap;
-            r.coord_cap = d.coord_cap;
-        });
-}
-
-// MVT columns (include/covt.h "Geometry as MVT"): slices in a buffer of their own (covt_mvt_plan.h).
-void plan_mvt(covt_plan* p) {
-    p->mvt_bytes = plan_geometry_product(
-        p, p->mvinfo, p->mvdescs,
-        [](const covt_geom_info& g, int64_t off, covt_mvt_desc& d) {
-            return mvt_column_layout(g.n_features, g.ring_cap, g.coord_cap, (uint32_t)g.flags, off, d);
-        },
-        [](covt_mvt_info& r, const covt_mvt_desc& d) {
-            r.off = d.off;
-            r.byte_cap = d.byte_cap;
-            r.ring_cap = d.ring_cap;
-            r.coord_cap = d.coord_cap;
-        });
+    Products::for_each([&](auto product) {
+        using P = decltype(product);
+        PlanProduct<P>& s = p->product<P>();
+        s.info.resize(nc);
+        s.descs.resize(nc);
+        int64_t off = 0;
+        for (size_t c = 0; c < nc; ++c) off = product_record<P>(p->ginfo[c], off, s.info[c], s.descs.data());
+        s.bytes = off;
+    });
 }
 
 // Property (sub)columns (include/covt.h "Property columns"; CovtParser.decodePropertyColumn
@@ -1496,12 +1390,7 @@ int covt_plan_create_opts(const uint8_t* bytes, const uint64_t* tile_offsets, co
                 if (c < p->ginfo.size() && p->ginfo[c].tile == le.tile && p->ginfo[c].layer == le.layer)
                     p->gextent[c++] = le.extent;
     }
-    plan_wkb(p);
-    plan_bbox(p);
-    plan_measures(p);
-    plan_select(p);
-    plan_simplify(p);
-    plan_mvt(p);
+    plan_products(p);
     plan_property_layout(p);
     *out = p;
     return COVT_OK;
@@ -1739,12 +1628,52 @@ int decode_host_shards(const covt_plan* p, const uint8_t* bytes, uint64_t n_byte
 
 namespace {
 
-// the *_columns / *_descs accessors: the plan's records as they lie
+// The geometry and the property columns as products: not of the list (covt_products.h), each has a builder of its
+// own (plan_geometry, plan_property_layout), but the accessors and the host pipeline read them the same way.
+struct GeometryColumns {
+    using Info = covt_geom_info;
+    using Desc = covt_geom_desc;
+    using Res = covt_geom_result;
+    static constexpr bool kReadsSimplified = false;
+};
+struct PropertyColumns {
+    using Info = covt_prop_info;
+    using Desc = covt_prop_desc;
+    using Res = covt_prop_result;
+    static constexpr bool kReadsSimplified = false;
+};
+template <class P>
+struct ProductRef {  // a product's records, descriptors and buffer size where the plan keeps them
+    const std::vector<typename P::Info>& info;
+    const std::vector<typename P::Desc>& descs;
+    int64_t bytes;
+};
+template <class P>
+ProductRef<P> product_ref(const covt_plan* p) {
+    const PlanProduct<P>& s = p->product<P>();
+    return {s.info, s.descs, s.bytes};
+}
+template <>
+ProductRef<GeometryColumns> product_ref<GeometryColumns>(const covt_plan* p) { return {p->ginfo, p->gdescs, p->asm_bytes}; }
+template <>
+ProductRef<PropertyColumns> product_ref<PropertyColumns>(const covt_plan* p) { return {p->pinfo, p->pdescs, p->prop_bytes}; }
+
+// the *_bytes / *_columns / *_descs accessors: the plan's records as they lie
 template <class T>
-int copy_records(const std::vector<T>* v, T* out) {
-    if (!v || (!out && !v->empty())) return COVT_ERR_INVALID_ARG;
-    if (!v->empty()) std::memcpy(out, v->data(), v->size() * sizeof(T));
+int copy_records(const std::vector<T>& v, T* out) {
+    if (!out && !v.empty()) return COVT_ERR_INVALID_ARG;
+    if (!v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(T));
     return COVT_OK;
+}
+template <class P>
+int64_t bytes_of(const covt_plan* p) { return p ? product_ref<P>(p).bytes : 0; }
+template <class P>
+int columns_of(const covt_plan* p, typename P::Info* out) {
+    return p ? copy_records(product_ref<P>(p).info, out) : COVT_ERR_INVALID_ARG;
+}
+template <class P>
+int descs_of(const covt_plan* p, typename P::Desc* out) {
+    return p ? copy_records(product_ref<P>(p).descs, out) : COVT_ERR_INVALID_ARG;
 }
 
 // Device memory and the stream of one whole-plan call, released by scope.
@@ -1778,13 +1707,18 @@ struct PlanDev {
 // Whole plan on the current device, the one pipeline of the four *_host entry points below: the
 // caller's tile bytes [0, n_bytes) go to the device as they lie (the plan's offsets index them), then
 // decode, the assembly if the product reads it, the product's own launch and the copies back, on one
-// stream.  A product is its descriptor table `descs` (launch order), its records `info` (tile order;
-// their desc_index reorders the results), its buffer of `out_bytes` and launch(dev, d_descs, n, d_buf,
-// d_results, stream).  The first error wins; host_res is written on success only.
-template <class Info, class Desc, class Res, class Launch>
-int plan_product_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, const std::vector<Info>& info,
-                      const std::vector<Desc>& descs, int64_t out_bytes, uint8_t* host_out, Res* host_res,
-                      bool assemble_first, Launch launch) {
+// stream.  Product P is, in the plan, its descriptor table (launch order), its records (tile order; their
+// desc_index reorders the results) and its buffer's size, and here launch(dev, d_descs, n, d_buf, d_results,
+// stream).  The first error wins; host_res is written on success only.
+template <class P, class Launch>
+int plan_product_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, uint8_t* host_out,
+                      typename P::Res* host_res, bool assemble_first, Launch launch) {
+    using Desc = typename P::Desc;
+    using Res = typename P::Res;
+    const ProductRef<P> product = product_ref<P>(p);
+    const std::vector<typename P::Info>& info = product.info;
+    const std::vector<Desc>& descs = product.descs;
+    const int64_t out_bytes = product.bytes;
     if ((!bytes && n_bytes) || (!host_out && out_bytes) || (!host_res && !info.empty())) return COVT_ERR_INVALID_ARG;
     for (int32_t t = 0; t < p->n_tiles; ++t)
         if (p->tile_off[(size_t)t] + p->tile_size[(size_t)t] > n_bytes) return COVT_ERR_INVALID_ARG;
@@ -1794,16 +1728,16 @@ int plan_product_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes
     const size_t nd = p->descs.size(), nc = descs.size(), ng = p->gdescs.size();
     int st = COVT_OK;
     auto chk = [&](hipError_t e) { if (e != hipSuccess && st == COVT_OK) st = COVT_ERR_DEVICE; };
-    auto bytes_of = [](int64_t n) { return (size_t)std::max<int64_t>(n, 16); };
+    auto buf_bytes = [](int64_t n) { return (size_t)std::max<int64_t>(n, 16); };
     auto rows_of = [](size_t n, size_t elem) { return std::max<size_t>(n, 1) * elem; };
     DevMem m_in, m_out, m_asm, m_buf, m_desc, m_res, m_gdesc, m_gres, m_pdesc, m_pres;
     DevMem m_sbuf, m_sdesc, m_sgdesc, m_sgres, m_shift;  // covt_plan_set_simplify
-    // (the simplify product itself reads the assembled column)
-    const bool simplify = assemble_first && p->simplify_on && !std::is_same<Desc, covt_simplify_desc>::value;
+    const bool simplify = assemble_first && p->simplify_on && P::kReadsSimplified;
+    const PlanProduct<SimplifyProduct>& sp = p->product<SimplifyProduct>();
     chk(hipMalloc(&m_in.p, (size_t)n_bytes + COVT_INPUT_PADDING));
-    chk(hipMalloc(&m_out.p, bytes_of(p->out_bytes)));
-    if (assemble_first) chk(hipMalloc(&m_asm.p, bytes_of(p->asm_bytes)));
-    chk(hipMalloc(&m_buf.p, bytes_of(out_bytes)));
+    chk(hipMalloc(&m_out.p, buf_bytes(p->out_bytes)));
+    if (assemble_first) chk(hipMalloc(&m_asm.p, buf_bytes(p->asm_bytes)));
+    chk(hipMalloc(&m_buf.p, buf_bytes(out_bytes)));
     chk(hipMalloc(&m_desc.p, rows_of(nd, sizeof(covt_stream_desc))));
     chk(hipMalloc(&m_res.p, rows_of(nd, sizeof(covt_stream_result))));
     if (assemble_first) {
@@ -1835,15 +1769,15 @@ int plan_product_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes
         PlanDev use = dev;
         if (st == COVT_OK && simplify) {
             rg.resize(ng);
-            for (size_t k = 0; k < ng; ++k) rg[k] = simplify_retarget(p->gdescs[k], p->spdescs[k]);
+            for (size_t k = 0; k < ng; ++k) rg[k] = simplify_retarget(p->gdescs[k], sp.descs[k]);
             const std::vector<int32_t>& cs = p->simplify_col_shift;
-            chk(hipMalloc(&m_sbuf.p, bytes_of(p->simplify_bytes)));
+            chk(hipMalloc(&m_sbuf.p, buf_bytes(sp.bytes)));
             chk(hipMalloc(&m_sdesc.p, rows_of(ng, sizeof(covt_simplify_desc))));
             chk(hipMalloc(&m_sgdesc.p, rows_of(ng, sizeof(covt_geom_desc))));
             chk(hipMalloc(&m_sgres.p, rows_of(ng, sizeof(covt_geom_result))));
             chk(hipMalloc(&m_shift.p, rows_of(ng, sizeof(int32_t))));
             if (st == COVT_OK && ng) {
-                chk(hipMemcpyAsync(m_sdesc.p, p->spdescs.data(), ng * sizeof(covt_simplify_desc), hipMemcpyHostToDevice, s));
+                chk(hipMemcpyAsync(m_sdesc.p, sp.descs.data(), ng * sizeof(covt_simplify_desc), hipMemcpyHostToDevice, s));
                 chk(hipMemcpyAsync(m_sgdesc.p, rg.data(), ng * sizeof(covt_geom_desc), hipMemcpyHostToDevice, s));
                 if (!cs.empty()) chk(hipMemcpyAsync(m_shift.p, cs.data(), ng * sizeof(int32_t), hipMemcpyHostToDevice, s));
             }
@@ -1871,60 +1805,60 @@ int plan_product_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes
 extern "C" {
 
 int64_t covt_plan_num_geometry_columns(const covt_plan* p) { return p ? (int64_t)p->ginfo.size() : 0; }
-int64_t covt_plan_assembly_bytes(const covt_plan* p) { return p ? p->asm_bytes : 0; }
-int covt_plan_geometry_columns(const covt_plan* p, covt_geom_info* out) { return copy_records(p ? &p->ginfo : nullptr, out); }
-int covt_plan_geometry_descs(const covt_plan* p, covt_geom_desc* out) { return copy_records(p ? &p->gdescs : nullptr, out); }
+int64_t covt_plan_assembly_bytes(const covt_plan* p) { return bytes_of<GeometryColumns>(p); }
+int covt_plan_geometry_columns(const covt_plan* p, covt_geom_info* out) { return columns_of<GeometryColumns>(p, out); }
+int covt_plan_geometry_descs(const covt_plan* p, covt_geom_desc* out) { return descs_of<GeometryColumns>(p, out); }
 
 // decode, then the assembly as the product
 int covt_plan_assemble_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, uint8_t* host_asm,
                             covt_geom_result* host_gres) {
     if (!p) return COVT_ERR_INVALID_ARG;
-    return plan_product_host(p, bytes, n_bytes, p->ginfo, p->gdescs, p->asm_bytes, host_asm, host_gres, false,
+    return plan_product_host<GeometryColumns>(p, bytes, n_bytes, host_asm, host_gres, false,
                              [](const PlanDev& d, const covt_geom_desc* gdesc, int64_t n, uint8_t* buf,
                                 covt_geom_result* gres, hipStream_t s) {
                                  return covt_assemble_geometry_device(d.out, d.res, gdesc, n, buf, gres, s);
                              });
 }
 
-int64_t covt_plan_wkb_bytes(const covt_plan* p) { return p ? p->wkb_bytes : 0; }
-int covt_plan_wkb_columns(const covt_plan* p, covt_wkb_info* out) { return copy_records(p ? &p->winfo : nullptr, out); }
-int covt_plan_wkb_descs(const covt_plan* p, covt_wkb_desc* out) { return copy_records(p ? &p->wdescs : nullptr, out); }
+int64_t covt_plan_wkb_bytes(const covt_plan* p) { return bytes_of<WkbProduct>(p); }
+int covt_plan_wkb_columns(const covt_plan* p, covt_wkb_info* out) { return columns_of<WkbProduct>(p, out); }
+int covt_plan_wkb_descs(const covt_plan* p, covt_wkb_desc* out) { return descs_of<WkbProduct>(p, out); }
 
 // decode, assembly, WKB serialization
 int covt_plan_wkb_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, uint8_t* host_wkb,
                        covt_wkb_result* host_wres) {
     if (!p) return COVT_ERR_INVALID_ARG;
-    return plan_product_host(p, bytes, n_bytes, p->winfo, p->wdescs, p->wkb_bytes, host_wkb, host_wres, true,
+    return plan_product_host<WkbProduct>(p, bytes, n_bytes, host_wkb, host_wres, true,
                              [](const PlanDev& d, const covt_wkb_desc* wdesc, int64_t n, uint8_t* buf,
                                 covt_wkb_result* wres, hipStream_t s) {
                                  return covt_geometry_wkb_device(d.out, d.gdesc, d.asm_buf, d.gres, wdesc, n, buf, wres, s);
                              });
 }
 
-int64_t covt_plan_bbox_bytes(const covt_plan* p) { return p ? p->bbox_bytes : 0; }
-int covt_plan_bbox_columns(const covt_plan* p, covt_bbox_info* out) { return copy_records(p ? &p->binfo : nullptr, out); }
-int covt_plan_bbox_descs(const covt_plan* p, covt_bbox_desc* out) { return copy_records(p ? &p->bdescs : nullptr, out); }
+int64_t covt_plan_bbox_bytes(const covt_plan* p) { return bytes_of<BboxProduct>(p); }
+int covt_plan_bbox_columns(const covt_plan* p, covt_bbox_info* out) { return columns_of<BboxProduct>(p, out); }
+int covt_plan_bbox_descs(const covt_plan* p, covt_bbox_desc* out) { return descs_of<BboxProduct>(p, out); }
 
 // decode, assembly, bounding boxes
 int covt_plan_bbox_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, uint8_t* host_bbox,
                         covt_bbox_result* host_bres) {
     if (!p) return COVT_ERR_INVALID_ARG;
-    return plan_product_host(p, bytes, n_bytes, p->binfo, p->bdescs, p->bbox_bytes, host_bbox, host_bres, true,
+    return plan_product_host<BboxProduct>(p, bytes, n_bytes, host_bbox, host_bres, true,
                              [](const PlanDev& d, const covt_bbox_desc* bdesc, int64_t n, uint8_t* buf,
                                 covt_bbox_result* bres, hipStream_t s) {
                                  return covt_geometry_bbox_device(d.gdesc, d.asm_buf, d.gres, bdesc, n, buf, bres, s);
                              });
 }
 
-int64_t covt_plan_measures_bytes(const covt_plan* p) { return p ? p->measures_bytes : 0; }
-int covt_plan_measures_columns(const covt_plan* p, covt_measures_info* out) { return copy_records(p ? &p->minfo : nullptr, out); }
-int covt_plan_measures_descs(const covt_plan* p, covt_measures_desc* out) { return copy_records(p ? &p->mdescs : nullptr, out); }
+int64_t covt_plan_measures_bytes(const covt_plan* p) { return bytes_of<MeasuresProduct>(p); }
+int covt_plan_measures_columns(const covt_plan* p, covt_measures_info* out) { return columns_of<MeasuresProduct>(p, out); }
+int covt_plan_measures_descs(const covt_plan* p, covt_measures_desc* out) { return descs_of<MeasuresProduct>(p, out); }
 
 // decode, assembly, measures
 int covt_plan_measures_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, uint8_t* host_measures,
                             covt_measures_result* host_mres) {
     if (!p) return COVT_ERR_INVALID_ARG;
-    return plan_product_host(p, bytes, n_bytes, p->minfo, p->mdescs, p->measures_bytes, host_measures, host_mres, true,
+    return plan_product_host<MeasuresProduct>(p, bytes, n_bytes, host_measures, host_mres, true,
                              [](const PlanDev& d, const covt_measures_desc* mdesc, int64_t n, uint8_t* buf,
                                 covt_measures_result* mres, hipStream_t s) {
                                  return covt_geometry_measures_device(d.out, d.gdesc, d.asm_buf, d.gres, mdesc, n, buf,
@@ -1938,7 +1872,9 @@ int covt_geo_transform(int32_t crs, int32_t z, int32_t x, int32_t y, int32_t ext
     return geo_transform(crs, z, x, y, extent, *out);
 }
 
-int covt_plan_geometry_extents(const covt_plan* p, int32_t* out) { return copy_records(p ? &p->gextent : nullptr, out); }
+int covt_plan_geometry_extents(const covt_plan* p, int32_t* out) {
+    return p ? copy_records(p->gextent, out) : COVT_ERR_INVALID_ARG;
+}
 
 int covt_plan_geo_transforms(const covt_plan* p, int32_t crs, const int32_t* tile_zxy, covt_geo_xform* out,
                              uint32_t* kinds) {
@@ -1992,7 +1928,7 @@ int covt_plan_wkb_projected_host(const covt_plan* p, const uint8_t* bytes, uint6
     if (!p) return COVT_ERR_INVALID_ARG;
     GeoTable g;  // (outlives the pipeline's synchronize)
     if (const int st = g.make(p, crs, tile_zxy)) return st;
-    return plan_product_host(p, bytes, n_bytes, p->winfo, p->wdescs, p->wkb_bytes, host_wkb, host_wres, true,
+    return plan_product_host<WkbProduct>(p, bytes, n_bytes, host_wkb, host_wres, true,
                              [&g](const PlanDev& d, const covt_wkb_desc* wdesc, int64_t n, uint8_t* buf,
                                   covt_wkb_result* wres, hipStream_t s) {
                                  if (const int st = g.upload(s)) return st;
@@ -2007,7 +1943,7 @@ int covt_plan_bbox_projected_host(const covt_plan* p, const uint8_t* bytes, uint
     if (!p) return COVT_ERR_INVALID_ARG;
     GeoTable g;
     if (const int st = g.make(p, crs, tile_zxy)) return st;
-    return plan_product_host(p, bytes, n_bytes, p->binfo, p->bdescs, p->bbox_bytes, host_bbox, host_bres, true,
+    return plan_product_host<BboxProduct>(p, bytes, n_bytes, host_bbox, host_bres, true,
                              [&g](const PlanDev& d, const covt_bbox_desc* bdesc, int64_t n, uint8_t* buf,
                                   covt_bbox_result* bres, hipStream_t s) {
                                  if (const int st = g.upload(s)) return st;
@@ -2016,73 +1952,110 @@ int covt_plan_bbox_projected_host(const covt_plan* p, const uint8_t* bytes, uint
                              });
 }
 
-int64_t covt_plan_select_bytes(const covt_plan* p) { return p ? p->select_bytes : 0; }
-int covt_plan_select_columns(const covt_plan* p, covt_select_info* out) { return copy_records(p ? &p->sinfo : nullptr, out); }
-int covt_plan_select_descs(const covt_plan* p, covt_select_desc* out) { return copy_records(p ? &p->sdescs : nullptr, out); }
+int64_t covt_plan_select_bytes(const covt_plan* p) { return bytes_of<SelectProduct>(p); }
+int covt_plan_select_columns(const covt_plan* p, covt_select_info* out) { return columns_of<SelectProduct>(p, out); }
+int covt_plan_select_descs(const covt_plan* p, covt_select_desc* out) { return descs_of<SelectProduct>(p, out); }
 
 }  // extern "C"
 
 namespace {
 
 // a product the select pipeline computes on the way and keeps on the device: descriptors, buffer, results
-template <class Desc, class Res>
+template <class P>
 struct DevProduct {
     DevMem desc, buf, res;
-    int make(const std::vector<Desc>& descs, int64_t bytes, hipStream_t s) {
-        const size_t n = descs.size();
-        if (hipMalloc(&desc.p, std::max<size_t>(n, 1) * sizeof(Desc)) != hipSuccess ||
-            hipMalloc(&buf.p, (size_t)std::max<int64_t>(bytes, 16)) != hipSuccess ||
-            hipMalloc(&res.p, std::max<size_t>(n, 1) * sizeof(Res)) != hipSuccess)
+    int make(const covt_plan* p, hipStream_t s) {
+        const ProductRef<P> product = product_ref<P>(p);
+        const size_t n = product.descs.size();
+        if (hipMalloc(&desc.p, std::max<size_t>(n, 1) * sizeof(typename P::Desc)) != hipSuccess ||
+            hipMalloc(&buf.p, (size_t)std::max<int64_t>(product.bytes, 16)) != hipSuccess ||
+            hipMalloc(&res.p, std::max<size_t>(n, 1) * sizeof(typename P::Res)) != hipSuccess)
             return COVT_ERR_DEVICE;
-        if (n && hipMemcpyAsync(desc.p, descs.data(), n * sizeof(Desc), hipMemcpyHostToDevice, s) != hipSuccess)
+        if (n && hipMemcpyAsync(desc.p, product.descs.data(), n * sizeof(typename P::Desc), hipMemcpyHostToDevice, s) !=
+                     hipSuccess)
             return COVT_ERR_DEVICE;
         return COVT_OK;
     }
+    typename P::Desc* d() const { return desc.as<typename P::Desc>(); }
+    uint8_t* b() const { return buf.as<uint8_t>(); }
+    typename P::Res* r() const { return res.as<typename P::Res>(); }
 };
+
+// The select pipeline of covt_plan_select_host and covt_plan_select_where_host, which check their arguments:
+// decode, assembly, WKB in `crs`, select.  With `pred`: bounding boxes in `crs`, measures if the predicate reads
+// them, and the predicate before the select.  With `where` (and its bind table `bind`): the properties
+// materialized into a device-only buffer and the where pass after the geometric predicate (AND) or in its place
+// (WRITE); host_where_status may be null.
+int select_pipeline(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, int32_t crs, const int32_t* tile_zxy,
+                    const covt_select_pred* pred, const covt_where* where, const std::vector<int32_t>& bind,
+                    uint8_t* host_select, covt_select_result* host_sres, int32_t* host_where_status) {
+    const size_t ng = p->ginfo.size();
+    std::vector<int32_t> wst(where ? std::max<size_t>(ng, 1) : 0, 0);
+    GeoTable g;  // (this and the intermediate products outlive the pipeline's synchronize)
+    if (const int st = g.make(p, crs, tile_zxy)) return st;
+    DevProduct<WkbProduct> w;
+    DevProduct<BboxProduct> b;
+    DevProduct<MeasuresProduct> m;
+    DevProduct<PropertyColumns> pr;
+    DevMem d_where, d_bind, d_wst;
+    const int rc = plan_product_host<SelectProduct>(
+        p, bytes, n_bytes, host_select, host_sres, true,
+        [&](const PlanDev& d, const covt_select_desc* sdesc, int64_t n, uint8_t* buf, covt_select_result* sres,
+            hipStream_t s) {
+            const bool size = pred && (pred->flags & COVT_SELECT_MIN_SIZE) != 0;
+            const int64_t np = (int64_t)p->pdescs.size();
+            int st = g.upload(s);
+            if (st == COVT_OK) st = w.make(p, s);
+            if (st == COVT_OK && pred) st = b.make(p, s);
+            if (st == COVT_OK && size) st = m.make(p, s);
+            if (st == COVT_OK && where) st = pr.make(p, s);
+            if (st == COVT_OK && where &&
+                (hipMalloc(&d_where.p, sizeof(covt_where)) != hipSuccess ||
+                 hipMalloc(&d_bind.p, bind.size() * sizeof(int32_t)) != hipSuccess ||
+                 hipMalloc(&d_wst.p, wst.size() * sizeof(int32_t)) != hipSuccess ||
+                 hipMemcpyAsync(d_where.p, where, sizeof(covt_where), hipMemcpyHostToDevice, s) != hipSuccess ||
+                 hipMemcpyAsync(d_bind.p, bind.data(), bind.size() * sizeof(int32_t), hipMemcpyHostToDevice, s) != hipSuccess ||
+                 hipMemsetAsync(d_wst.p, 0, wst.size() * sizeof(int32_t), s) != hipSuccess))
+                st = COVT_ERR_DEVICE;
+            const covt_geo_xform* xf = g.dev.as<covt_geo_xform>();
+            if (st == COVT_OK && where)
+                st = covt_materialize_properties_device(d.in, d.out, d.res, pr.d(), np, pr.b(), pr.r(), s);
+            if (st == COVT_OK)
+                st = covt_geometry_wkb_projected_device(d.out, d.gdesc, d.asm_buf, d.gres, w.d(), n, w.b(), w.r(), xf,
+                                                        g.kinds, s);
+            if (st == COVT_OK && pred)
+                st = covt_geometry_bbox_projected_device(d.gdesc, d.asm_buf, d.gres, b.d(), n, b.b(), b.r(), xf, g.kinds, s);
+            if (st == COVT_OK && size)
+                st = covt_geometry_measures_device(d.out, d.gdesc, d.asm_buf, d.gres, m.d(), n, m.b(), m.r(), s);
+            if (st == COVT_OK && pred)
+                st = covt_select_predicate_device(b.d(), b.b(), b.r(), m.d(), m.b(), m.r(), sdesc, n, pred, buf, s);
+            if (st == COVT_OK && where)
+                st = covt_select_where_device(pr.d(), pr.b(), pr.r(), np, sdesc, n, d_where.as<covt_where>(),
+                                              d_bind.as<int32_t>(), pred ? COVT_WHERE_AND : COVT_WHERE_WRITE, buf,
+                                              d_wst.as<int32_t>(), s);
+            if (st == COVT_OK) st = covt_geometry_select_device(w.d(), w.b(), w.r(), sdesc, n, buf, sres, s);
+            if (st == COVT_OK && where && n &&
+                hipMemcpyAsync(wst.data(), d_wst.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess)
+                st = COVT_ERR_DEVICE;
+            return st;
+        });
+    if (rc == COVT_OK && where && host_where_status) {
+        const std::vector<covt_select_info>& sinfo = p->product<SelectProduct>().info;
+        for (size_t k = 0; k < ng; ++k) host_where_status[k] = wst[(size_t)sinfo[k].desc_index];
+    }
+    return rc;
+}
 
 }  // namespace
 
 extern "C" {
 
-// decode, assembly, WKB and bounding boxes in `crs`, measures if the predicate reads them, predicate, select
+// the select pipeline with the geometric predicate alone
 int covt_plan_select_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, int32_t crs,
                           const int32_t* tile_zxy, const covt_select_pred* pred, uint8_t* host_select,
                           covt_select_result* host_sres) {
     if (!p || !select_pred_valid(pred)) return COVT_ERR_INVALID_ARG;
-    GeoTable g;  // (this and the intermediate products outlive the pipeline's synchronize)
-    if (const int st = g.make(p, crs, tile_zxy)) return st;
-    DevProduct<covt_wkb_desc, covt_wkb_result> w;
-    DevProduct<covt_bbox_desc, covt_bbox_result> b;
-    DevProduct<covt_measures_desc, covt_measures_result> m;
-    return plan_product_host(
-        p, bytes, n_bytes, p->sinfo, p->sdescs, p->select_bytes, host_select, host_sres, true,
-        [&](const PlanDev& d, const covt_select_desc* sdesc, int64_t n, uint8_t* buf, covt_select_result* sres,
-            hipStream_t s) {
-            const bool size = (pred->flags & COVT_SELECT_MIN_SIZE) != 0;
-            int st = g.upload(s);
-            if (st == COVT_OK) st = w.make(p->wdescs, p->wkb_bytes, s);
-            if (st == COVT_OK) st = b.make(p->bdescs, p->bbox_bytes, s);
-            if (st == COVT_OK && size) st = m.make(p->mdescs, p->measures_bytes, s);
-            const covt_geo_xform* xf = g.dev.as<covt_geo_xform>();
-            if (st == COVT_OK)
-                st = covt_geometry_wkb_projected_device(d.out, d.gdesc, d.asm_buf, d.gres, w.desc.as<covt_wkb_desc>(), n,
-                                                        w.buf.as<uint8_t>(), w.res.as<covt_wkb_result>(), xf, g.kinds, s);
-            if (st == COVT_OK)
-                st = covt_geometry_bbox_projected_device(d.gdesc, d.asm_buf, d.gres, b.desc.as<covt_bbox_desc>(), n,
-                                                         b.buf.as<uint8_t>(), b.res.as<covt_bbox_result>(), xf, g.kinds, s);
-            if (st == COVT_OK && size)
-                st = covt_geometry_measures_device(d.out, d.gdesc, d.asm_buf, d.gres, m.desc.as<covt_measures_desc>(), n,
-                                                   m.buf.as<uint8_t>(), m.res.as<covt_measures_result>(), s);
-            if (st == COVT_OK)
-                st = covt_select_predicate_device(b.desc.as<covt_bbox_desc>(), b.buf.as<uint8_t>(),
-                                                  b.res.as<covt_bbox_result>(), m.desc.as<covt_measures_desc>(),
-                                                  m.buf.as<uint8_t>(), m.res.as<covt_measures_result>(), sdesc, n, pred,
-                                                  buf, s);
-            if (st == COVT_OK)
-                st = covt_geometry_select_device(w.desc.as<covt_wkb_desc>(), w.buf.as<uint8_t>(),
-                                                 w.res.as<covt_wkb_result>(), sdesc, n, buf, sres, s);
-            return st;
-        });
+    return select_pipeline(p, bytes, n_bytes, crs, tile_zxy, pred, nullptr, {}, host_select, host_sres, nullptr);
 }
 
 // the bind table of `w` over the plan's geometry and property records (covt_where_plan.h)
@@ -2092,84 +2065,23 @@ int covt_plan_where_bind(const covt_plan* p, const uint8_t* bytes, uint64_t n_by
                       n_bytes, out);
 }
 
-// covt_plan_select_host with a property predicate: the properties materialized into a device-only buffer, the
-// where pass after the geometric predicate (AND) or in its place (WRITE)
+// the select pipeline with a property predicate, and the geometric one if `pred` is given
 int covt_plan_select_where_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, int32_t crs,
                                 const int32_t* tile_zxy, const covt_select_pred* pred, const covt_where* where,
                                 uint8_t* host_select, covt_select_result* host_sres, int32_t* host_where_status) {
     if (!p || (pred && !select_pred_valid(pred)) || (!bytes && n_bytes)) return COVT_ERR_INVALID_ARG;
-    const size_t ng = p->ginfo.size();
-    std::vector<int32_t> bind(std::max<size_t>(ng, 1) * COVT_WHERE_MAX_CLAUSES, -1), wst(std::max<size_t>(ng, 1), 0);
+    std::vector<int32_t> bind(std::max<size_t>(p->ginfo.size(), 1) * COVT_WHERE_MAX_CLAUSES, -1);
     if (const int st = covt_plan_where_bind(p, bytes, n_bytes, where, bind.data())) return st;
-    GeoTable g;  // (this and the intermediate products outlive the pipeline's synchronize)
-    if (const int st = g.make(p, crs, tile_zxy)) return st;
-    DevProduct<covt_wkb_desc, covt_wkb_result> w;
-    DevProduct<covt_bbox_desc, covt_bbox_result> b;
-    DevProduct<covt_measures_desc, covt_measures_result> m;
-    DevProduct<covt_prop_desc, covt_prop_result> pr;
-    DevMem d_where, d_bind, d_wst;
-    const int rc = plan_product_host(
-        p, bytes, n_bytes, p->sinfo, p->sdescs, p->select_bytes, host_select, host_sres, true,
-        [&](const PlanDev& d, const covt_select_desc* sdesc, int64_t n, uint8_t* buf, covt_select_result* sres,
-            hipStream_t s) {
-            const bool size = pred && (pred->flags & COVT_SELECT_MIN_SIZE) != 0;
-            const int64_t np = (int64_t)p->pdescs.size();
-            int st = g.upload(s);
-            if (st == COVT_OK) st = w.make(p->wdescs, p->wkb_bytes, s);
-            if (st == COVT_OK && pred) st = b.make(p->bdescs, p->bbox_bytes, s);
-            if (st == COVT_OK && size) st = m.make(p->mdescs, p->measures_bytes, s);
-            if (st == COVT_OK) st = pr.make(p->pdescs, p->prop_bytes, s);
-            if (st == COVT_OK &&
-                (hipMalloc(&d_where.p, sizeof(covt_where)) != hipSuccess ||
-                 hipMalloc(&d_bind.p, bind.size() * sizeof(int32_t)) != hipSuccess ||
-                 hipMalloc(&d_wst.p, wst.size() * sizeof(int32_t)) != hipSuccess ||
-                 hipMemcpyAsync(d_where.p, where, sizeof(covt_where), hipMemcpyHostToDevice, s) != hipSuccess ||
-                 hipMemcpyAsync(d_bind.p, bind.data(), bind.size() * sizeof(int32_t), hipMemcpyHostToDevice, s) != hipSuccess ||
-                 hipMemsetAsync(d_wst.p, 0, wst.size() * sizeof(int32_t), s) != hipSuccess))
-                st = COVT_ERR_DEVICE;
-            const covt_geo_xform* xf = g.dev.as<covt_geo_xform>();
-            if (st == COVT_OK)
-                st = covt_materialize_properties_device(d.in, d.out, d.res, pr.desc.as<covt_prop_desc>(), np,
-                                                        pr.buf.as<uint8_t>(), pr.res.as<covt_prop_result>(), s);
-            if (st == COVT_OK)
-                st = covt_geometry_wkb_projected_device(d.out, d.gdesc, d.asm_buf, d.gres, w.desc.as<covt_wkb_desc>(), n,
-                                                        w.buf.as<uint8_t>(), w.res.as<covt_wkb_result>(), xf, g.kinds, s);
-            if (st == COVT_OK && pred)
-                st = covt_geometry_bbox_projected_device(d.gdesc, d.asm_buf, d.gres, b.desc.as<covt_bbox_desc>(), n,
-                                                         b.buf.as<uint8_t>(), b.res.as<covt_bbox_result>(), xf, g.kinds, s);
-            if (st == COVT_OK && size)
-                st = covt_geometry_measures_device(d.out, d.gdesc, d.asm_buf, d.gres, m.desc.as<covt_measures_desc>(), n,
-                                                   m.buf.as<uint8_t>(), m.res.as<covt_measures_result>(), s);
-            if (st == COVT_OK && pred)
-                st = covt_select_predicate_device(b.desc.as<covt_bbox_desc>(), b.buf.as<uint8_t>(),
-                                                  b.res.as<covt_bbox_result>(), m.desc.as<covt_measures_desc>(),
-                                                  m.buf.as<uint8_t>(), m.res.as<covt_measures_result>(), sdesc, n, pred,
-                                                  buf, s);
-            if (st == COVT_OK)
-                st = covt_select_where_device(pr.desc.as<covt_prop_desc>(), pr.buf.as<uint8_t>(),
-                                              pr.res.as<covt_prop_result>(), np, sdesc, n, d_where.as<covt_where>(),
-                                              d_bind.as<int32_t>(), pred ? COVT_WHERE_AND : COVT_WHERE_WRITE, buf,
-                                              d_wst.as<int32_t>(), s);
-            if (st == COVT_OK)
-                st = covt_geometry_select_device(w.desc.as<covt_wkb_desc>(), w.buf.as<uint8_t>(),
-                                                 w.res.as<covt_wkb_result>(), sdesc, n, buf, sres, s);
-            if (st == COVT_OK && n &&
-                hipMemcpyAsync(wst.data(), d_wst.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess)
-                st = COVT_ERR_DEVICE;
-            return st;
-        });
-    if (rc == COVT_OK && host_where_status)
-        for (size_t k = 0; k < ng; ++k) host_where_status[k] = wst[(size_t)p->sinfo[k].desc_index];
-    return rc;
+    return select_pipeline(p, bytes, n_bytes, crs, tile_zxy, pred, where, bind, host_select, host_sres, host_where_status);
 }
 
-int64_t covt_plan_simplify_bytes(const covt_plan* p) { return p ? p->simplify_bytes : 0; }
-int covt_plan_simplify_columns(const covt_plan* p, covt_simplify_info* out) { return copy_records(p ? &p->spinfo : nullptr, out); }
-int covt_plan_simplify_descs(const covt_plan* p, covt_simplify_desc* out) { return copy_records(p ? &p->spdescs : nullptr, out); }
+int64_t covt_plan_simplify_bytes(const covt_plan* p) { return bytes_of<SimplifyProduct>(p); }
+int covt_plan_simplify_columns(const covt_plan* p, covt_simplify_info* out) { return columns_of<SimplifyProduct>(p, out); }
+int covt_plan_simplify_descs(const covt_plan* p, covt_simplify_desc* out) { return descs_of<SimplifyProduct>(p, out); }
 
 int covt_plan_simplified_geometry_descs(const covt_plan* p, covt_geom_desc* out) {
     if (!p || (!out && !p->gdescs.empty())) return COVT_ERR_INVALID_ARG;
-    for (size_t k = 0; k < p->gdescs.size(); ++k) out[k] = simplify_retarget(p->gdescs[k], p->spdescs[k]);
+    for (size_t k = 0; k < p->gdescs.size(); ++k) out[k] = simplify_retarget(p->gdescs[k], p->product<SimplifyProduct>().descs[k]);
     return COVT_OK;
 }
 
@@ -2211,8 +2123,7 @@ int covt_plan_simplify_host(const covt_plan* p, const uint8_t* bytes, uint64_t n
         cs.resize(p->ginfo.size());
         if (const int st = covt_plan_simplify_shifts(p, tile_shift, cs.data())) return st;
     }
-    return plan_product_host(
-        p, bytes, n_bytes, p->spinfo, p->spdescs, p->simplify_bytes, host_simplify, host_gres, true,
+    return plan_product_host<SimplifyProduct>(p, bytes, n_bytes, host_simplify, host_gres, true,
         [&](const PlanDev& d, const covt_simplify_desc* sdesc, int64_t n, uint8_t* buf, covt_geom_result* gres,
             hipStream_t s) {
             if (tile_shift) {
@@ -2226,15 +2137,15 @@ int covt_plan_simplify_host(const covt_plan* p, const uint8_t* bytes, uint64_t n
         });
 }
 
-int64_t covt_plan_mvt_bytes(const covt_plan* p) { return p ? p->mvt_bytes : 0; }
-int covt_plan_mvt_columns(const covt_plan* p, covt_mvt_info* out) { return copy_records(p ? &p->mvinfo : nullptr, out); }
-int covt_plan_mvt_descs(const covt_plan* p, covt_mvt_desc* out) { return copy_records(p ? &p->mvdescs : nullptr, out); }
+int64_t covt_plan_mvt_bytes(const covt_plan* p) { return bytes_of<MvtProduct>(p); }
+int covt_plan_mvt_columns(const covt_plan* p, covt_mvt_info* out) { return columns_of<MvtProduct>(p, out); }
+int covt_plan_mvt_descs(const covt_plan* p, covt_mvt_desc* out) { return descs_of<MvtProduct>(p, out); }
 
 // decode, assembly (simplify while covt_plan_set_simplify is set), mvt
 int covt_plan_mvt_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, const covt_mvt_options* opts,
                        uint8_t* host_mvt, covt_mvt_result* host_mvres) {
     if (!p || !mvt_options_valid(opts)) return COVT_ERR_INVALID_ARG;
-    return plan_product_host(p, bytes, n_bytes, p->mvinfo, p->mvdescs, p->mvt_bytes, host_mvt, host_mvres, true,
+    return plan_product_host<MvtProduct>(p, bytes, n_bytes, host_mvt, host_mvres, true,
                              [opts](const PlanDev& d, const covt_mvt_desc* mdesc, int64_t n, uint8_t* buf,
                                     covt_mvt_result* mres, hipStream_t s) {
                                  return covt_geometry_mvt_device(d.out, d.gdesc, d.asm_buf, d.gres, mdesc, n, opts, buf,
@@ -2243,15 +2154,15 @@ int covt_plan_mvt_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_byte
 }
 
 int64_t covt_plan_num_property_columns(const covt_plan* p) { return p ? (int64_t)p->pinfo.size() : 0; }
-int64_t covt_plan_property_bytes(const covt_plan* p) { return p ? p->prop_bytes : 0; }
-int covt_plan_property_columns(const covt_plan* p, covt_prop_info* out) { return copy_records(p ? &p->pinfo : nullptr, out); }
-int covt_plan_property_descs(const covt_plan* p, covt_prop_desc* out) { return copy_records(p ? &p->pdescs : nullptr, out); }
+int64_t covt_plan_property_bytes(const covt_plan* p) { return bytes_of<PropertyColumns>(p); }
+int covt_plan_property_columns(const covt_plan* p, covt_prop_info* out) { return columns_of<PropertyColumns>(p, out); }
+int covt_plan_property_descs(const covt_plan* p, covt_prop_desc* out) { return descs_of<PropertyColumns>(p, out); }
 
 // decode, property materialization
 int covt_plan_properties_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, uint8_t* host_props,
                               covt_prop_result* host_pres) {
     if (!p) return COVT_ERR_INVALID_ARG;
-    return plan_product_host(p, bytes, n_bytes, p->pinfo, p->pdescs, p->prop_bytes, host_props, host_pres, false,
+    return plan_product_host<PropertyColumns>(p, bytes, n_bytes, host_props, host_pres, false,
                              [](const PlanDev& d, const covt_prop_desc* pdesc, int64_t n, uint8_t* buf,
                                 covt_prop_result* pres, hipStream_t s) {
                                  return covt_materialize_properties_device(d.in, d.out, d.res, pdesc, n, buf, pres, s);

@@ -48,4 +48,20 @@ COVT_MEASURES_HD inline int64_t measures_column_layout(int32_t n_features, int32
     return measures_align16(off + measures_slice_bytes(m.n_features, m.ring_cap));
 }
 
+// The measures product of a plan (covt_products.h).
+struct MeasuresProduct {
+    using Info = covt_measures_info;
+    using Desc = covt_measures_desc;
+    using Res = covt_measures_result;
+    static constexpr uint32_t kTooLarge = COVT_MEASURES_TOO_LARGE;
+    static constexpr bool kReadsSimplified = true;
+    COVT_MEASURES_HD static int64_t layout(const covt_geom_info& g, int64_t off, Desc& d) {
+        return measures_column_layout(g.n_features, g.ring_cap, (uint32_t)g.flags, off, d);
+    }
+    COVT_MEASURES_HD static void fill(Info& m, const Desc& d) {
+        m.off = d.off;
+        m.ring_cap = d.ring_cap;
+    }
+};
+
 #endif

@@ -63,6 +63,24 @@ COVT_MVT_HD inline int64_t mvt_column_layout(int32_t n_features, int32_t ring_ca
     return mvt_align16(off + mvt_slice_bytes(m.n_features, m.byte_cap, m.ring_cap, m.coord_cap));
 }
 
+// The MVT product of a plan (covt_products.h).
+struct MvtProduct {
+    using Info = covt_mvt_info;
+    using Desc = covt_mvt_desc;
+    using Res = covt_mvt_result;
+    static constexpr uint32_t kTooLarge = COVT_MVT_TOO_LARGE;
+    static constexpr bool kReadsSimplified = true;
+    COVT_MVT_HD static int64_t layout(const covt_geom_info& g, int64_t off, Desc& d) {
+        return mvt_column_layout(g.n_features, g.ring_cap, g.coord_cap, (uint32_t)g.flags, off, d);
+    }
+    COVT_MVT_HD static void fill(Info& r, const Desc& d) {
+        r.off = d.off;
+        r.byte_cap = d.byte_cap;
+        r.ring_cap = d.ring_cap;
+        r.coord_cap = d.coord_cap;
+    }
+};
+
 // the options a call accepts
 COVT_MVT_HD inline bool mvt_options_valid(const covt_mvt_options* o) {
     return o && o->size == (uint32_t)sizeof(covt_mvt_options) && !(o->flags & ~(uint32_t)COVT_MVT_ORIENT) && o->shift >= 0 &&

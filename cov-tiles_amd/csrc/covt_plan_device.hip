@@ -39,12 +39,16 @@
 #include "covt_walk.h"
 #include "covt_props_plan.h"
 #include "covt_container.h"
-#include "covt_wkb_plan.h"
-#include "covt_bbox_plan.h"
-#include "covt_measures_plan.h"
-#include "covt_select_plan.h"
-#include "covt_mvt_plan.h"
-#include "covt_simplify_plan.h"
+#include "covt_products.h"
+
+// one per-column product of a device plan (covt_products.h), built with the geometry records in the geometry
+// arena: records (tile order), descriptors (launch order) and the size of the product's buffer
+template <class P>
+struct DeviceProduct {
+    typename P::Info* info = nullptr;
+    typename P::Desc* desc = nullptr;
+    int64_t bytes = 0;
+};
 
 struct covt_device_plan {
     int dev = 0;
@@ -60,25 +64,12 @@ struct covt_device_plan {
     int64_t n_geo = 0, asm_bytes = 0;
     covt_geom_info* d_ginfo = nullptr;
     covt_geom_desc* d_gdesc = nullptr;
-    int64_t wkb_bytes = 0;         // WKB columns (built with the geometry records, in the geometry arena)
-    covt_wkb_info* d_winfo = nullptr;
-    covt_wkb_desc* d_wdesc = nullptr;
-    int64_t bbox_bytes = 0;        // bounding-box columns (likewise)
-    covt_bbox_info* d_binfo = nullptr;
-    covt_bbox_desc* d_bdesc = nullptr;
-    int64_t measures_bytes = 0;    // measures columns (likewise)
-    covt_measures_info* d_minfo = nullptr;
-    covt_measures_desc* d_mdesc = nullptr;
-    int64_t select_bytes = 0;      // select columns (likewise)
-    covt_select_info* d_sinfo = nullptr;
-    covt_select_desc* d_sdesc = nullptr;
-    int64_t simplify_bytes = 0;    // simplify columns (likewise), and the geometry descriptors that name them
-    covt_simplify_info* d_spinfo = nullptr;
-    covt_simplify_desc* d_spdesc = nullptr;
-    covt_geom_desc* d_sgdesc = nullptr;
-    int64_t mvt_bytes = 0;         // mvt columns (likewise)
-    covt_mvt_info* d_mvinfo = nullptr;
-    covt_mvt_desc* d_mvdesc = nullptr;
+    Products::Each<DeviceProduct> products;
+    template <class P>
+    DeviceProduct<P>& product() { return std::get<DeviceProduct<P>>(products); }
+    template <class P>
+    const DeviceProduct<P>& product() const { return std::get<DeviceProduct<P>>(products); }
+    covt_geom_desc* d_sgdesc = nullptr;  // the geometry descriptors that name the simplify product's columns
     void* prop_arena = nullptr;    // property columns (COVT_PLAN_PROPERTIES): records, infos, descriptors
     void* scratch = nullptr;       // creation-time scratch (the property walk's record slots), freed on the way
     int64_t n_props = 0, prop_bytes = 0;
@@ -2144,77 +2135,8 @@ __global__ void geom_descs(const covt_stream_info* __restrict__ info, covt_geom_
     gdesc[k] = d;
 }
 
-// Products computed per geometry column (covt_host.cpp plan_geometry_product): slices in tile order from
-// the product's layout rule, a record per column and its descriptor at the geometry descriptor's row.  A
-// product names its record and descriptor types, the rule and the offsets the record repeats.
-struct WkbProduct {  // covt_wkb_plan.h
-    using Info = covt_wkb_info;
-    using Desc = covt_wkb_desc;
-    static __device__ int64_t layout(const covt_geom_info& g, int64_t off, Desc& d) {
-        return wkb_column_layout(g.n_features, g.part_cap, g.ring_cap, g.coord_cap, (uint32_t)g.flags, off, d);
-    }
-    static __device__ void fill(Info& w, const Desc& d) {
-        w.offsets_off = d.offsets_off;
-        w.bytes_off = d.bytes_off;
-        w.byte_cap = d.byte_cap;
-    }
-};
-struct BboxProduct {  // covt_bbox_plan.h
-    using Info = covt_bbox_info;
-    using Desc = covt_bbox_desc;
-    static __device__ int64_t layout(const covt_geom_info& g, int64_t off, Desc& d) {
-        return bbox_column_layout(g.n_features, (uint32_t)g.flags, off, d);
-    }
-    static __device__ void fill(Info& b, const Desc& d) { b.off = d.off; }
-};
-struct MeasuresProduct {  // covt_measures_plan.h
-    using Info = covt_measures_info;
-    using Desc = covt_measures_desc;
-    static __device__ int64_t layout(const covt_geom_info& g, int64_t off, Desc& d) {
-        return measures_column_layout(g.n_features, g.ring_cap, (uint32_t)g.flags, off, d);
-    }
-    static __device__ void fill(Info& m, const Desc& d) {
-        m.off = d.off;
-        m.ring_cap = d.ring_cap;
-    }
-};
-struct SelectProduct {  // covt_select_plan.h
-    using Info = covt_select_info;
-    using Desc = covt_select_desc;
-    static __device__ int64_t layout(const covt_geom_info& g, int64_t off, Desc& d) {
-        return select_column_layout(g.n_features, g.part_cap, g.ring_cap, g.coord_cap, (uint32_t)g.flags, off, d);
-    }
-    static __device__ void fill(Info& r, const Desc& d) {
-        r.off = d.off;
-        r.byte_cap = d.byte_cap;
-    }
-};
-struct SimplifyProduct {  // covt_simplify_plan.h
-    using Info = covt_simplify_info;
-    using Desc = covt_simplify_desc;
-    static __device__ int64_t layout(const covt_geom_info& g, int64_t off, Desc& d) {
-        return simplify_column_layout(g.n_features, g.part_cap, g.ring_cap, g.coord_cap, (uint32_t)g.flags, off, d);
-    }
-    static __device__ void fill(Info& r, const Desc& d) {
-        r.off = d.off;
-        r.part_cap = d.part_cap;
-        r.ring_cap = d.ring_cap;
-        r.coord_cap = d.coord_cap;
-    }
-};
-struct MvtProduct {  // covt_mvt_plan.h
-    using Info = covt_mvt_info;
-    using Desc = covt_mvt_desc;
-    static __device__ int64_t layout(const covt_geom_info& g, int64_t off, Desc& d) {
-        return mvt_column_layout(g.n_features, g.ring_cap, g.coord_cap, (uint32_t)g.flags, off, d);
-    }
-    static __device__ void fill(Info& r, const Desc& d) {
-        r.off = d.off;
-        r.byte_cap = d.byte_cap;
-        r.ring_cap = d.ring_cap;
-        r.coord_cap = d.coord_cap;
-    }
-};
+// The per-column products (covt_products.h, as covt_host.cpp plan_products): slices in tile order from the
+// product's layout rule, a record per column and its descriptor at the geometry descriptor's row.
 // the geometry descriptors of the simplified columns (covt_plan_simplified_geometry_descs), launch order
 __global__ void simplified_descs(const covt_geom_desc* __restrict__ gdesc, const covt_simplify_desc* __restrict__ sdesc,
                                  int64_t nc, covt_geom_desc* __restrict__ out) {
@@ -2233,18 +2155,7 @@ __global__ void product_records(const covt_geom_info* __restrict__ ginfo, int64_
                                 typename P::Info* __restrict__ info, typename P::Desc* __restrict__ desc) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= nc) return;
-    const covt_geom_info& g = ginfo[c];
-    typename P::Desc d{};
-    (void)P::layout(g, off[c], d);
-    typename P::Info r{};
-    r.tile = g.tile;
-    r.layer = g.layer;
-    r.n_features = d.n_features;
-    r.desc_index = g.desc_index;
-    r.flags = d.flags;
-    P::fill(r, d);
-    info[c] = r;
-    desc[g.desc_index] = d;
+    (void)product_record<P>(ginfo[c], off[c], info[c], desc);
 }
 
 // a HIP (or hipcub) call of a function that returns a plan status
@@ -2269,22 +2180,24 @@ struct DeviceGuard {
 
 // One product of covt_device_plan_geometry.  Its slice of the geometry arena: records | descriptors | column
 // bytes | column offsets.  Over the nc finished geometry records (tile order): the bytes kernel, their scan, the
-// records kernel and the copy of the total to *total, which holds after the caller's synchronize.
+// records kernel and the copy of the total to out.bytes, which holds after the caller's synchronize.
 template <class P>
 struct ProductSlice {
     ArenaSlot<typename P::Info> info;
     ArenaSlot<typename P::Desc> desc;
     ArenaSlot<int64_t> bytes, off;
-    ProductSlice(ArenaLayout& a, size_t m)
-        : info(a.take<typename P::Info>(m)), desc(a.take<typename P::Desc>(m)), bytes(a.take<int64_t>(m + 1)),
-          off(a.take<int64_t>(m + 1)) {}
+    void take(ArenaLayout& a, size_t m) {
+        info = a.take<typename P::Info>(m);
+        desc = a.take<typename P::Desc>(m);
+        bytes = a.take<int64_t>(m + 1);
+        off = a.take<int64_t>(m + 1);
+    }
 };
 template <class P>
 int plan_product(const ProductSlice<P>& slice, void* arena, size_t m, int64_t nc, const covt_geom_info* ginfo,
-                 void* scan_mem, size_t scan_tmp, hipStream_t s, typename P::Info*& info, typename P::Desc*& desc,
-                 int64_t* total) {
-    info = slice.info.at(arena);
-    desc = slice.desc.at(arena);
+                 void* scan_mem, size_t scan_tmp, hipStream_t s, DeviceProduct<P>& out) {
+    typename P::Info* info = out.info = slice.info.at(arena);
+    typename P::Desc* desc = out.desc = slice.desc.at(arena);
     int64_t *bytes = slice.bytes.at(arena), *off = slice.off.at(arena);
     HIP_TRY(hipMemsetAsync(bytes, 0, (m + 1) * 8, s));
     if (nc <= 0) return COVT_OK;
@@ -2294,7 +2207,7 @@ int plan_product(const ProductSlice<P>& slice, void* arena, size_t m, int64_t nc
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_mem, scan_tmp, bytes, off, (int)(nc + 1), s));
     product_records<P><<<cb, 256, 0, s>>>(ginfo, nc, off, info, desc);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(total, off + nc, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&out.bytes, off + nc, 8, hipMemcpyDeviceToHost, s));
     return COVT_OK;
 }
 
@@ -2305,6 +2218,26 @@ int copy_to_host(int64_t n, Info* infos, const Info* d_infos, Desc* descs, const
     if (infos) HIP_TRY(hipMemcpy(infos, d_infos, (size_t)n * sizeof(Info), hipMemcpyDeviceToHost));
     if (descs) HIP_TRY(hipMemcpy(descs, d_descs, (size_t)n * sizeof(Desc), hipMemcpyDeviceToHost));
     return COVT_OK;
+}
+
+// the accessors of product P, which exists once covt_device_plan_geometry has built it
+template <class P>
+int64_t bytes_of(const covt_device_plan* p) { return p && p->geo_built ? p->product<P>().bytes : 0; }
+template <class P>
+const typename P::Desc* descs_device_of(const covt_device_plan* p) {
+    return p && p->geo_built ? p->product<P>().desc : nullptr;
+}
+template <class P>
+int copy_of(const covt_device_plan* p, typename P::Info* infos, typename P::Desc* descs) {
+    if (!p || !p->geo_built) return COVT_ERR_INVALID_ARG;
+    return copy_to_host(p->n_geo, infos, p->product<P>().info, descs, p->product<P>().desc);
+}
+// the launch wrappers: the geometry part of the plan, built at the first of them, then the pass
+template <class Launch>
+int with_geometry(covt_device_plan* p, void* hip_stream, Launch launch) {
+    if (!p) return COVT_ERR_INVALID_ARG;
+    const int st = covt_device_plan_geometry(p, hip_stream);
+    return st ? st : launch();
 }
 
 // The build of one plan (covt_device_plan_create_opts) in stages, run() in order; each returns a status and the
@@ -2836,12 +2769,8 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     const auto a_k0 = L.take<uint64_t>(m), a_k1 = L.take<uint64_t>(m);
     const auto a_v0 = L.take<uint32_t>(m), a_v1 = L.take<uint32_t>(m);
     const auto a_st = L.take<uint8_t>(sort_tmp), a_cs = L.take<uint8_t>(cscan_tmp);
-    const ProductSlice<WkbProduct> a_wkb(L, m);
-    const ProductSlice<BboxProduct> a_bbox(L, m);
-    const ProductSlice<MeasuresProduct> a_measures(L, m);
-    const ProductSlice<SelectProduct> a_select(L, m);
-    const ProductSlice<SimplifyProduct> a_simplify(L, m);
-    const ProductSlice<MvtProduct> a_mvt(L, m);
+    Products::Each<ProductSlice> a_products;
+    Products::for_each([&](auto product) { std::get<ProductSlice<decltype(product)>>(a_products).take(L, m); });
     const auto a_sgd = L.take<covt_geom_desc>(m);
     // the arena is the plan's only on success: a failed build frees it (a retry allocates afresh)
     StreamFree arena{nullptr, s};
@@ -2853,8 +2782,7 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     uint32_t* v1 = a_v1.at(g);
     uint8_t* cscan = a_cs.at(g);
     HIP_TRY(hipMemsetAsync(colbytes, 0, (m + 1) * 8, s));
-    int64_t asm_bytes = 0, wkb_bytes = 0, bbox_bytes = 0, measures_bytes = 0, select_bytes = 0, simplify_bytes = 0;
-    int64_t mvt_bytes = 0;
+    int64_t asm_bytes = 0;
     if (nc > 0) {
         geom_columns<<<(int)((ns + 255) / 256), 256, 0, s>>>(p->d_info, ns, p->format, gst, gpos, p->d_ginfo, colbytes);
         HIP_TRY(hipGetLastError());
@@ -2868,21 +2796,20 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
         HIP_TRY(hipGetLastError());
     }
     // the products' layouts over the finished records, descriptors at the geometry descriptors' rows
-    int st = plan_product(a_wkb, g, m, nc, p->d_ginfo, cscan, cscan_tmp, s, p->d_winfo, p->d_wdesc, &wkb_bytes);
-    if (st == COVT_OK)
-        st = plan_product(a_bbox, g, m, nc, p->d_ginfo, cscan, cscan_tmp, s, p->d_binfo, p->d_bdesc, &bbox_bytes);
-    if (st == COVT_OK)
-        st = plan_product(a_measures, g, m, nc, p->d_ginfo, cscan, cscan_tmp, s, p->d_minfo, p->d_mdesc, &measures_bytes);
-    if (st == COVT_OK)
-        st = plan_product(a_select, g, m, nc, p->d_ginfo, cscan, cscan_tmp, s, p->d_sinfo, p->d_sdesc, &select_bytes);
-    if (st == COVT_OK)
-        st = plan_product(a_simplify, g, m, nc, p->d_ginfo, cscan, cscan_tmp, s, p->d_spinfo, p->d_spdesc, &simplify_bytes);
-    if (st == COVT_OK)
-        st = plan_product(a_mvt, g, m, nc, p->d_ginfo, cscan, cscan_tmp, s, p->d_mvinfo, p->d_mvdesc, &mvt_bytes);
+    // (built here and handed to the plan on success: the totals arrive with the synchronize below)
+    Products::Each<DeviceProduct> built;
+    int st = COVT_OK;
+    Products::for_each([&](auto product) {
+        using P = decltype(product);
+        if (st == COVT_OK)
+            st = plan_product(std::get<ProductSlice<P>>(a_products), g, m, nc, p->d_ginfo, cscan, cscan_tmp, s,
+                              std::get<DeviceProduct<P>>(built));
+    });
     if (st) return st;
     p->d_sgdesc = a_sgd.at(g);
     if (nc > 0) {
-        simplified_descs<<<(int)((nc + 255) / 256), 256, 0, s>>>(p->d_gdesc, p->d_spdesc, nc, p->d_sgdesc);
+        simplified_descs<<<(int)((nc + 255) / 256), 256, 0, s>>>(
+            p->d_gdesc, std::get<DeviceProduct<SimplifyProduct>>(built).desc, nc, p->d_sgdesc);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(&asm_bytes, coloff + nc, 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -2892,12 +2819,7 @@ int covt_device_plan_geometry(covt_device_plan* p, void* hip_stream) {
     arena.q = nullptr;
     p->n_geo = nc;
     p->asm_bytes = asm_bytes;
-    p->wkb_bytes = wkb_bytes;
-    p->bbox_bytes = bbox_bytes;
-    p->measures_bytes = measures_bytes;
-    p->select_bytes = select_bytes;
-    p->simplify_bytes = simplify_bytes;
-    p->mvt_bytes = mvt_bytes;
+    p->products = built;
     p->geo_built = true;
     return COVT_OK;
 }
@@ -2927,120 +2849,103 @@ int covt_device_plan_geometry_copy(const covt_device_plan* p, covt_geom_info* in
     return copy_to_host(p->n_geo, infos, p->d_ginfo, descs, p->d_gdesc);
 }
 
-int64_t covt_device_plan_wkb_bytes(const covt_device_plan* p) { return p && p->geo_built ? p->wkb_bytes : 0; }
-const covt_wkb_desc* covt_device_plan_wkb_descs_device(const covt_device_plan* p) {
-    return p && p->geo_built ? p->d_wdesc : nullptr;
-}
+int64_t covt_device_plan_wkb_bytes(const covt_device_plan* p) { return bytes_of<WkbProduct>(p); }
+const covt_wkb_desc* covt_device_plan_wkb_descs_device(const covt_device_plan* p) { return descs_device_of<WkbProduct>(p); }
 int covt_device_plan_wkb_copy(const covt_device_plan* p, covt_wkb_info* infos, covt_wkb_desc* descs) {
-    if (!p || !p->geo_built) return COVT_ERR_INVALID_ARG;
-    return copy_to_host(p->n_geo, infos, p->d_winfo, descs, p->d_wdesc);
+    return copy_of<WkbProduct>(p, infos, descs);
 }
 int covt_device_plan_wkb(covt_device_plan* p, const uint8_t* d_decoded, const covt_stream_result* d_res,
                          const uint8_t* d_asm, const covt_geom_result* d_gres, uint8_t* d_wkb,
                          covt_wkb_result* d_wres, void* hip_stream) {
     (void)d_res;
-    if (!p) return COVT_ERR_INVALID_ARG;
-    const int st = covt_device_plan_geometry(p, hip_stream);
-    if (st) return st;
-    return covt_geometry_wkb_device(d_decoded, p->d_gdesc, d_asm, d_gres, p->d_wdesc, p->n_geo, d_wkb, d_wres,
-                                    hip_stream);
+    return with_geometry(p, hip_stream, [&] {
+        return covt_geometry_wkb_device(d_decoded, p->d_gdesc, d_asm, d_gres, p->product<WkbProduct>().desc, p->n_geo,
+                                        d_wkb, d_wres, hip_stream);
+    });
 }
 
-int64_t covt_device_plan_bbox_bytes(const covt_device_plan* p) { return p && p->geo_built ? p->bbox_bytes : 0; }
-const covt_bbox_desc* covt_device_plan_bbox_descs_device(const covt_device_plan* p) {
-    return p && p->geo_built ? p->d_bdesc : nullptr;
-}
+int64_t covt_device_plan_bbox_bytes(const covt_device_plan* p) { return bytes_of<BboxProduct>(p); }
+const covt_bbox_desc* covt_device_plan_bbox_descs_device(const covt_device_plan* p) { return descs_device_of<BboxProduct>(p); }
 int covt_device_plan_bbox_copy(const covt_device_plan* p, covt_bbox_info* infos, covt_bbox_desc* descs) {
-    if (!p || !p->geo_built) return COVT_ERR_INVALID_ARG;
-    return copy_to_host(p->n_geo, infos, p->d_binfo, descs, p->d_bdesc);
+    return copy_of<BboxProduct>(p, infos, descs);
 }
 int covt_device_plan_bbox(covt_device_plan* p, const uint8_t* d_asm, const covt_geom_result* d_gres, uint8_t* d_bbox,
                           covt_bbox_result* d_bres, void* hip_stream) {
-    if (!p) return COVT_ERR_INVALID_ARG;
-    const int st = covt_device_plan_geometry(p, hip_stream);
-    if (st) return st;
-    return covt_geometry_bbox_device(p->d_gdesc, d_asm, d_gres, p->d_bdesc, p->n_geo, d_bbox, d_bres, hip_stream);
+    return with_geometry(p, hip_stream, [&] {
+        return covt_geometry_bbox_device(p->d_gdesc, d_asm, d_gres, p->product<BboxProduct>().desc, p->n_geo, d_bbox,
+                                         d_bres, hip_stream);
+    });
 }
 
-int64_t covt_device_plan_measures_bytes(const covt_device_plan* p) { return p && p->geo_built ? p->measures_bytes : 0; }
+int64_t covt_device_plan_measures_bytes(const covt_device_plan* p) { return bytes_of<MeasuresProduct>(p); }
 const covt_measures_desc* covt_device_plan_measures_descs_device(const covt_device_plan* p) {
-    return p && p->geo_built ? p->d_mdesc : nullptr;
+    return descs_device_of<MeasuresProduct>(p);
 }
 int covt_device_plan_measures_copy(const covt_device_plan* p, covt_measures_info* infos, covt_measures_desc* descs) {
-    if (!p || !p->geo_built) return COVT_ERR_INVALID_ARG;
-    return copy_to_host(p->n_geo, infos, p->d_minfo, descs, p->d_mdesc);
+    return copy_of<MeasuresProduct>(p, infos, descs);
 }
 int covt_device_plan_measures(covt_device_plan* p, const uint8_t* d_decoded, const uint8_t* d_asm,
                               const covt_geom_result* d_gres, uint8_t* d_measures, covt_measures_result* d_mres,
                               void* hip_stream) {
-    if (!p) return COVT_ERR_INVALID_ARG;
-    const int st = covt_device_plan_geometry(p, hip_stream);
-    if (st) return st;
-    return covt_geometry_measures_device(d_decoded, p->d_gdesc, d_asm, d_gres, p->d_mdesc, p->n_geo, d_measures, d_mres,
-                                         hip_stream);
+    return with_geometry(p, hip_stream, [&] {
+        return covt_geometry_measures_device(d_decoded, p->d_gdesc, d_asm, d_gres, p->product<MeasuresProduct>().desc,
+                                             p->n_geo, d_measures, d_mres, hip_stream);
+    });
 }
 
-int64_t covt_device_plan_select_bytes(const covt_device_plan* p) { return p && p->geo_built ? p->select_bytes : 0; }
+int64_t covt_device_plan_select_bytes(const covt_device_plan* p) { return bytes_of<SelectProduct>(p); }
 const covt_select_desc* covt_device_plan_select_descs_device(const covt_device_plan* p) {
-    return p && p->geo_built ? p->d_sdesc : nullptr;
+    return descs_device_of<SelectProduct>(p);
 }
 int covt_device_plan_select_copy(const covt_device_plan* p, covt_select_info* infos, covt_select_desc* descs) {
-    if (!p || !p->geo_built) return COVT_ERR_INVALID_ARG;
-    return copy_to_host(p->n_geo, infos, p->d_sinfo, descs, p->d_sdesc);
+    return copy_of<SelectProduct>(p, infos, descs);
 }
 int covt_device_plan_select(covt_device_plan* p, const uint8_t* d_wkb, const covt_wkb_result* d_wres, uint8_t* d_select,
                             covt_select_result* d_sres, void* hip_stream) {
-    if (!p) return COVT_ERR_INVALID_ARG;
-    const int st = covt_device_plan_geometry(p, hip_stream);
-    if (st) return st;
-    return covt_geometry_select_device(p->d_wdesc, d_wkb, d_wres, p->d_sdesc, p->n_geo, d_select, d_sres, hip_stream);
+    return with_geometry(p, hip_stream, [&] {
+        return covt_geometry_select_device(p->product<WkbProduct>().desc, d_wkb, d_wres, p->product<SelectProduct>().desc,
+                                           p->n_geo, d_select, d_sres, hip_stream);
+    });
 }
 
-int64_t covt_device_plan_simplify_bytes(const covt_device_plan* p) { return p && p->geo_built ? p->simplify_bytes : 0; }
+int64_t covt_device_plan_simplify_bytes(const covt_device_plan* p) { return bytes_of<SimplifyProduct>(p); }
 const covt_simplify_desc* covt_device_plan_simplify_descs_device(const covt_device_plan* p) {
-    return p && p->geo_built ? p->d_spdesc : nullptr;
+    return descs_device_of<SimplifyProduct>(p);
 }
 const covt_geom_desc* covt_device_plan_simplified_geometry_descs_device(const covt_device_plan* p) {
     return p && p->geo_built ? p->d_sgdesc : nullptr;
 }
 int covt_device_plan_simplify_copy(const covt_device_plan* p, covt_simplify_info* infos, covt_simplify_desc* descs) {
-    if (!p || !p->geo_built) return COVT_ERR_INVALID_ARG;
-    return copy_to_host(p->n_geo, infos, p->d_spinfo, descs, p->d_spdesc);
+    return copy_of<SimplifyProduct>(p, infos, descs);
 }
 int covt_device_plan_simplify(covt_device_plan* p, const uint8_t* d_decoded, const uint8_t* d_asm,
                               const covt_geom_result* d_gres, int32_t shift, const int32_t* d_shift,
                               uint8_t* d_simplify, covt_geom_result* d_gres_out, void* hip_stream) {
-    if (!p) return COVT_ERR_INVALID_ARG;
-    const int st = covt_device_plan_geometry(p, hip_stream);
-    if (st) return st;
-    return covt_geometry_simplify_device(d_decoded, p->d_gdesc, d_asm, d_gres, p->d_spdesc, p->n_geo, shift, d_shift,
-                                         d_simplify, d_gres_out, hip_stream);
+    return with_geometry(p, hip_stream, [&] {
+        return covt_geometry_simplify_device(d_decoded, p->d_gdesc, d_asm, d_gres, p->product<SimplifyProduct>().desc,
+                                             p->n_geo, shift, d_shift, d_simplify, d_gres_out, hip_stream);
+    });
 }
 
-int64_t covt_device_plan_mvt_bytes(const covt_device_plan* p) { return p && p->geo_built ? p->mvt_bytes : 0; }
-const covt_mvt_desc* covt_device_plan_mvt_descs_device(const covt_device_plan* p) {
-    return p && p->geo_built ? p->d_mvdesc : nullptr;
-}
+int64_t covt_device_plan_mvt_bytes(const covt_device_plan* p) { return bytes_of<MvtProduct>(p); }
+const covt_mvt_desc* covt_device_plan_mvt_descs_device(const covt_device_plan* p) { return descs_device_of<MvtProduct>(p); }
 int covt_device_plan_mvt_copy(const covt_device_plan* p, covt_mvt_info* infos, covt_mvt_desc* descs) {
-    if (!p || !p->geo_built) return COVT_ERR_INVALID_ARG;
-    return copy_to_host(p->n_geo, infos, p->d_mvinfo, descs, p->d_mvdesc);
+    return copy_of<MvtProduct>(p, infos, descs);
 }
 int covt_device_plan_mvt(covt_device_plan* p, const uint8_t* d_decoded, const uint8_t* d_asm,
                          const covt_geom_result* d_gres, int32_t simplified, const covt_mvt_options* opts,
                          uint8_t* d_mvt, covt_mvt_result* d_mvres, void* hip_stream) {
-    if (!p) return COVT_ERR_INVALID_ARG;
-    const int st = covt_device_plan_geometry(p, hip_stream);
-    if (st) return st;
-    return covt_geometry_mvt_device(d_decoded, simplified ? p->d_sgdesc : p->d_gdesc, d_asm, d_gres, p->d_mvdesc, p->n_geo,
-                                    opts, d_mvt, d_mvres, hip_stream);
+    return with_geometry(p, hip_stream, [&] {
+        return covt_geometry_mvt_device(d_decoded, simplified ? p->d_sgdesc : p->d_gdesc, d_asm, d_gres,
+                                        p->product<MvtProduct>().desc, p->n_geo, opts, d_mvt, d_mvres, hip_stream);
+    });
 }
 
 int covt_device_plan_assemble(covt_device_plan* p, const uint8_t* d_decoded, const covt_stream_result* d_res,
                               uint8_t* d_asm, covt_geom_result* d_gres, void* hip_stream) {
-    if (!p) return COVT_ERR_INVALID_ARG;
-    const int st = covt_device_plan_geometry(p, hip_stream);
-    if (st) return st;
-    return covt_assemble_geometry_device(d_decoded, d_res, p->d_gdesc, p->n_geo, d_asm, d_gres, hip_stream);
+    return with_geometry(p, hip_stream, [&] {
+        return covt_assemble_geometry_device(d_decoded, d_res, p->d_gdesc, p->n_geo, d_asm, d_gres, hip_stream);
+    });
 }
 
 int covt_device_plan_decode(const covt_device_plan* p, const uint8_t* d_in, uint8_t* d_out, covt_stream_result* d_res,

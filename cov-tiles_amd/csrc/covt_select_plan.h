@@ -46,6 +46,22 @@ COVT_SELECT_HD inline int64_t select_column_layout(int32_t n_features, int32_t p
     return select_align16(off + select_slice_bytes(s.n_features, s.byte_cap));
 }
 
+// The select product of a plan (covt_products.h).
+struct SelectProduct {
+    using Info = covt_select_info;
+    using Desc = covt_select_desc;
+    using Res = covt_select_result;
+    static constexpr uint32_t kTooLarge = COVT_SELECT_TOO_LARGE;
+    static constexpr bool kReadsSimplified = true;
+    COVT_SELECT_HD static int64_t layout(const covt_geom_info& g, int64_t off, Desc& d) {
+        return select_column_layout(g.n_features, g.part_cap, g.ring_cap, g.coord_cap, (uint32_t)g.flags, off, d);
+    }
+    COVT_SELECT_HD static void fill(Info& r, const Desc& d) {
+        r.off = d.off;
+        r.byte_cap = d.byte_cap;
+    }
+};
+
 // the predicate a call accepts: its size, known flags only, no NaN in the window or the minima
 COVT_SELECT_HD inline bool select_pred_valid(const covt_select_pred* p) {
     if (!p || p->size != (uint32_t)sizeof(covt_select_pred)) return false;

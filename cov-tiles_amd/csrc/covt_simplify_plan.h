@@ -62,6 +62,25 @@ COVT_SIMPLIFY_HD inline int64_t simplify_column_layout(int32_t n_features, int32
     return simplify_align16(off + simplify_slice_bytes(s.n_features, s.part_cap, s.ring_cap, s.coord_cap));
 }
 
+// The simplify product of a plan (covt_products.h).  Its result is a geometry result: the simplified column's
+// counts.
+struct SimplifyProduct {
+    using Info = covt_simplify_info;
+    using Desc = covt_simplify_desc;
+    using Res = covt_geom_result;
+    static constexpr uint32_t kTooLarge = COVT_SIMPLIFY_TOO_LARGE;
+    static constexpr bool kReadsSimplified = false;  // the pass that writes the simplified column reads the assembled one
+    COVT_SIMPLIFY_HD static int64_t layout(const covt_geom_info& g, int64_t off, Desc& d) {
+        return simplify_column_layout(g.n_features, g.part_cap, g.ring_cap, g.coord_cap, (uint32_t)g.flags, off, d);
+    }
+    COVT_SIMPLIFY_HD static void fill(Info& r, const Desc& d) {
+        r.off = d.off;
+        r.part_cap = d.part_cap;
+        r.ring_cap = d.ring_cap;
+        r.coord_cap = d.coord_cap;
+    }
+};
+
 // the geometry descriptor whose out_off[0 .. 3] name the simplified column in the simplify buffer (the inputs,
 // the capacities and the two scratch offsets stay): what every pass that reads an assembled column takes
 COVT_SIMPLIFY_HD inline covt_geom_desc simplify_retarget(covt_geom_desc g, const covt_simplify_desc& s) {

@@ -39,4 +39,22 @@ COVT_WKB_HD inline int64_t wkb_column_layout(int32_t n_features, int32_t part_ca
     return wkb_align16(off + w.byte_cap);
 }
 
+// The WKB product of a plan (covt_products.h): its record, descriptor and result types, the layout rule over a
+// geometry column and the offsets the record repeats from the descriptor.
+struct WkbProduct {
+    using Info = covt_wkb_info;
+    using Desc = covt_wkb_desc;
+    using Res = covt_wkb_result;
+    static constexpr uint32_t kTooLarge = COVT_WKB_TOO_LARGE;
+    static constexpr bool kReadsSimplified = true;  // covt_plan_set_simplify: the pass takes the simplified column
+    COVT_WKB_HD static int64_t layout(const covt_geom_info& g, int64_t off, Desc& d) {
+        return wkb_column_layout(g.n_features, g.part_cap, g.ring_cap, g.coord_cap, (uint32_t)g.flags, off, d);
+    }
+    COVT_WKB_HD static void fill(Info& w, const Desc& d) {
+        w.offsets_off = d.offsets_off;
+        w.bytes_off = d.bytes_off;
+        w.byte_cap = d.byte_cap;
+    }
+};
+
 #endif
