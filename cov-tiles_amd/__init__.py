@@ -373,6 +373,44 @@ class Where(C.Structure):
                                                              bytes(self.text[:self.text_len]))
 
 
+# geometry queries (include/covt.h "Geometry queries")
+QUERY_INTERSECTS, QUERY_WITHIN = 0, 1
+_QUERY_RELATIONS = {"intersects": QUERY_INTERSECTS, "within": QUERY_WITHIN}
+
+
+class SelectQuery(C.Structure):
+    """covt_select_query (include/covt.h "Geometry queries"): an exact relation of every feature with a closed,
+    axis-aligned int32 window in tile pixels, decided from the coordinates.  ``window`` = (x0, y0, x1, y1);
+    ``relation`` "intersects" keeps the features that share a point with the window (a polygon's interior
+    counts, its holes do not), "within" those that lie wholly inside it.  ``SelectQuery.at(x, y, radius)`` is
+    the point query with a tolerance: what is under this pixel."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("relation", C.c_int32), ("reserved", C.c_int32),
+                ("window", C.c_int32 * 4)]
+
+    def __init__(self, window=(0, 0, 0, 0), relation="intersects"):
+        super().__init__()
+        lib().covt_select_query_init(C.byref(self))
+        if isinstance(relation, str):
+            if relation not in _QUERY_RELATIONS:
+                raise IllegalArgumentException("unknown query relation %r" % (relation,))
+            relation = _QUERY_RELATIONS[relation]
+        w = [int(v) for v in window]
+        if len(w) != 4 or any(v < -2**31 or v > 2**31 - 1 for v in w):
+            raise IllegalArgumentException("a query window is four int32: (x0, y0, x1, y1)")
+        self.relation = int(relation)
+        self.window = (C.c_int32 * 4)(*w)
+
+    @classmethod
+    def at(cls, x: int, y: int, radius: int = 0, relation="intersects") -> "SelectQuery":
+        """The point (x, y), or with ``radius`` the square of that half-width around it (clamped to int32)."""
+        lo, hi = -2**31, 2**31 - 1
+        x, y, r = int(x), int(y), int(radius)
+        return cls((max(x - r, lo), max(y - r, lo), min(x + r, hi), min(y + r, hi)), relation)
+
+    def __repr__(self):
+        return "SelectQuery(window=%r, relation=%d)" % (tuple(self.window), self.relation)
+
+
 def where_dict_bounds():
     """(workgroup per column, wave per column): the dictionary sizes up to which the where kernel answers a
     STRING clause from a match bitmap in LDS (covt_where_dict_bound)."""
@@ -457,6 +495,10 @@ _SIGNATURES = {
     "covt_where_dict_bound": (_i32, [_i32]),
     "covt_select_where_device": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp]),
     "covt_plan_select_where_host": (_int, [_vp, _u8p, _u64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # geometry queries
+    "covt_select_query_init": (None, [_vp]),
+    "covt_select_query_device": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp]),
+    "covt_plan_select_query_host": (_int, [_vp, _u8p, _u64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # geometry simplification
     "covt_plan_simplify_shifts": (_int, [_vp, _vp, _vp]),
     "covt_geometry_simplify_device": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
@@ -1070,16 +1112,33 @@ class Plan:
         return MeasuresColumn(buf[o:o + 8 * n].view(np.float64), buf[o + 8 * n:o + 16 * n].view(np.float64),
                               buf[o + 16 * n:o + 20 * n].view(np.int32))
 
-    def select_host(self, pred: Optional["SelectPred"], crs=None, tile_zxy=None, where: Optional["Where"] = None):
+    def select_host(self, pred: Optional["SelectPred"], crs=None, tile_zxy=None, where: Optional["Where"] = None,
+                    query: Optional["SelectQuery"] = None):
         """H2D + decode + geometry assembly + WKB and bounding boxes (in `crs`, given the tiles' z, x, y) +
         measures if `pred` has a size cut + predicate + select + D2H (covt_plan_select_host).  With `where`
         (a plan made with PLAN_PROPERTIES) covt_plan_select_where_host: the property predicate ANDed into
         `pred`'s masks, or alone with pred=None; its per-column statuses in tile order are kept as
-        ``self.where_status``.
+        ``self.where_status``.  With `query` (covt_plan_select_query_host) the exact window query, in tile
+        pixels, ANDed into those masks, or alone with pred=None and where=None; its per-column statuses are kept
+        as ``self.query_status``.
         Returns (uint8 select buffer, results[num_geometry_columns] in tile order); see select_column."""
         buf = np.zeros(max(self.select_bytes, 1), dtype=np.uint8)
         res = np.zeros(max(self.num_geometry_columns, 1), dtype=SELECT_RESULT_DTYPE)
         zxy = _zxy(tile_zxy, self.n_tiles) if tile_zxy is not None else None
+        if query is not None:
+            wst = np.zeros(max(self.num_geometry_columns, 1), dtype=np.int32)
+            qst = np.zeros(max(self.num_geometry_columns, 1), dtype=np.int32)
+            _raise(lib().covt_plan_select_query_host(self._h, _ptr(self.blob, C.c_uint8), self.blob.size,
+                                                     CRS_TILE if crs is None else crs,
+                                                     zxy.ctypes.data if zxy is not None else None,
+                                                     C.byref(pred) if pred is not None else None,
+                                                     C.byref(where) if where is not None else None, C.byref(query),
+                                                     buf.ctypes.data, res.ctypes.data, wst.ctypes.data,
+                                                     qst.ctypes.data), "covt_plan_select_query_host")
+            if where is not None:
+                self.where_status = wst[:self.num_geometry_columns]
+            self.query_status = qst[:self.num_geometry_columns]
+            return buf[:self.select_bytes], res[:self.num_geometry_columns]
         if where is None:
             _raise(lib().covt_plan_select_host(self._h, _ptr(self.blob, C.c_uint8), self.blob.size,
                                                CRS_TILE if crs is None else crs,
@@ -1501,6 +1560,29 @@ class DeviceBatch:
         idx = self.plan.select["desc_index"]
         return st[idx] if idx.size else st
 
+    def select_query(self, query: "SelectQuery", mode: int = WHERE_WRITE, stream=None, simplified: bool = False):
+        """Enqueue the query pass: every column's keep mask from the exact relation of its features with the
+        query's window (WHERE_WRITE), or ANDed into the masks already there (WHERE_AND), after assemble() and
+        whatever wrote the masks on the same stream.  simplified: over the simplified column (after
+        simplify()).  Until select() runs, the head of each slice's bytes member holds the pass's scratch."""
+        import torch
+
+        gdesc, col, gres = self._column_source(simplified)
+        self._buffers("select")
+        if getattr(self, "d_query_status", None) is None:
+            self.d_query_status = torch.zeros(max(self.plan.num_geometry_columns, 1), dtype=torch.int32,
+                                              device=self.device)
+        _raise(lib().covt_select_query_device(self.d_out.data_ptr(), gdesc, col, gres, self.d_sdesc.data_ptr(),
+                                              self.plan.num_geometry_columns, C.byref(query), int(mode),
+                                              self.d_select.data_ptr(), self.d_query_status.data_ptr(),
+                                              _stream(stream, self.device)), "covt_select_query_device")
+
+    def query_status(self) -> np.ndarray:
+        """The query pass's per-column statuses in tile order, copied to the host (after select_query())."""
+        st = self.d_query_status.cpu().numpy()[:self.plan.num_geometry_columns]
+        idx = self.plan.select["desc_index"]
+        return st[idx] if idx.size else st
+
     def select(self, stream=None):
         """Enqueue the selection: every column's selection vector and compacted WKB from its keep mask (after
         wkb() and select_predicate(), or the caller's own masks, on the same stream)."""
@@ -1788,6 +1870,20 @@ class DevicePlan:
                                           d_status.data_ptr() if d_status is not None else None,
                                           _stream(stream, self.device)), "covt_select_where_device")
 
+    def select_query(self, d_out, d_asm, d_gres, query: "SelectQuery", d_select, mode: int = WHERE_WRITE,
+                     d_status=None, stream=None):
+        """Enqueue the query pass over this plan's geometry and select descriptors (after assemble() and whatever
+        wrote the masks on the same stream); d_out is the decode output, which holds the GeometryTypes;
+        d_status an int32 tensor of num_geometry_columns entries or None."""
+        self.geometry(stream)
+        L = lib()
+        _raise(L.covt_select_query_device(d_out.data_ptr(), L.covt_device_plan_geometry_descs_device(self._h),
+                                          d_asm.data_ptr(), d_gres.data_ptr(),
+                                          L.covt_device_plan_select_descs_device(self._h), self.num_geometry_columns,
+                                          C.byref(query), int(mode), d_select.data_ptr(),
+                                          d_status.data_ptr() if d_status is not None else None,
+                                          _stream(stream, self.device)), "covt_select_query_device")
+
     def simplify_copy(self):
         """(simplify records in tile order, descriptors in launch order) as host arrays (Plan.simplify /
         Plan.spdescs)."""
@@ -2068,7 +2164,8 @@ class CovtParser:
     def decode_covt(covt_buffer: bytes, fmt: int = FORMAT_GENC, id_mode: int = ID_FORMAT,
                     properties: bool = False, tile_id=None, crs: int = CRS_TILE,
                     select: Optional[SelectPred] = None, simplify: Optional[int] = None,
-                    where: Optional["Where"] = None, mvt: Optional["MvtOptions"] = None) -> List[LayerColumns]:
+                    where: Optional["Where"] = None, mvt: Optional["MvtOptions"] = None,
+                    query: Optional["SelectQuery"] = None) -> List[LayerColumns]:
         """CovtParser.decodeCovt (CovtParser.java:53-133) decoded on the GPU: Id + Geometry columns, and with
         ``properties`` every property column as a PropertyColumn (LayerColumns.properties, by name).
         ``tile_id`` = (z, x, y) and ``crs`` give every layer's wkb / bbox in that CRS (LayerColumns.crs).
@@ -2080,7 +2177,10 @@ class CovtParser:
         ``select`` both must hold); it implies the property plan, and a layer without a named column sees that
         clause's values as absent.
         ``mvt``, an MvtOptions, gives every layer's geometries as MVT command streams (LayerColumns.mvt), from the
-        simplified column when ``simplify`` is given; mvt_layer_bytes and mvt_tile_bytes wrap them into a tile."""
+        simplified column when ``simplify`` is given; mvt_layer_bytes and mvt_tile_bytes wrap them into a tile.
+        ``query``, a SelectQuery (tile pixels, whatever ``crs``), keeps in LayerColumns.selected only the features
+        in that exact relation with its window (with ``select`` and ``where`` all must hold), of the simplified
+        column when ``simplify`` is given."""
         if crs != CRS_TILE and tile_id is None:
             raise IllegalArgumentException("a CRS other than CRS_TILE needs the tile's (z, x, y)")
         geo = (crs, [tile_id]) if crs != CRS_TILE else (None, None)
@@ -2120,8 +2220,8 @@ class CovtParser:
                     lc = by_layer.get(int(plan.mvt["layer"][c]))
                     if lc is not None and int(vres["status"][c]) == OK:  # (a failed column keeps mvt = None)
                         lc.mvt = plan.mvt_column(vbuf, vres, c)
-            if select is not None or where is not None:
-                sbuf, sres = plan.select_host(select, *geo, where=where)
+            if select is not None or where is not None or query is not None:
+                sbuf, sres = plan.select_host(select, *geo, where=where, query=query)
                 for c in range(plan.num_geometry_columns):
                     lc = by_layer.get(int(plan.select["layer"][c]))
                     if lc is not None and int(sres["status"][c]) == OK:  # (a failed column keeps selected = None)
@@ -2219,12 +2319,13 @@ def version() -> str:
 _BUILD_SOURCES = (  # the Makefile's SRC, then its HDR, one to one
     ("csrc/covt_decode.hip", "csrc/covt_assemble.hip", "csrc/covt_props.hip", "csrc/covt_plan_device.hip",
      "csrc/covt_wkb.hip", "csrc/covt_bbox.hip", "csrc/covt_measures.hip", "csrc/covt_select.hip",
-     "csrc/covt_simplify.hip", "csrc/covt_where.hip", "csrc/covt_mvt.hip", "csrc/covt_host.cpp")
+     "csrc/covt_simplify.hip", "csrc/covt_where.hip", "csrc/covt_mvt.hip", "csrc/covt_query.hip", "csrc/covt_host.cpp")
     + ("../include/covt.h", "csrc/covt_internal.h", "csrc/covt_wave.h", "csrc/covt_segscan.h", "csrc/covt_walk.h",
        "csrc/covt_props_plan.h",
        "csrc/covt_scratch.h", "csrc/covt_coop.h", "csrc/covt_wkb_plan.h", "csrc/covt_bbox_plan.h",
        "csrc/covt_measures_plan.h", "csrc/covt_select_plan.h", "csrc/covt_simplify_plan.h", "csrc/covt_geo_plan.h", "csrc/covt_arena.h", "csrc/covt_split_plan.h",
-       "csrc/covt_container.h", "csrc/covt_where_plan.h", "csrc/covt_mvt_plan.h", "csrc/covt_products.h"))
+       "csrc/covt_container.h", "csrc/covt_where_plan.h", "csrc/covt_mvt_plan.h", "csrc/covt_products.h",
+       "csrc/covt_query_plan.h"))
 
 
 def source_build_id() -> str:

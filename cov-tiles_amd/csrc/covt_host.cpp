@@ -26,6 +26,7 @@
 #include "covt_props_plan.h"
 #include "covt_container.h"
 #include "covt_products.h"
+#include "covt_query_plan.h"
 #include "covt_where_plan.h"
 #include "covt_geo_plan.h"
 
@@ -1985,19 +1986,22 @@ struct DevProduct {
 // decode, assembly, WKB in `crs`, select.  With `pred`: bounding boxes in `crs`, measures if the predicate reads
 // them, and the predicate before the select.  With `where` (and its bind table `bind`): the properties
 // materialized into a device-only buffer and the where pass after the geometric predicate (AND) or in its place
-// (WRITE); host_where_status may be null.
+// (WRITE); host_where_status may be null.  With `query`: the query pass over the (simplified) column after
+// both, in AND mode if either wrote the masks, else in WRITE mode; host_query_status may be null.
 int select_pipeline(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, int32_t crs, const int32_t* tile_zxy,
                     const covt_select_pred* pred, const covt_where* where, const std::vector<int32_t>& bind,
-                    uint8_t* host_select, covt_select_result* host_sres, int32_t* host_where_status) {
+                    uint8_t* host_select, covt_select_result* host_sres, int32_t* host_where_status,
+                    const covt_select_query* query = nullptr, int32_t* host_query_status = nullptr) {
     const size_t ng = p->ginfo.size();
     std::vector<int32_t> wst(where ? std::max<size_t>(ng, 1) : 0, 0);
+    std::vector<int32_t> qst(query ? std::max<size_t>(ng, 1) : 0, 0);
     GeoTable g;  // (this and the intermediate products outlive the pipeline's synchronize)
     if (const int st = g.make(p, crs, tile_zxy)) return st;
     DevProduct<WkbProduct> w;
     DevProduct<BboxProduct> b;
     DevProduct<MeasuresProduct> m;
     DevProduct<PropertyColumns> pr;
-    DevMem d_where, d_bind, d_wst;
+    DevMem d_where, d_bind, d_wst, d_qst;
     const int rc = plan_product_host<SelectProduct>(
         p, bytes, n_bytes, host_select, host_sres, true,
         [&](const PlanDev& d, const covt_select_desc* sdesc, int64_t n, uint8_t* buf, covt_select_result* sres,
@@ -2017,6 +2021,10 @@ int select_pipeline(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, 
                  hipMemcpyAsync(d_bind.p, bind.data(), bind.size() * sizeof(int32_t), hipMemcpyHostToDevice, s) != hipSuccess ||
                  hipMemsetAsync(d_wst.p, 0, wst.size() * sizeof(int32_t), s) != hipSuccess))
                 st = COVT_ERR_DEVICE;
+            if (st == COVT_OK && query &&
+                (hipMalloc(&d_qst.p, qst.size() * sizeof(int32_t)) != hipSuccess ||
+                 hipMemsetAsync(d_qst.p, 0, qst.size() * sizeof(int32_t), s) != hipSuccess))
+                st = COVT_ERR_DEVICE;
             const covt_geo_xform* xf = g.dev.as<covt_geo_xform>();
             if (st == COVT_OK && where)
                 st = covt_materialize_properties_device(d.in, d.out, d.res, pr.d(), np, pr.b(), pr.r(), s);
@@ -2033,16 +2041,23 @@ int select_pipeline(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, 
                 st = covt_select_where_device(pr.d(), pr.b(), pr.r(), np, sdesc, n, d_where.as<covt_where>(),
                                               d_bind.as<int32_t>(), pred ? COVT_WHERE_AND : COVT_WHERE_WRITE, buf,
                                               d_wst.as<int32_t>(), s);
+            if (st == COVT_OK && query)
+                st = covt_select_query_device(d.out, d.gdesc, d.asm_buf, d.gres, sdesc, n, query,
+                                              pred || where ? COVT_WHERE_AND : COVT_WHERE_WRITE, buf, d_qst.as<int32_t>(), s);
             if (st == COVT_OK) st = covt_geometry_select_device(w.d(), w.b(), w.r(), sdesc, n, buf, sres, s);
             if (st == COVT_OK && where && n &&
                 hipMemcpyAsync(wst.data(), d_wst.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess)
                 st = COVT_ERR_DEVICE;
+            if (st == COVT_OK && query && n &&
+                hipMemcpyAsync(qst.data(), d_qst.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess)
+                st = COVT_ERR_DEVICE;
             return st;
         });
-    if (rc == COVT_OK && where && host_where_status) {
-        const std::vector<covt_select_info>& sinfo = p->product<SelectProduct>().info;
+    const std::vector<covt_select_info>& sinfo = p->product<SelectProduct>().info;
+    if (rc == COVT_OK && where && host_where_status)
         for (size_t k = 0; k < ng; ++k) host_where_status[k] = wst[(size_t)sinfo[k].desc_index];
-    }
+    if (rc == COVT_OK && query && host_query_status)
+        for (size_t k = 0; k < ng; ++k) host_query_status[k] = qst[(size_t)sinfo[k].desc_index];
     return rc;
 }
 
@@ -2073,6 +2088,23 @@ int covt_plan_select_where_host(const covt_plan* p, const uint8_t* bytes, uint64
     std::vector<int32_t> bind(std::max<size_t>(p->ginfo.size(), 1) * COVT_WHERE_MAX_CLAUSES, -1);
     if (const int st = covt_plan_where_bind(p, bytes, n_bytes, where, bind.data())) return st;
     return select_pipeline(p, bytes, n_bytes, crs, tile_zxy, pred, where, bind, host_select, host_sres, host_where_status);
+}
+
+// the select pipeline with any of the geometric predicate, the property predicate and the query pass
+int covt_plan_select_query_host(const covt_plan* p, const uint8_t* bytes, uint64_t n_bytes, int32_t crs,
+                                const int32_t* tile_zxy, const covt_select_pred* pred, const covt_where* where,
+                                const covt_select_query* query, uint8_t* host_select, covt_select_result* host_sres,
+                                int32_t* host_where_status, int32_t* host_query_status) {
+    if (!p || (pred && !select_pred_valid(pred)) || (query && !query_valid(query)) || (!pred && !where && !query) ||
+        (!bytes && n_bytes))
+        return COVT_ERR_INVALID_ARG;
+    std::vector<int32_t> bind;
+    if (where) {
+        bind.assign(std::max<size_t>(p->ginfo.size(), 1) * COVT_WHERE_MAX_CLAUSES, -1);
+        if (const int st = covt_plan_where_bind(p, bytes, n_bytes, where, bind.data())) return st;
+    }
+    return select_pipeline(p, bytes, n_bytes, crs, tile_zxy, pred, where, bind, host_select, host_sres, host_where_status,
+                           query, host_query_status);
 }
 
 int64_t covt_plan_simplify_bytes(const covt_plan* p) { return bytes_of<SimplifyProduct>(p); }

@@ -1273,6 +1273,95 @@ int covt_plan_select_where_host(const covt_plan* plan, const uint8_t* bytes, uin
                                 const int32_t* tile_zxy, const covt_select_pred* pred, const covt_where* where,
                                 uint8_t* host_select, covt_select_result* host_sres, int32_t* host_where_status);
 
+/* ---------------------------------------------------------------------------
+ * Geometry queries: the *query* pass.  For every feature of every assembled geometry column it decides one of
+ * two exact relations with a closed, axis-aligned window in tile pixels, from the coordinates themselves, and
+ * writes the keep masks covt_geometry_select_device consumes, or ANDs into them: what is under this pixel
+ * within r pixels, what meets this viewport, what lies wholly inside it.  (COVT_SELECT_WINDOW of the
+ * geometric predicate looks at the bounding box only: a prefilter.)
+ *
+ * The window is W = [wx0, wx1] x [wy0, wy1] = window[0 .. 3] = (wx0, wy0, wx1, wy1), int32, closed;
+ * in(p) = wx0 <= x <= wx1 && wy0 <= y <= wy1; Q = (wx0, wy0).  A point query is wx0 = wx1, wy0 = wy1; a point
+ * with tolerance r is the square of half-width r around it.  The window is always in tile pixels, whatever
+ * CRS the boxes were computed in, as the measures are.
+ *
+ * Segment test.  meets(a, b) says whether the closed segment ab and W share a point:
+ *   1. false if max(ax, bx) < wx0, or min(ax, bx) > wx1, or the same in y;
+ *   2. otherwise true if in(a) or in(b);
+ *   3. otherwise, for each of the four corners c of W, s = (bx - ax) * (cy - ay) - (by - ay) * (cx - ax):
+ *      true iff the four s are not all > 0 and not all < 0.
+ * Crossing test.  cross(a, b) = ((ay > qy) != (by > qy)) && ((D > 0) == (by > ay)) with
+ *   D = (qy - ay) * (bx - ax) - (qx - ax) * (by - ay).
+ * Every difference of two int32 has 33 bits and every product 66: the signs are those of the exact integers,
+ * no floating point.
+ *
+ * Per ring.  Ring r has the coordinates p_0 .. p_{m-1} as assembled (the closing vertex included, no implicit
+ * closing edge, as in the measures).  Three bits:
+ *   touch_r = m == 1 ? in(p_0) : OR over i <= m - 2 of meets(p_i, p_{i+1})      (m = 0: 0)
+ *   out_r   = OR over all i of !in(p_i)
+ *   par_r   = XOR over i <= m - 2 of cross(p_i, p_{i+1})
+ * Per feature f of GeometryTypes ordinal t, the OR and XOR over all rings of all its parts:
+ *   INTERSECTS_f = OR touch_r, or (t in {2, 5} and XOR par_r = 1).  (If no edge meets W, W lies wholly inside
+ *     or outside every ring; even-odd of one point of W over the rings is then "in a shell and in no hole".)
+ *   WITHIN_f = f has at least one coordinate and OR out_r = 0.  (W is convex: all vertices inside puts all
+ *     edges and interiors inside.)
+ * A feature without a coordinate gets 0 for both.  An inverted window (wx0 > wx1 or wy0 > wy1) gives 0 for
+ * both for every feature.
+ *
+ * Predicate and masks.  P_f is INTERSECTS_f or WITHIN_f, whichever `relation` names.  COVT_WHERE_WRITE:
+ * mask[f] = P_f; COVT_WHERE_AND: mask[f] = (mask[f] != 0) && P_f; the values are 0 or 1.
+ * Column rule.  A column gets the status of the other products' precheck and, in both modes, an all-zero
+ * mask, when its assembly result is not COVT_OK (that status), or its select descriptor is flagged
+ * COVT_SELECT_TOO_LARGE, is misaligned (off negative or not a multiple of 16), or is planned for another feature
+ * count than the assembly walked (COVT_ERR_INVALID_ARG).  (No byte is written at a negative off.)
+ *
+ * Scratch.  The pass is no product of its own: it writes into the select product's slice.  Its per-ring
+ * scratch, one byte per ring (touch | out << 1 | par << 2), lives in the first ring_cap bytes (the geometry
+ * descriptor's) of the slice's `bytes` member, which covt_geometry_select_device writes afterwards; byte_cap =
+ * 9 (n + part_cap) + 4 ring_cap + 16 coord_cap always holds it, and a hand-made descriptor with byte_cap <
+ * ring_cap gets COVT_ERR_INVALID_ARG by the column rule.  Between this pass and covt_geometry_select_device
+ * the head of `bytes` is unspecified; no other byte of the slice outside `mask` is touched.
+ * No atomics, every mask byte written exactly once, no allocation: the same input gives the same bytes and the
+ * pass can be captured in a HIP graph as it is.
+ * Out of scope: clipping to the window; queries in a CRS; distance to a feature; polygons as query shapes; a
+ * nonzero fill rule; the Java binding.
+ * ------------------------------------------------------------------------- */
+#define COVT_QUERY_INTERSECTS 0
+#define COVT_QUERY_WITHIN 1
+
+typedef struct covt_select_query {
+    uint32_t size;     /* sizeof(covt_select_query), set by covt_select_query_init */
+    uint32_t flags;    /* 0 */
+    int32_t relation;  /* COVT_QUERY_* */
+    int32_t reserved;  /* 0 */
+    int32_t window[4]; /* wx0, wy0, wx1, wy1 */
+} covt_select_query;
+
+void covt_select_query_init(covt_select_query* query); /* size set, INTERSECTS, the window (0, 0, 0, 0) */
+
+/* The query pass on `hip_stream`, after the assembly (or covt_geometry_simplify_device: with the simplified
+ * descriptors, buffer and results it runs on the simplified column unchanged) and, with COVT_WHERE_AND, after
+ * whatever wrote the masks, on the same stream.  d_decoded / d_gdesc / d_asm / d_gres as the measures pass
+ * takes them, d_sdesc the select descriptors (launch order), `query` in host memory, read before the call
+ * returns; mode COVT_WHERE_WRITE or COVT_WHERE_AND; d_select the select buffer (16-byte aligned); d_status
+ * n_columns statuses in launch order (may be null).  COVT_ERR_INVALID_ARG for a query with a wrong size, a
+ * nonzero flags or reserved or an unknown relation, an unknown mode, a negative n_columns or a null array.
+ * Asynchronous, capturable, allocates nothing. */
+int covt_select_query_device(const uint8_t* d_decoded, const covt_geom_desc* d_gdesc, const uint8_t* d_asm,
+                             const covt_geom_result* d_gres, const covt_select_desc* d_sdesc, int64_t n_columns,
+                             const covt_select_query* query, int32_t mode, uint8_t* d_select, int32_t* d_status,
+                             void* hip_stream);
+
+/* Convenience: the select pipeline of covt_plan_select_where_host with the query pass as a third optional stage
+ * after the geometric predicate (pred) and the where pass (where): in AND mode when one of them wrote the
+ * masks, in WRITE mode when both are null -- then no boxes and no properties are computed.  At least one of the
+ * three must be given; `where` needs a plan made with COVT_PLAN_PROPERTIES.  host_where_status /
+ * host_query_status: one status per column in tile order (each may be null).  Honours covt_plan_set_simplify. */
+int covt_plan_select_query_host(const covt_plan* plan, const uint8_t* bytes, uint64_t n_bytes, int32_t crs,
+                                const int32_t* tile_zxy, const covt_select_pred* pred, const covt_where* where,
+                                const covt_select_query* query, uint8_t* host_select, covt_select_result* host_sres,
+                                int32_t* host_where_status, int32_t* host_query_status);
+
 /* ---- Device-side plan ------------------------------------------------------------------------
  * covt_plan_create's Id / Geometry walk run on the GPU, for tiles already resident in HBM (the host
  * half of CovtParser.decodeCovt, CovtParser.java:53-133 / :574-652, without the round trip through
